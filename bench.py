@@ -29,6 +29,14 @@ sends each rank chunk k + 2 of ITS streams over RCCL (xGMI) while step k decodes
 design and reported beside value.  Every rank checks one step of its
 ensemble 0 against the transmitted bits in both legs.  value = symbols decoded by all
 ranks / max-over-ranks time.
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times the K steps
+and prints the line (metric, value, ms_per_step, the timed steps' per-kernel times).  --full
+adds every other leg after the timed steps, as one line: the CPU baseline, the checked step,
+the solo steps behind the roofline's *_alone figures, the delivered, sync-loss and C5 legs
+and, for N > 1, the C4 leg.  --dump-outputs DIR writes what the last timed step delivered
+as DIR/<name>.npy; the streams are seeded, so two builds run with the same arguments can be
+compared output for output.
 """
 import argparse
 import json
@@ -554,8 +562,20 @@ def main():
                     help="timed steps of the C5 leg (BASELINE configs[4], 16 ensembles x 16 DAB+ subchannels) run "
                          "after the C3 measurement at N = 1, reported as c5 in the same line (0: skip)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, every other leg and check: the CPU baseline, the checked step, the "
+                         "solo steps, the delivered, sync-loss and C5 legs and (N > 1) the C4 leg; without it the run "
+                         "sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step delivered (FIC, CRC flags, MSC, msc_valid; DAB+ records) as "
+                         "DIR/<name>.npy (float32; a fixed seeded sample of the large arrays, zeros where the run "
+                         "delivered nothing); N > 1: DIR/rank<r>/")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline alone: no leg after the timed steps
+        args.no_cpu_baseline = args.no_c4_fed = True
+        args.solo_steps = args.delivered_steps = args.sync_loss_steps = args.c5_steps = 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -575,9 +595,17 @@ def main():
     deliv_steps = args.delivered_steps + 1 if args.delivered_steps > 0 else 0     # + one untimed warm-up
     loss_steps = 2 * (args.sync_loss_steps + 1) if args.sync_loss_steps > 0 else 0  # two modes, + one each
     # (+ 2F: a stream that loses sync skips frames and reaches the end of its samples sooner)
-    total_frames = F * (args.warmup + args.steps + 1 + args.solo_steps + deliv_steps + loss_steps + (2 if loss_steps else 0)) + 1
-    ens = Ensemble(total_frames, subch=SUBCH, snr_db=30.0, cfo_hz=args.cfo, amplitude=AMPLITUDE)
+    tail_steps = 1 + args.solo_steps + deliv_steps + loss_steps + (2 if loss_steps else 0)
+    # The streams in HBM do not grow with --steps: a stream is its period of P frames repeated,
+    # and the warm-up and timed steps take a period every P / F steps, so from step k on the
+    # pipeline is handed the same buffer (k F // P) periods further on (Rewound) -- sample for
+    # sample the stream it would read from a buffer as long as the run.  The legs after the
+    # timed steps read on from where those stop, at most P / F - 1 steps into the buffer.
     P = period_frames(F, dabplus)
+    loop_steps = P // F
+    run_steps = args.warmup + args.steps
+    total_frames = F * (min(run_steps, loop_steps - 1) + tail_steps) + 1
+    ens = Ensemble(total_frames, subch=SUBCH, snr_db=30.0, cfo_hz=args.cfo, amplitude=AMPLITUDE)
     ctx = dabamd.Context(rank_device(local))
     stride = ens.length
     threads = gen_threads(world)
@@ -590,8 +618,9 @@ def main():
     t0 = time.time()
     diq = ctx.buf(E * stride * bps)
     seed0 = rank_seed0(rank, E)
-    truth = ens.generate_period(seed0, P, truth=True)
-    truth.pop("iq")
+    truth = ens.generate_period(seed0, P, truth=True) if args.full else None    # for the checks alone
+    if truth is not None:
+        truth.pop("iq")
     for g0 in range(0, E, 8):
         n = min(8, E - g0)
         per = ens.period_many(n, seed0=seed0 + g0, period=P, threads=threads)
@@ -620,14 +649,19 @@ def main():
     pipe.sync()
     acquire_ms = (time.perf_counter() - t_acq) * 1e3
 
+    def rewound(k):
+        """samples the streams' buffer lies further on at step k (whole periods)"""
+        return min(k, run_steps) // loop_steps * P * TF
+
     def step(k, download=False, partial=False):
         try:
-            r = pipe.run(diq, stride, [stride] * E, download=download, partial=partial)
+            sh = rewound(k)
+            r = pipe.run(Rewound(diq, sh * bps), stride, [stride + sh] * E, download=download, partial=partial)
         except dabamd.DabError:
             # which stream, where: every stream's state to stderr before the error ends the run
             for s in range(E):
                 x = pipe.state(s)
-                print(f"rank {rank} step {k} stream {s}: next_pos {x.next_pos} of {stride} "
+                print(f"rank {rank} step {k} stream {s}: next_pos {x.next_pos - sh} of {stride} "
                       f"frames_run {x.frames_run} cif_count {x.cif_count} synced {x.synced} "
                       f"acquiring {x.acquiring} resyncs {x.resyncs} acquisitions {x.acquisitions}", file=sys.stderr)
             raise
@@ -643,8 +677,9 @@ def main():
     barrier(dist)
     pipe.sync()
     t0 = time.perf_counter()
+    last = None
     for i in range(args.steps):
-        step(args.warmup + i)
+        last = step(args.warmup + i)
     pipe.sync()
     el = time.perf_counter() - t0
     barrier(dist)
@@ -654,19 +689,16 @@ def main():
     # kernel time per step and per launch over the timed region
     tm = {k: (v[0] / args.steps, v[0] / max(v[1], 1)) for k, v in tsum.items()}
 
+    if args.dump_outputs and last is not None:
+        dump_outputs(os.path.join(args.dump_outputs, f"rank{rank}") if world > 1 else args.dump_outputs,
+                     dabamd, pipe, last[0])
+
     # one extra step (outside the timed region) whose outputs are checked against the
     # transmitted bits of ensemble 0 of every rank: every FIB, every MSC subchannel
     ck = args.warmup + args.steps
-    st0 = pipe.state(0)
-    (fic, crc, msc, valid), dp = step(ck, download=True)
-    if pipe.packed:
-        msc = np.unpackbits(msc, axis=-1)
-    # every rank checks its ensemble 0 against the transmitted bits; rank 0 reports all
-    st1 = pipe.state(0)
-    check = check_step(truth, P, st0, st1, fic, crc, msc, valid, SUBCH)
-    check["rank"] = rank
-    check["seed"] = seed0
-    checks = gather_objects(dist, check)
+    checks, dp = None, None
+    if args.full:
+        checks, dp = checked_step(pipe, step, ck, truth, P, SUBCH, rank, seed0, dist)
     # the same workload with every kernel alone (after the measurement: never timed)
     tm_alone = {}
     if args.solo_steps > 0:
@@ -689,7 +721,7 @@ def main():
     if loss_steps and E >= 2:
         k0 = ck + 1 + args.solo_steps + deliv_steps
         sync_loss = sync_loss_leg(dabamd, ctx, pipe, step, k0, args.sync_loss_steps, E, F, stride, diq, dist,
-                                  el / args.steps * 1e3, args.iq_format)
+                                  el / args.steps * 1e3, args.iq_format, rewound(run_steps))
     c5 = None
     if args.c5_steps > 0 and args.workload == "c3" and world == 1 and dist is None:
         # BASELINE configs[4] in the same run (its own pipeline, after every C3 leg: never timed with
@@ -787,7 +819,7 @@ def main():
         "kernel_ms_per_launch": {k: v[1] for k, v in tm.items()},
         "kernel_ms_per_launch_alone": tm_alone,
         "kernel_timing": "HIP events on each launch's stream over the timed steps (rocprofv3 --kernel-trace agrees)",
-        "checked_step": checks[0] if world == 1 else checks,
+        "full": args.full,
         "dabplus_last_step": sf_ok,
         "gen_seconds": gen_s,
         "acquire_ms": {"streams": E, "ms": acquire_ms, "note": "initial null search of every stream (host-timed, first launch)"},
@@ -797,6 +829,8 @@ def main():
                               "int16 out per symbol) / 8 TB/s; the bytes the front end moves per symbol here: "
                               f"{bps} T_s in + 3072 out = {bps * TS + 3072} B",
     }
+    if checks is not None:
+        out["checked_step"] = checks[0] if world == 1 else checks
     if delivered is not None:
         out["delivered_symbols_per_s"] = delivered.pop("value")
         out["delivered"] = delivered
@@ -858,6 +892,68 @@ def main():
         out["c4_fed"] = c4
     if rank == 0:
         print(json.dumps(out))
+
+
+def checked_step(pipe, step, k, truth, P, subch, rank, seed0, dist):
+    """one step after the timed region whose downloaded outputs of this rank's ensemble 0 are
+    checked against the transmitted bits; returns every rank's check and the step's DAB+
+    download (None without DAB+ subchannels)"""
+    st0 = pipe.state(0)
+    (fic, crc, msc, valid), dp = step(k, download=True)
+    if pipe.packed:
+        msc = np.unpackbits(msc, axis=-1)
+    # every rank checks its ensemble 0 against the transmitted bits; rank 0 reports all
+    st1 = pipe.state(0)
+    check = check_step(truth, P, st0, st1, fic, crc, msc, valid, subch)
+    check["rank"] = rank
+    check["seed"] = seed0
+    return gather_objects(dist, check), dp
+
+
+DUMP_VALUES = {"fic": 6 << 20, "msc": 8 << 20}    # values kept of the large outputs (x 4 B as float32)
+
+
+def dump_sample(a, limit):
+    """a flattened, or -- above `limit` values -- a fixed sample of it (seed 0, in index order)"""
+    a = a.reshape(-1)
+    if a.size <= limit:
+        return a
+    return a[np.sort(np.random.default_rng(0).choice(a.size, limit, replace=False))]
+
+
+def dump_outputs(path, dabamd, pipe, valid):
+    """--dump-outputs: the device outputs of the last dabgpu_pipe_run (and DAB+ layer) as a
+    caller receives them -- fic [S, F, 4, 768 bits or 96 bytes], crc [S, F, 12], msc
+    [S, 4F, n_subch, stride] (bits, or bytes with --msc-format packed), msc_valid [S, 4F] --
+    written as float32 .npy files.  What a run leaves untouched is written as 0: MSC rows
+    with msc_valid = 0 and the stride's padding behind a codeword, FIC / CRC rows of frames
+    a stream did not run.  The large arrays are sampled (dump_sample)."""
+    S, F = pipe.S, pipe.F
+    pipe.sync()
+    os.makedirs(path, exist_ok=True)
+    ran = np.array([pipe.state(s).frames_run for s in range(S)])
+    frame_ok = np.arange(F)[None, :] < ran[:, None]
+    fic = pipe.fic_d.download(np.uint8, (S, F, 4, 96 if pipe.fic_packed else 768)) * frame_ok[:, :, None, None]
+    crc = pipe.crc_d.download(np.uint8, (S, F, 12)) * frame_ok[:, :, None]
+    arrays = {"fic": dump_sample(fic, DUMP_VALUES["fic"]), "crc": crc, "msc_valid": valid}
+    if pipe.subch:
+        ms = pipe.msc_stride_packed if pipe.packed else pipe.msc_stride
+        msc = pipe.msc_d.download(np.uint8, (S, 4 * F, len(pipe.subch), ms))
+        msc *= (valid != 0).astype(np.uint8)[:, :, None, None]
+        for k, sc in enumerate(pipe.subch):
+            msc[:, :, k, (3 if pipe.packed else 24) * sc.bitRate:] = 0
+        arrays["msc"] = dump_sample(msc, DUMP_VALUES["msc"])
+    if pipe.dp:
+        import ctypes as C
+        n = S * 4 * F * len(pipe.dp)
+        raw = pipe.sfi_d.download(np.uint8, n * C.sizeof(dabamd.Superframe))
+        info = np.frombuffer(raw.tobytes(), dtype=dabamd.SUPERFRAME_DTYPE)
+        done = info["status"] == 3
+        arrays["dabplus_status"] = info["status"]
+        arrays["dabplus_au_crc_ok"] = info["au_crc_ok"] * done
+        arrays["dabplus_n_corrected"] = info["n_corrected"] * done
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def c5_leg(dabamd, Ensemble, ctx, steps, warmup, F, cfo, iq_format, msc_format, threads, seed0=7000):
@@ -1117,7 +1213,7 @@ def delivered_leg(dabamd, ctx, pipe, step, k0, steps, E, F, subch, dabplus, dist
                        "(dabgpu_pipe_fetch), overlapping the next run")}
 
 
-def sync_loss_leg(dabamd, ctx, pipe, step, k0, steps, E, F, stride, diq, dist, base_ms, fmt="f32"):
+def sync_loss_leg(dabamd, ctx, pipe, step, k0, steps, E, F, stride, diq, dist, base_ms, fmt="f32", rewound=0):
     """The price of a sync loss (ofdm-processor.cpp:354-357: findIndex fails -> notSynced,
     the null search from where the stream is).  Before step k0 + 2j + 1 of each mode, stream
     j gets an interferer over 300,000 samples (1.5 frames) in the middle of that step's
@@ -1143,7 +1239,7 @@ def sync_loss_leg(dabamd, ctx, pipe, step, k0, steps, E, F, stride, diq, dist, b
         step(k0, partial=True)                             # untimed
         k0 += 1
         frames0 = [pipe.state(s).cif_count // 4 for s in range(E)]
-        pos0 = [pipe.state(s).next_pos for s in range(E)]
+        pos0 = [pipe.state(s).next_pos - rewound for s in range(E)]   # in the buffer (main's Rewound)
         losses = 0
         jammed = []
         for i in range(0, steps, 2):
@@ -1174,7 +1270,7 @@ def sync_loss_leg(dabamd, ctx, pipe, step, k0, steps, E, F, stride, diq, dist, b
         ms = el / steps * 1e3
         # lost for good: a search that reached the end of the stream's samples (a search still
         # running at the end of the leg is acquiring_at_end; one that found its null resumes)
-        lost = [s for s in jammed if st[s].next_pos + TF > stride]
+        lost = [s for s in jammed if st[s].next_pos - rewound + TF > stride]
         res[mode] = {"steps": steps, "losses": losses, "ms_per_step": ms, "streams_not_back": len(lost),
                      "hit_ms_per_loss": (ms - base_ms) * steps / max(losses, 1),
                      "hit_steps_per_loss": (ms - base_ms) * steps / max(losses, 1) / base_ms,
@@ -1202,6 +1298,17 @@ def _crc_flip():
     for q in range(3):
         m[256 * q + 240:256 * q + 256] = 1
     return m
+
+
+class Rewound:
+    """a stream buffer handed to the pipeline `nbytes` further on: sample p of every stream
+    reads the buffer's sample p - nbytes / (bytes per sample).  For cyclic streams and whole
+    periods that is the same sample; the caller keeps every position the pipeline reads
+    (from each stream's next_pos up to its n_avail) inside the buffer."""
+
+    def __init__(self, buf, nbytes):
+        import ctypes as C
+        self.ptr = C.c_void_p(buf.ptr.value - nbytes)
 
 
 class _TorchBuf:

@@ -5,7 +5,7 @@
 set -o pipefail
 O=$1; REPS=${2:-3}
 mkdir -p gpurun_out/$O
-A="--steps 8 --warmup 2 --no-cpu-baseline --solo-steps 0 --sync-loss-steps 0 --c5-steps 0"
+A="--full --steps 8 --warmup 2 --no-cpu-baseline --solo-steps 0 --sync-loss-steps 0 --c5-steps 0"
 for r in $(seq 1 $REPS); do
     for m in direct fetch; do
         timeout -k 10 240 python3 bench.py $A --delivered-mode $m > gpurun_out/$O/bench_${m}_$r.log 2>&1 || { tail -5 gpurun_out/$O/bench_${m}_$r.log; exit 1; }

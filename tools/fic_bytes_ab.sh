@@ -8,7 +8,7 @@ mkdir -p gpurun_out/$O
 timeout -k 10 300 python3 -u -m pytest tests/test_gpu_pipeline_oracle.py -x -q -m gpu -k "packed or fetch or compact" \
     --timeout 120 --timeout-method thread > gpurun_out/$O/tests.log 2>&1 || { tail -30 gpurun_out/$O/tests.log; exit 1; }
 tail -2 gpurun_out/$O/tests.log
-A="--steps 8 --warmup 2 --no-cpu-baseline --solo-steps 0 --sync-loss-steps 0 --c5-steps 0"
+A="--full --steps 8 --warmup 2 --no-cpu-baseline --solo-steps 0 --sync-loss-steps 0 --c5-steps 0"
 for r in $(seq 1 $REPS); do
     for f in bytes bits; do
         timeout -k 10 240 python3 bench.py $A --delivered-fic $f > gpurun_out/$O/bench_${f}_$r.log 2>&1 || { tail -5 gpurun_out/$O/bench_${f}_$r.log; exit 1; }

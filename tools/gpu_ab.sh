@@ -10,7 +10,7 @@ for r in $(seq 1 $reps); do
     lib=${spec%%:*}; env=${spec#*:}
     libp=$(pwd)/sdr-j-dab_amd/lib/libdabgpu.so; [ "$lib" != cur ] && libp=$L/libdabgpu_$lib.so
     tag=$(echo "$spec" | tr ':=/ ' '____')
-    env DABGPU_LIB=$libp $env timeout -k 10 240 python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline ${BENCH_ARGS} > $O/${tag}_$r.log 2>&1 || { tail -3 $O/${tag}_$r.log; exit 1; }
+    env DABGPU_LIB=$libp $env timeout -k 10 240 python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline ${BENCH_ARGS} > $O/${tag}_$r.log 2>&1 || { tail -3 $O/${tag}_$r.log; exit 1; }
     grep '"value"' $O/${tag}_$r.log | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); k=d['kernel_ms_per_launch']; a=d['kernel_ms_per_launch_alone']
 print('%-28s rep $r value %.4g M ms/step %.3f acs %.3f demod %.3f tb %.3f | alone acs %.3f demod %.3f tb %.3f ok=%s' % ('$spec', d['value']/1e6, d['ms_per_step'], k['msc_acs'], k['demod'], k['msc_traceback'], a['msc_acs'], a['demod'], a['msc_traceback'], d['checked_step']['msc_equal_transmitted']))"

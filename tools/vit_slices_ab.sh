@@ -10,7 +10,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 mkdir -p $R/gpurun_out/$O
 for r in $(seq 1 $REPS); do
   for k in "$@"; do
-    DABGPU_VIT_SLICES=$k timeout -k 10 240 python3 bench.py --steps 12 --warmup 3 --no-cpu-baseline --solo-steps 0 \
+    DABGPU_VIT_SLICES=$k timeout -k 10 240 python3 bench.py --full --steps 12 --warmup 3 --no-cpu-baseline --solo-steps 0 \
         --delivered-steps 0 --sync-loss-steps 0 --c5-steps 0 > $R/gpurun_out/$O/slices_${k}_$r.log 2>&1 \
         || { echo "K=$k failed"; tail -5 $R/gpurun_out/$O/slices_${k}_$r.log; exit 1; }
     grep '"value"' $R/gpurun_out/$O/slices_${k}_$r.log | python3 -c "
