@@ -265,7 +265,8 @@ int dabgpu_msc_deconvolve(dabgpu_ctx *ctx, const int16_t *frag_d, int64_t frag_s
  * stream.  Sync, AFC, DQPSK references and the 16-CIF time de-interleaver
  * state (dab-concurrent.cpp:162-175: the first 16 CIFs are warm-up) are
  * carried across calls.  subch lists the subchannels decoded for every
- * stream (the reference decodes one selected subchannel; this decodes all). */
+ * stream (the reference decodes one selected subchannel; this decodes all) until
+ * dabgpu_pipe_set_subch gives a stream a table of its own. */
 typedef struct dabgpu_pipe dabgpu_pipe;
 typedef struct {
     int32_t n_streams;
@@ -309,6 +310,49 @@ typedef struct {
 } dabgpu_frame_info;
 
 int dabgpu_pipe_create(dabgpu_ctx *ctx, const dabgpu_pipe_cfg *cfg, dabgpu_pipe **out);
+/* Per-stream subchannel tables, changeable between runs (entry points added within ABI 7;
+ * a pipeline that never calls them behaves as before).  Two multiplexes never share a
+ * subchannel organisation, and a receiver learns it from the FIC (FIG 0/1, 0/2) only after
+ * it has started decoding: the reference starts a new dabConcurrent for a newly selected
+ * subchannel (mscHandler::set_audioChannel / set_dataChannel, msc-handler.cpp), with its
+ * own 16-CIF warm-up (dab-concurrent.cpp:162-175).
+ * The caps size the pipeline; every stream's table then holds up to max_subch entries. */
+typedef struct {
+    int32_t max_subch;     /* table entries per stream; the MSC output's row count */
+    int32_t max_bitrate;   /* largest bitRate any entry may have (sizes decisions, msc_stride check) */
+    int32_t max_dabplus;   /* DAB+ entries per stream; the DAB+ outputs' slot count */
+    int32_t reserved;
+} dabgpu_pipe_caps;
+/* dabgpu_pipe_create with buffers sized by caps: cfg->subch[0..n_subch) is every stream's
+ * initial table (n_subch = 0: a FIC-only pipeline until dabgpu_pipe_set_subch).
+ * dabgpu_pipe_create is this call with the caps of its table (n_subch, its largest bitRate,
+ * its number of DAB+ entries).  Output layouts with caps:
+ *   msc_bits_d [n_streams][4*n_frames][max_subch][msc_stride]: entry k of a stream is row k;
+ *              rows of absent or not-yet-valid entries are left untouched
+ *   sf_bytes_d / info_d (and the compact form): max_dabplus in place of n_dabplus; DAB+
+ *              slot j of a stream is its j-th entry flagged DABGPU_SUBCH_DABPLUS; the info
+ *              records of absent slots have status -1. */
+int dabgpu_pipe_create_caps(dabgpu_ctx *ctx, const dabgpu_pipe_cfg *cfg, const dabgpu_pipe_caps *caps,
+                            dabgpu_pipe **out);
+/* Replace the table of one stream (stream = -1: of every stream) for the runs that follow.
+ * Validates as create does: DABGPU_E_UNSUP for an undefined protection or a bad DAB+
+ * bitRate, DABGPU_E_ARG for an entry outside its CUs, for n > max_subch, a bitRate above
+ * max_bitrate or more DAB+ entries than max_dabplus; on any error the table is unchanged.
+ * Waits for everything the pipeline has enqueued (as dabgpu_pipe_set_profiling): call
+ * dabgpu_pipe_dabplus for the last run before it.
+ * An entry whose index and all six fields are unchanged keeps its since_cif and DAB+ state
+ * and decodes without interruption.  Every other entry gets since_cif = the stream's
+ * cif_count at the call, its DAB+ ring and state zeroed (a new mp4Processor), and delivers
+ * CIF c only when the stream delivered c and c >= since_cif + 16: all 16 source CIFs of
+ * such a codeword lie at or after the switch, so the result equals a reference decoder
+ * started at the switch.  Initial entries have since_cif 0. */
+int dabgpu_pipe_set_subch(dabgpu_pipe *p, int stream, const dabgpu_subch *subch, int32_t n);
+/* The stream's table: subch[max_subch], *n entries, since_cif[max_subch] (or NULL). */
+int dabgpu_pipe_get_subch(dabgpu_pipe *p, int stream, dabgpu_subch *subch, int32_t *n, int64_t *since_cif);
+/* Per entry, for the last run: valid_h [n_streams][4*n_frames][max_subch], 1 where the
+ * stream delivered the CIF and it is past the entry's own warm-up (dabgpu_pipe_run's
+ * msc_valid_h stays stream level: past the stream's first 16 CIFs). */
+int dabgpu_pipe_msc_entry_valid(dabgpu_pipe *p, uint8_t *valid_h);
 int dabgpu_pipe_destroy(dabgpu_pipe *p);
 /* Acquire (notSynced/SyncOnNull/SyncOnEndNull, ofdm-processor.cpp:274-338)
  * every stream not yet synchronised from sample start_h[s] of its IQ (device,

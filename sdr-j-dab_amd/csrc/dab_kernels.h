@@ -130,6 +130,18 @@ struct VitJob {
     const int64_t *cif0s;           // [stream] CIF index (count delivered so far) of the batch's first CIF
     const int32_t *ncifs;           // [stream] CIFs of the batch the stream delivered (<= ncif)
     const int32_t *sub_start;       // startAddr*64 per subchannel (up to 55232: int32)
+    // SRC_MSC with per-stream subchannel tables (ent_prof non-null; null: the shared table
+    // above -- profile = sub, sub_start, delivery from CIF 16).  Entry e = stream * nsub + sub:
+    const int32_t *ent_prof;        // [S * nsub] index into prof (distinct profiles), -1: absent entry
+    const int32_t *ent_start;       // [S * nsub] startAddr*64
+    const int64_t *ent_since;       // [S * nsub] the stream's CIF count when the entry was set:
+                                    // it delivers CIF c once c - since >= 16
+    // ACS and traceback decode the active entries only: codeword = act pair * ncif + CIF
+    // over act[0..n_act) (entries e in (stream, sub) order), n_acs = n_act * ncif of them,
+    // which is also the codeword's decision row; n_cw stays the padded output row count
+    // S * ncif * nsub (rows of out: (stream * ncif + CIF) * nsub + sub)
+    const int32_t *act;
+    int32_t n_acs;
     // outputs
     uint32_t *dec;                  // decision words (dec_bytes(n_cw, max nbits) bytes)
     int64_t dec_ncw;                // rows of the decision buffer: >= dec_rows(n_cw)
@@ -160,8 +172,9 @@ struct DpJob {
     int32_t packed;                 // msc holds bytes (8 bits msb first), else one bit per byte
     const int64_t *cif0s;           // [stream] CIF index of the run's first CIF slot
     const int32_t *ncifs;           // [stream] CIFs the stream delivered in the run
-    const int32_t *dp_sub;          // [ndp] subchannel index of each DAB+ subchannel
-    const int16_t *dp_br;           // [ndp] its bitRate
+    const int32_t *dp_sub;          // [S][ndp] table entry of each DAB+ slot of the stream, -1: absent
+    const int16_t *dp_br;           // [S][ndp] its bitRate
+    const int64_t *dp_since;        // [S][ndp] its entry's since_cif (VitJob::ent_since)
     uint8_t *ring;                  // [S][ndp][120*DP_MAX_RS] 5-CIF byte rings
     DpState *state;                 // [S][ndp]
     uint8_t *code;                  // [S][ndp][ncif] scratch: 0 fire code failed, 2 rejected, 3 decoded

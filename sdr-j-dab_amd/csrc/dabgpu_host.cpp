@@ -854,7 +854,21 @@ struct dabgpu_pipe {
     int16_t threshold = 3;
     int16_t method = 1;              // freqSyncMethod
     bool scan = false;               // scanMode (No_Signal_Found after > 5 attempts)
-    std::vector<dabgpu_subch> sub;
+    // Subchannel tables, one per stream (dabgpu_pipe_set_subch): NSUB = caps.max_subch output
+    // rows and NDP = caps.max_dabplus DAB+ slots per stream, whatever the tables hold.
+    // since[s][k]: the stream's cif_count when entry k was set (it delivers from since + 16).
+    std::vector<std::vector<dabgpu_subch>> tab;
+    std::vector<std::vector<int64_t>> since;
+    int max_bitrate = 0;
+    // uniform: every stream has the same full table (NSUB entries, since 0) -- the kernels
+    // take the shared-table path (VitJob::ent_prof null); else the per-(stream, entry)
+    // descriptor tables below and the list of active pairs (rebuild_tables)
+    bool uniform = true;
+    int n_act = 0;
+    int32_t *ent_prof_d = nullptr, *ent_start_d = nullptr, *act_d = nullptr;
+    int64_t *ent_since_d = nullptr;
+    int64_t *dp_since_d = nullptr;   // [S][NDP]
+    std::vector<uint8_t> entry_valid;   // [S][4F][NSUB] of the last run (dabgpu_pipe_msc_entry_valid)
     std::vector<StreamSt> st;
     uint8_t *ring = nullptr;         // [S][R][75][3072] RING8 bytes (soft bit + 127, dab_kernels.h)
     Profile *prof_d = nullptr;       // [NSUB]
@@ -1050,44 +1064,167 @@ static int acq_async_setup(dabgpu_pipe *p) {
     return 0;
 }
 
+// A subchannel table against the reference's definitions and the pipeline's caps
+// (dabgpu_pipe_create_caps and dabgpu_pipe_set_subch validate alike)
+static int check_table(const dabgpu_subch *sub, int n, int max_subch, int max_bitrate, int max_dabplus) {
+    if (n < 0 || (n > 0 && !sub)) return fail(DABGPU_E_ARG, "bad subchannel table");
+    if (n > max_subch) return fail(DABGPU_E_ARG, "%d subchannels, the pipeline holds %d per stream", n, max_subch);
+    int ndp = 0;
+    for (int i = 0; i < n; i++) {
+        Profile P;
+        if (make_profile(sub[i], P)) return fail(DABGPU_E_UNSUP, "subchannel %d protection undefined", i);
+        if (sub[i].startAddr < 0 || sub[i].startAddr + sub[i].length > 864 || P.frag > sub[i].length * 64)
+            return fail(DABGPU_E_ARG, "subchannel %d does not fit its CUs", i);
+        if (sub[i].bitRate > max_bitrate)
+            return fail(DABGPU_E_ARG, "subchannel %d: bitRate %d above the pipeline's %d", i, sub[i].bitRate, max_bitrate);
+        if (!(sub[i].flags & DABGPU_SUBCH_DABPLUS)) continue;
+        // DAB+ subchannels (mp4Processor: RSDims = bitRate / 8, mp4processor.cpp:83-84)
+        const int br = sub[i].bitRate;
+        if (br < 8 || br % 8 || br / 8 > DP_MAX_RS)
+            return fail(DABGPU_E_UNSUP, "DAB+ subchannel %d: bitRate %d is not a multiple of 8 in [8, 384]", i, br);
+        ndp++;
+    }
+    if (ndp > max_dabplus) return fail(DABGPU_E_ARG, "%d DAB+ subchannels, the pipeline holds %d per stream", ndp, max_dabplus);
+    return 0;
+}
+
+static bool same_subch(const dabgpu_subch &a, const dabgpu_subch &b) {
+    return a.startAddr == b.startAddr && a.length == b.length && a.bitRate == b.bitRate && a.protLevel == b.protLevel &&
+           a.uepFlag == b.uepFlag && a.flags == b.flags;
+}
+
+// The device's descriptor tables from p->tab / p->since.  The caller has waited for the
+// pipeline's streams (in-flight kernels read the old tables): the tables are replaced.
+static int rebuild_tables(dabgpu_pipe *p) {
+    const int S = p->S, NS = p->NSUB;
+    p->uniform = true;
+    for (int s = 0; s < S && p->uniform; s++) {
+        if ((int)p->tab[s].size() != NS) p->uniform = false;
+        for (int k = 0; k < (int)p->tab[s].size() && p->uniform; k++)
+            if (p->since[s][k] != 0 || !same_subch(p->tab[s][k], p->tab[0][k])) p->uniform = false;
+    }
+    std::vector<Profile> profs;
+    std::vector<uint8_t> inv;
+    std::vector<int32_t> ss(std::max(1, NS), 0);
+    std::vector<int32_t> eprof(std::max<size_t>(1, (size_t)S * NS), -1), estart(eprof.size(), 0), act;
+    std::vector<int64_t> esince(eprof.size(), 0);
+    auto add_profile = [&](const dabgpu_subch &sc, bool dedup) {
+        Profile P;
+        (void)make_profile(sc, P);                      // validated by check_table
+        if (dedup)
+            for (size_t i = 0; i < profs.size(); i++) {
+                Profile Q = profs[i];
+                Q.inv_off = 0;
+                if (!memcmp(&Q, &P, sizeof P)) return (int32_t)i;
+            }
+        profs.push_back(P);
+        profs.back().inv_off = (int32_t)inv.size();
+        const std::vector<uint8_t> v = make_inv(P);
+        inv.insert(inv.end(), v.begin(), v.end());
+        return (int32_t)profs.size() - 1;
+    };
+    if (p->uniform) {                                   // profile k = entry k, as the kernels index it
+        for (int k = 0; k < NS; k++) {
+            add_profile(p->tab[0][k], false);
+            ss[k] = p->tab[0][k].startAddr * 64;
+        }
+        p->n_act = S * NS;
+    } else {
+        // distinct profiles (and their inverse tables) once, whatever streams use them
+        for (int s = 0; s < S; s++)
+            for (int k = 0; k < (int)p->tab[s].size(); k++) {
+                const size_t e = (size_t)s * NS + k;
+                eprof[e] = add_profile(p->tab[s][k], true);
+                estart[e] = p->tab[s][k].startAddr * 64;
+                esince[e] = p->since[s][k];
+                act.push_back((int32_t)e);
+            }
+        p->n_act = (int)act.size();
+    }
+    if (profs.empty()) profs.push_back(Profile());
+    if (inv.empty()) inv.push_back(0);
+    if (act.empty()) act.push_back(0);
+    // DAB+ slots: slot j of a stream is its j-th entry flagged DABGPU_SUBCH_DABPLUS
+    const size_t nd = std::max<size_t>(1, (size_t)S * p->NDP);
+    std::vector<int32_t> dps(nd, -1);
+    std::vector<int16_t> dpb(nd, 0);
+    std::vector<int64_t> dpc(nd, 0);
+    p->dp_max_rs = 0;
+    for (int s = 0; s < S; s++) {
+        int j = 0;
+        for (int k = 0; k < (int)p->tab[s].size(); k++) {
+            if (!(p->tab[s][k].flags & DABGPU_SUBCH_DABPLUS)) continue;
+            const size_t i = (size_t)s * p->NDP + j++;
+            dps[i] = k;
+            dpb[i] = p->tab[s][k].bitRate;
+            dpc[i] = p->since[s][k];
+            p->dp_max_rs = std::max(p->dp_max_rs, p->tab[s][k].bitRate / 8);
+        }
+    }
+    for (void **x : {(void **)&p->prof_d, (void **)&p->inv_d, (void **)&p->substart_d, (void **)&p->ent_prof_d,
+                     (void **)&p->ent_start_d, (void **)&p->ent_since_d, (void **)&p->act_d, (void **)&p->substart_bad_d}) {
+        if (*x) HIPCHK(hipFree(*x));
+        *x = nullptr;
+    }
+    auto up = [&](void **dst, const void *src, size_t bytes) -> int {
+        HIPCHK(hipMalloc(dst, std::max<size_t>(bytes, 256)));
+        HIPCHK(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+        return 0;
+    };
+    if (int rc = up((void **)&p->prof_d, profs.data(), sizeof(Profile) * profs.size())) return rc;
+    if (int rc = up((void **)&p->inv_d, inv.data(), inv.size())) return rc;
+    if (int rc = up((void **)&p->substart_d, ss.data(), sizeof(int32_t) * ss.size())) return rc;
+    if (!p->uniform) {
+        if (int rc = up((void **)&p->ent_prof_d, eprof.data(), sizeof(int32_t) * eprof.size())) return rc;
+        if (int rc = up((void **)&p->ent_start_d, estart.data(), sizeof(int32_t) * estart.size())) return rc;
+        if (int rc = up((void **)&p->ent_since_d, esince.data(), sizeof(int64_t) * esince.size())) return rc;
+        if (int rc = up((void **)&p->act_d, act.data(), sizeof(int32_t) * act.size())) return rc;
+    }
+    if (p->NDP) {
+        HIPCHK(hipMemcpy(p->dp_sub_d, dps.data(), sizeof(int32_t) * nd, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(p->dp_br_d, dpb.data(), sizeof(int16_t) * nd, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(p->dp_since_d, dpc.data(), sizeof(int64_t) * nd, hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
 int dabgpu_pipe_create(dabgpu_ctx *c, const dabgpu_pipe_cfg *cfg, dabgpu_pipe **out) {
     if (!c || !cfg || !out) return fail(DABGPU_E_ARG, "null arg");
     *out = nullptr;
+    if (cfg->n_subch < 0 || (cfg->n_subch > 0 && !cfg->subch)) return fail(DABGPU_E_ARG, "bad sizes");
+    // the caps of the table itself
+    dabgpu_pipe_caps caps = {cfg->n_subch, 0, 0, 0};
+    for (int i = 0; i < cfg->n_subch; i++) {
+        caps.max_bitrate = std::max<int32_t>(caps.max_bitrate, cfg->subch[i].bitRate);
+        if (cfg->subch[i].flags & DABGPU_SUBCH_DABPLUS) caps.max_dabplus++;
+    }
+    return dabgpu_pipe_create_caps(c, cfg, &caps, out);
+}
+
+int dabgpu_pipe_create_caps(dabgpu_ctx *c, const dabgpu_pipe_cfg *cfg, const dabgpu_pipe_caps *caps, dabgpu_pipe **out) {
+    if (!c || !cfg || !caps || !out) return fail(DABGPU_E_ARG, "null arg");
+    *out = nullptr;
     if (cfg->n_streams <= 0 || cfg->n_frames <= 0 || cfg->n_subch < 0) return fail(DABGPU_E_ARG, "bad sizes");
+    if (caps->max_subch < 0 || caps->max_bitrate < 0 || caps->max_dabplus < 0 || caps->max_dabplus > caps->max_subch ||
+        caps->max_subch > 64 || caps->max_bitrate > 8 * DP_MAX_RS)
+        return fail(DABGPU_E_ARG, "bad caps (at most 64 subchannels of at most 384 kbit/s)");
     if (cfg->freq_sync_method < 0 || cfg->freq_sync_method > 2)
         return fail(DABGPU_E_UNSUP, "freqSyncMethod %d (0, 1 or 2: ofdm-decoder.cpp:103-161)", cfg->freq_sync_method);
+    if (int rc = check_table(cfg->subch, cfg->n_subch, caps->max_subch, caps->max_bitrate, caps->max_dabplus)) return rc;
     auto *p = new dabgpu_pipe();
     p->c = c;
     p->S = cfg->n_streams;
     p->F = cfg->n_frames;
-    p->NSUB = cfg->n_subch;
+    p->NSUB = caps->max_subch;
+    p->NDP = caps->max_dabplus;
+    p->max_bitrate = caps->max_bitrate;
     p->R = 2 * cfg->n_frames + 4;
     p->threshold = cfg->threshold;
     p->method = cfg->freq_sync_method;
-    p->sub.assign(cfg->subch, cfg->subch + cfg->n_subch);
+    p->tab.assign(p->S, std::vector<dabgpu_subch>(cfg->subch, cfg->subch + cfg->n_subch));
+    p->since.assign(p->S, std::vector<int64_t>(cfg->n_subch, 0));
     p->st.assign(p->S, StreamSt());
-    std::vector<Profile> profs(std::max(1, p->NSUB));
-    std::vector<int32_t> ss(std::max(1, p->NSUB), 0);
-    p->max_nbits = 768;
-    for (int i = 0; i < p->NSUB; i++) {
-        if (make_profile(p->sub[i], profs[i])) {
-            delete p;
-            return fail(DABGPU_E_UNSUP, "subchannel %d protection undefined", i);
-        }
-        if (p->sub[i].startAddr < 0 || p->sub[i].startAddr + p->sub[i].length > 864 || profs[i].frag > p->sub[i].length * 64) {
-            delete p;
-            return fail(DABGPU_E_ARG, "subchannel %d does not fit its CUs", i);
-        }
-        ss[i] = p->sub[i].startAddr * 64;
-        p->max_nbits = std::max(p->max_nbits, profs[i].nbits);
-    }
-    std::vector<uint8_t> inv;
-    for (int i = 0; i < p->NSUB; i++) {
-        profs[i].inv_off = (int32_t)inv.size();
-        const std::vector<uint8_t> v = make_inv(profs[i]);
-        inv.insert(inv.end(), v.begin(), v.end());
-    }
-    if (inv.empty()) inv.push_back(0);
+    p->max_nbits = std::max(768, 24 * p->max_bitrate);
     const size_t SF = (size_t)p->S * p->F;
     int rc = 0;
     auto A = [&](void **ptr, size_t bytes) {
@@ -1095,8 +1232,6 @@ int dabgpu_pipe_create(dabgpu_ctx *c, const dabgpu_pipe_cfg *cfg, dabgpu_pipe **
         if (hipMalloc(ptr, std::max<size_t>(bytes, 256)) != hipSuccess) rc = fail(DABGPU_E_NOMEM, "pipe alloc %zu", bytes);
     };
     A((void **)&p->ring, (size_t)p->S * p->R * FRAME_SOFT);
-    A((void **)&p->prof_d, sizeof(Profile) * profs.size());
-    A((void **)&p->substart_d, sizeof(int32_t) * ss.size());
     A((void **)&p->frames_d, sizeof(dabgpu_frame) * SF);
     A((void **)&p->si_d, sizeof(int32_t) * SF);
     A((void **)&p->corr_d, sizeof(int16_t) * SF);
@@ -1134,7 +1269,6 @@ int dabgpu_pipe_create(dabgpu_ctx *c, const dabgpu_pipe_cfg *cfg, dabgpu_pipe **
     A((void **)&p->dec_d[0], p->dec_sz);
     A((void **)&p->dec_d[1], p->dec_sz);
     A((void **)&p->ficprof_d, sizeof(Profile));
-    A((void **)&p->inv_d, inv.size());
     int prio_least = 0, prio_greatest = 0;
     if (!rc && hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) rc = fail(DABGPU_E_HIP, "priority range");
     if (!rc && (hipStreamCreateWithPriority(&p->vs[0], hipStreamNonBlocking, prio_least) != hipSuccess ||
@@ -1153,41 +1287,22 @@ int dabgpu_pipe_create(dabgpu_ctx *c, const dabgpu_pipe_cfg *cfg, dabgpu_pipe **
         if (hipMemcpy(p->ficprof_d, &fp, sizeof fp, hipMemcpyHostToDevice) != hipSuccess)
             rc = fail(DABGPU_E_HIP, "pipe FIC profile upload failed");
     }
-    // DAB+ subchannels (mp4Processor: RSDims = bitRate / 8, mp4processor.cpp:83-84)
-    std::vector<int32_t> dps;
-    std::vector<int16_t> dpb;
-    for (int i = 0; i < p->NSUB; i++) {
-        if (!(p->sub[i].flags & DABGPU_SUBCH_DABPLUS)) continue;
-        const int br = p->sub[i].bitRate;
-        if (br < 8 || br % 8 || br / 8 > DP_MAX_RS) {
-            dabgpu_pipe_destroy(p);
-            return fail(DABGPU_E_UNSUP, "DAB+ subchannel %d: bitRate %d is not a multiple of 8 in [8, 384]", i, br);
-        }
-        dps.push_back(i);
-        dpb.push_back((int16_t)br);
-        p->dp_max_rs = std::max(p->dp_max_rs, br / 8);
-    }
-    p->NDP = (int)dps.size();
     if (p->NDP) {
-        A((void **)&p->dp_sub_d, sizeof(int32_t) * dps.size());
-        A((void **)&p->dp_br_d, sizeof(int16_t) * dpb.size());
-        A((void **)&p->dp_ring_d, (size_t)p->S * p->NDP * 120 * DP_MAX_RS);
-        A((void **)&p->dp_state_d, sizeof(DpState) * (size_t)p->S * p->NDP);
-        A((void **)&p->dp_code_d, (size_t)p->S * p->NDP * 4 * p->F);
-        A((void **)&p->dp_cand_d, sizeof(int32_t) * ((size_t)p->S * p->NDP * 4 * p->F + 1));
-        if (!rc && (hipMemcpy(p->dp_sub_d, dps.data(), sizeof(int32_t) * dps.size(), hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(p->dp_br_d, dpb.data(), sizeof(int16_t) * dpb.size(), hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemset(p->dp_ring_d, 0, (size_t)p->S * p->NDP * 120 * DP_MAX_RS) != hipSuccess ||
-                    hipMemset(p->dp_state_d, 0, sizeof(DpState) * (size_t)p->S * p->NDP) != hipSuccess))
+        const size_t nd = (size_t)p->S * p->NDP;
+        A((void **)&p->dp_sub_d, sizeof(int32_t) * nd);
+        A((void **)&p->dp_br_d, sizeof(int16_t) * nd);
+        A((void **)&p->dp_since_d, sizeof(int64_t) * nd);
+        A((void **)&p->dp_ring_d, nd * 120 * DP_MAX_RS);
+        A((void **)&p->dp_state_d, sizeof(DpState) * nd);
+        A((void **)&p->dp_code_d, nd * 4 * p->F);
+        A((void **)&p->dp_cand_d, sizeof(int32_t) * (nd * 4 * p->F + 1));
+        if (!rc && (hipMemset(p->dp_ring_d, 0, nd * 120 * DP_MAX_RS) != hipSuccess ||
+                    hipMemset(p->dp_state_d, 0, sizeof(DpState) * nd) != hipSuccess))
             rc = fail(DABGPU_E_HIP, "pipe DAB+ init failed");
     }
-    if (!rc) {
-        if (hipMemcpy(p->prof_d, profs.data(), sizeof(Profile) * profs.size(), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(p->substart_d, ss.data(), sizeof(int32_t) * ss.size(), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(p->inv_d, inv.data(), inv.size(), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemset(p->ring, RING8_BIAS, (size_t)p->S * p->R * FRAME_SOFT) != hipSuccess)
-            rc = fail(DABGPU_E_HIP, "pipe init copy failed");
-    }
+    if (!rc) rc = rebuild_tables(p);
+    if (!rc && hipMemset(p->ring, RING8_BIAS, (size_t)p->S * p->R * FRAME_SOFT) != hipSuccess)
+        rc = fail(DABGPU_E_HIP, "pipe init copy failed");
     // the default re-acquisition mode: a stream that loses sync is searched in the
     // background (DABGPU_CTL_ACQ_ASYNC; DABGPU_CTL_ACQ_SYNC restores the in-run search)
     if (!rc && !(rc = acq_async_setup(p))) p->acq_async = true;
@@ -1232,7 +1347,8 @@ int dabgpu_pipe_destroy(dabgpu_pipe *p) {
                     (void *)p->corr_d, (void *)p->snr_d, (void *)p->fc_d, (void *)p->fcpart_d, (void *)p->desc_d, (void *)p->dec_d[0], (void *)p->dec_d[1],
                     (void *)p->berr_d,
                     (void *)p->dp_sub_d, (void *)p->dp_br_d, (void *)p->dp_ring_d, (void *)p->dp_state_d, (void *)p->dp_code_d,
-                    (void *)p->dp_cand_d, (void *)p->disp_d, (void *)p->substart_bad_d})
+                    (void *)p->dp_cand_d, (void *)p->disp_d, (void *)p->substart_bad_d, (void *)p->ent_prof_d,
+                    (void *)p->ent_start_d, (void *)p->ent_since_d, (void *)p->act_d, (void *)p->dp_since_d})
         if (x) (void)hipFree(x);
     delete p;
     return 0;
@@ -1636,9 +1752,10 @@ int dabgpu_pipe_run(dabgpu_pipe *p, const void *iq, int64_t stride, const int64_
     if (!p || !iq || !n_avail) return fail(DABGPU_E_ARG, "null arg");
     dabgpu_ctx *c = p->c;
     const int S = p->S, F = p->F;
-    const bool do_msc = msc_bits && p->NSUB > 0;
+    const bool have_rows = msc_bits && p->NSUB > 0;
+    const bool do_msc = have_rows && p->n_act > 0;       // (no entry in any stream's table: nothing to decode)
     const int need = p->packed ? (p->max_nbits + 7) / 8 : p->max_nbits;
-    if (do_msc && msc_stride < need) return fail(DABGPU_E_ARG, "msc_stride %d < %d", msc_stride, need);
+    if (have_rows && msc_stride < need) return fail(DABGPU_E_ARG, "msc_stride %d < %d", msc_stride, need);
     if (int rc = back_errors(p, false)) return rc;
     if (int rc = acq_collect(p, false)) return rc;        // a background null search that finished
     p->last_frames.assign((size_t)S * F, dabgpu_frame());
@@ -1715,6 +1832,13 @@ int dabgpu_pipe_run(dabgpu_pipe *p, const void *iq, int64_t stride, const int64_
             JM.cif0s = p->cif0_dev(par);
             JM.ncifs = p->ncif_dev(par);
             JM.sub_start = p->inject_bounds ? p->substart_bad_d : p->substart_d;
+            if (!p->uniform) {                          // per-stream tables, the active pairs only
+                JM.ent_prof = p->ent_prof_d;
+                JM.ent_start = p->inject_bounds ? p->substart_bad_d : p->ent_start_d;
+                JM.ent_since = p->ent_since_d;
+                JM.act = p->act_d;
+                JM.n_acs = p->n_act * 4 * F;
+            }
             JM.out = msc_bits;
             JM.out_stride = msc_stride;
             JM.packed = p->packed ? 1 : 0;
@@ -1737,7 +1861,7 @@ int dabgpu_pipe_run(dabgpu_pipe *p, const void *iq, int64_t stride, const int64_
         if (!p->ev_front_demod) HIPCHK(hipEventRecord(p->ev_front, c->stream));
         p->ev_front_demod = false;
         HIPCHK(hipStreamWaitEvent(bs, p->ev_front, 0));
-        if (fic_bits && do_msc && p->vit_slices > 1) {
+        if (fic_bits && do_msc && p->vit_slices > 1 && p->uniform) {
             // the A/B form: K slices of traceback blocks; slice i's traceback on ts reads the
             // decisions slice i's ACS has just written while slice i + 1's ACS runs
             const int nblk = (JM.n_cw + 63) / 64, K = p->vit_slices, per = (nblk + K - 1) / K;
@@ -1883,13 +2007,20 @@ int dabgpu_pipe_run(dabgpu_pipe *p, const void *iq, int64_t stride, const int64_
     p->back_rec[par] = true;
     p->run_idx++;
     p->inject_bounds = false;
-    p->last_msc = do_msc ? msc_bits : nullptr;
+    p->last_msc = have_rows ? msc_bits : nullptr;
     p->last_msc_stride = msc_stride;
     p->last_msc_packed = p->packed;
     if (msc_valid)
         for (int s = 0; s < S; s++)
             for (int q = 0; q < 4 * F; q++)
                 msc_valid[(size_t)s * 4 * F + q] = (q < 4 * done[s] && p->st[s].cif_count + q >= 16) ? 1 : 0;
+    // per entry: the CIF was delivered and lies past the entry's own 16-CIF warm-up
+    p->entry_valid.assign((size_t)S * 4 * F * p->NSUB, 0);
+    if (have_rows)
+        for (int s = 0; s < S; s++)
+            for (int q = 0; q < 4 * done[s]; q++)
+                for (int k = 0; k < (int)p->tab[s].size(); k++)
+                    p->entry_valid[((size_t)s * 4 * F + q) * p->NSUB + k] = p->st[s].cif_count + q - p->since[s][k] >= 16;
     for (int s = 0; s < S; s++) cur[s].cif_count = p->st[s].cif_count + 4 * (int64_t)done[s];
     p->st = cur;
     if (!all) return fail(DABGPU_E_STATE, "a stream ran out of samples (see dabgpu_pipe_state)");
@@ -1957,6 +2088,7 @@ int dabgpu_pipe_dabplus(dabgpu_pipe *p, uint8_t *sf_bytes, int32_t sf_stride, da
     J.ncifs = p->ncif_dev(p->cur);
     J.dp_sub = p->dp_sub_d;
     J.dp_br = p->dp_br_d;
+    J.dp_since = p->dp_since_d;
     J.ring = p->dp_ring_d;
     J.state = p->dp_state_d;
     J.code = p->dp_code_d;
@@ -2030,6 +2162,30 @@ int dabgpu_pipe_frame_info(dabgpu_pipe *p, dabgpu_frame_info *info) {
     return 0;
 }
 
+// DABGPU_CTL_INJECT_BOUNDS: the table the next run's MSC job reads its start offsets from
+static int inject_table(dabgpu_pipe *p) {
+    if (!p->substart_bad_d) {                       // (rebuild_tables drops it with the tables)
+        // the start offsets in use (shared, or per entry) with the first decoded entry's
+        // far past any ring (no int32 overflow in the loader)
+        std::vector<int32_t> bad;
+        if (p->uniform) {
+            for (int i = 0; i < p->NSUB; i++) bad.push_back(p->tab[0][i].startAddr * 64);
+            bad[0] = 0x40000000;
+        } else {
+            bad.assign((size_t)p->S * p->NSUB, 0);
+            bool first = true;
+            for (int s = 0; s < p->S; s++)
+                for (int k = 0; k < (int)p->tab[s].size(); k++) {
+                    bad[(size_t)s * p->NSUB + k] = first ? 0x40000000 : p->tab[s][k].startAddr * 64;
+                    first = false;
+                }
+        }
+        HIPCHK(hipMalloc((void **)&p->substart_bad_d, sizeof(int32_t) * bad.size()));
+        HIPCHK(hipMemcpy(p->substart_bad_d, bad.data(), sizeof(int32_t) * bad.size(), hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
 int dabgpu_pipe_control(dabgpu_pipe *p, int stream, int op) {
     if (!p || stream < -1 || stream >= p->S) return fail(DABGPU_E_ARG, "bad args");
     if (op == DABGPU_CTL_SCAN_ON || op == DABGPU_CTL_SCAN_OFF) {      // set_scanMode (one flag, like the reference's)
@@ -2037,14 +2193,8 @@ int dabgpu_pipe_control(dabgpu_pipe *p, int stream, int op) {
         return 0;
     }
     if (op == DABGPU_CTL_INJECT_BOUNDS) {
-        if (p->NSUB == 0) return fail(DABGPU_E_STATE, "no MSC subchannel to corrupt");
-        if (!p->substart_bad_d) {
-            HIPCHK(hipMalloc((void **)&p->substart_bad_d, sizeof(int32_t) * p->NSUB));
-            std::vector<int32_t> bad(p->NSUB);
-            for (int i = 0; i < p->NSUB; i++) bad[i] = p->sub[i].startAddr * 64;
-            bad[0] = 0x40000000;                        // far past any ring (no int32 overflow in the loader)
-            HIPCHK(hipMemcpy(p->substart_bad_d, bad.data(), sizeof(int32_t) * p->NSUB, hipMemcpyHostToDevice));
-        }
+        if (p->n_act == 0) return fail(DABGPU_E_STATE, "no MSC subchannel to corrupt");
+        if (int rc = inject_table(p)) return rc;
         p->inject_bounds = true;
         return 0;
     }
@@ -2086,6 +2236,76 @@ int dabgpu_pipe_frame_slot(dabgpu_pipe *p, int frame, int32_t *slot) {
     *slot = p->last_frames.empty() ? -1 : p->last_frames[frame].out_slot;
     return 0;
 }
+int dabgpu_pipe_set_subch(dabgpu_pipe *p, int stream, const dabgpu_subch *sub, int32_t n) {
+    if (!p || stream < -1 || stream >= p->S) return fail(DABGPU_E_ARG, "bad args");
+    if (int rc = check_table(sub, n, p->NSUB, p->max_bitrate, p->NDP)) return rc;   // the table stays on error
+    // in-flight kernels read the device tables: a rare control call, so it waits for
+    // everything the pipeline has enqueued (as dabgpu_pipe_set_profiling) instead of
+    // double-buffering them
+    HIPCHK(hipStreamSynchronize(p->c->stream));
+    for (hipStream_t v : p->vs) HIPCHK(hipStreamSynchronize(v));
+    const size_t RB = 120 * DP_MAX_RS;
+    for (int s = (stream < 0 ? 0 : stream); s < (stream < 0 ? p->S : stream + 1); s++) {
+        const std::vector<dabgpu_subch> old = p->tab[s];
+        const std::vector<int64_t> old_since = p->since[s];
+        std::vector<int> old_slot(old.size(), -1);      // DAB+ slot of each old entry
+        for (int k = 0, j = 0; k < (int)old.size(); k++)
+            if (old[k].flags & DABGPU_SUBCH_DABPLUS) old_slot[k] = j++;
+        // an entry whose index and fields are unchanged goes on (since_cif, DAB+ ring and
+        // state kept, wherever its slot now lies); every other one starts like a new
+        // dabConcurrent / mp4Processor at the stream's current CIF
+        std::vector<uint8_t> rings, nrings;
+        std::vector<DpState> sts, nsts;
+        if (p->NDP) {
+            rings.resize(p->NDP * RB);
+            sts.resize(p->NDP);
+            HIPCHK(hipMemcpy(rings.data(), p->dp_ring_d + (size_t)s * p->NDP * RB, rings.size(), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(sts.data(), p->dp_state_d + (size_t)s * p->NDP, sizeof(DpState) * p->NDP, hipMemcpyDeviceToHost));
+            nrings.assign(rings.size(), 0);
+            nsts.assign(p->NDP, DpState{0, 0});
+        }
+        p->tab[s].assign(sub, sub + n);
+        p->since[s].assign(n, p->st[s].cif_count);
+        for (int k = 0, j = 0; k < n; k++) {
+            const bool kept = k < (int)old.size() && same_subch(old[k], sub[k]);
+            if (kept) p->since[s][k] = old_since[k];
+            if (!(sub[k].flags & DABGPU_SUBCH_DABPLUS)) continue;
+            if (kept) {
+                memcpy(nrings.data() + (size_t)j * RB, rings.data() + (size_t)old_slot[k] * RB, RB);
+                nsts[j] = sts[old_slot[k]];
+            }
+            j++;
+        }
+        if (p->NDP) {
+            HIPCHK(hipMemcpy(p->dp_ring_d + (size_t)s * p->NDP * RB, nrings.data(), nrings.size(), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(p->dp_state_d + (size_t)s * p->NDP, nsts.data(), sizeof(DpState) * p->NDP, hipMemcpyHostToDevice));
+        }
+    }
+    p->last_msc = nullptr;            // the last run's rows follow the old tables: no DAB+ layer over them now
+    if (int rc = rebuild_tables(p)) return rc;
+    if (p->inject_bounds) return inject_table(p);
+    return 0;
+}
+
+int dabgpu_pipe_get_subch(dabgpu_pipe *p, int stream, dabgpu_subch *sub, int32_t *n, int64_t *since_cif) {
+    if (!p || !n || stream < 0 || stream >= p->S || (!sub && !p->tab[stream].empty()))
+        return fail(DABGPU_E_ARG, "bad args");
+    *n = (int32_t)p->tab[stream].size();
+    for (int k = 0; k < *n; k++) {
+        sub[k] = p->tab[stream][k];
+        if (since_cif) since_cif[k] = p->since[stream][k];
+    }
+    return 0;
+}
+
+int dabgpu_pipe_msc_entry_valid(dabgpu_pipe *p, uint8_t *valid_h) {
+    if (!p || !valid_h) return fail(DABGPU_E_ARG, "bad args");
+    const size_t nb = (size_t)p->S * 4 * p->F * p->NSUB;
+    if (p->entry_valid.size() != nb) memset(valid_h, 0, nb);   // no run yet
+    else memcpy(valid_h, p->entry_valid.data(), nb);
+    return 0;
+}
+
 int dabgpu_pipe_set_packed(dabgpu_pipe *p, int on) {
     if (!p || on < 0 || on > (DABGPU_PACK_MSC | DABGPU_PACK_FIC)) return fail(DABGPU_E_ARG, "packing %d", on);
     p->packed = (on & DABGPU_PACK_MSC) != 0;

@@ -292,7 +292,9 @@ __global__ __launch_bounds__(64) void k_dp_fire(DpJob J) {
     __shared__ uint16_t fire[256];
     const int lane = threadIdx.x, sd = blockIdx.x;      // sd = stream * ndp + dp
     const int stream = sd / J.ndp, dp = sd - stream * J.ndp;
-    const int br = J.dp_br[dp], sub = J.dp_sub[dp], nbytes = 3 * br;
+    const int br = J.dp_br[sd], sub = J.dp_sub[sd], nbytes = 3 * br;
+    if (sub < 0) return;                                 // absent slot: nothing queued (k_dp_walk writes its records)
+    const int64_t since = J.dp_since[sd];
     const uint16_t *tf = (const uint16_t *)(J.tabs + offsetof(GfTabs, fire));
     for (int i = lane; i < 256; i += 64) fire[i] = tf[i];
     wave_sync();
@@ -303,7 +305,7 @@ __global__ __launch_bounds__(64) void k_dp_fire(DpJob J) {
         if (cl < J.ncif) {
             // a window holding an undelivered CIF (de-interleaver warm-up, or a CIF slot the
             // stream did not fill in this run) is never evaluated
-            ok = !(cl >= J.ncifs[stream] || J.cif0s[stream] + cl - 4 < 16);
+            ok = !(cl >= J.ncifs[stream] || J.cif0s[stream] + cl - 4 - since < 16);
             if (ok) {
                 uint32_t x[11];
 #pragma unroll
@@ -328,7 +330,7 @@ __global__ __launch_bounds__(64) void k_dp_fire(DpJob J) {
 __device__ void sf_decode(const DpJob &J, const GfTabs &g, int sd, int cl, uint8_t *sfb, uint32_t *syn_s,
                           uint8_t *rl, int32_t *red, int lane) {
     const int stream = sd / J.ndp, dp = sd - stream * J.ndp;
-    const int br = J.dp_br[dp], sub = J.dp_sub[dp];
+    const int br = J.dp_br[sd], sub = J.dp_sub[sd];
     const int RS = br / 8, nbytes = 3 * br, fsz = 120 * RS, end = 110 * RS;
     uint8_t *code = J.code + (int64_t)sd * J.ncif + cl;
     const uint8_t *carry = J.ring + (int64_t)sd * (120 * DP_MAX_RS);
@@ -474,11 +476,24 @@ __global__ __launch_bounds__(64) void k_dp_superframe(DpJob J) {
 // wave, and the carry (the run's last 4 CIFs) for the next run; nc: LDS [4 * 3 * 384]
 __device__ void dp_walk(const DpJob &J, int sd, uint8_t *nc, int lane) {
     const int stream = sd / J.ndp, dp = sd - stream * J.ndp;
-    const int br = J.dp_br[dp], sub = J.dp_sub[dp], nbytes = 3 * br;
+    const int br = J.dp_br[sd], sub = J.dp_sub[sd], nbytes = 3 * br;
+    if (sub < 0) {                                       // absent slot: status -1 records, no state
+        for (int cl = lane; cl < J.ncif; cl += 64) {
+            dabgpu_superframe info;
+            info.status = -1;
+            info.num_aus = 0;
+            info.n_corrected = 0;
+            for (int i = 0; i < 7; i++) info.au_start[i] = 0;
+            info.au_crc_ok = 0;
+            info.reserved = J.sf_compact ? 0xFF : 0;
+            J.info[((int64_t)stream * J.ncif + cl) * J.ndp + dp] = info;
+        }
+        return;
+    }
     DpState st = J.state[sd];
     const uint8_t *code = J.code + (int64_t)sd * J.ncif;
     const int nd = J.ncifs[stream];                     // CIFs this stream delivered
-    const int64_t cif0 = J.cif0s[stream];
+    const int64_t cif0 = J.cif0s[stream] - J.dp_since[sd];   // CIF index counted from the entry's since_cif
     for (int c0 = 0; c0 < J.ncif; c0 += 64) {
         const int cl = c0 + lane;
         const int v = cl < J.ncif ? code[cl] : 0;
@@ -556,7 +571,12 @@ __global__ __launch_bounds__(64 * DP_WAVES) void k_dp_layer(DpJob J) {
     __shared__ int32_t ncand;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, sd = blockIdx.x;
     const int stream = sd / J.ndp, dp = sd - stream * J.ndp;
-    const int br = J.dp_br[dp], sub = J.dp_sub[dp], nbytes = 3 * br;
+    const int br = J.dp_br[sd], sub = J.dp_sub[sd], nbytes = 3 * br;
+    if (sub < 0) {                                       // absent slot (the whole workgroup): status -1 records
+        if (w == 0) dp_walk(J, sd, sfb[1], lane);
+        return;
+    }
+    const int64_t since = J.dp_since[sd];
     const uint32_t *tabs32 = (const uint32_t *)J.tabs;
     for (int i = t; i < (int)sizeof(GfTabs) / 4; i += 64 * DP_WAVES) ((uint32_t *)&g)[i] = tabs32[i];
     if (t == 0) ncand = 0;
@@ -565,7 +585,7 @@ __global__ __launch_bounds__(64 * DP_WAVES) void k_dp_layer(DpJob J) {
     for (int cl = t; cl < J.ncif; cl += 64 * DP_WAVES) {
         // a window holding an undelivered CIF (de-interleaver warm-up, or a CIF slot the
         // stream did not fill in this run) is never evaluated
-        bool ok = !(cl >= J.ncifs[stream] || J.cif0s[stream] + cl - 4 < 16);
+        bool ok = !(cl >= J.ncifs[stream] || J.cif0s[stream] + cl - 4 - since < 16);
         if (ok) {
             uint32_t x[11];
 #pragma unroll

@@ -67,7 +67,9 @@ struct Src {
     __amdgpu_buffer_rsrc_t rs;   // buffer over the readable elements: 32-bit offsets, and
                                  // reads past its end (erasures, empty delay line) return 0
     int prof;              // profile index
-    int row;               // output / decision row of this codeword
+    int row;               // output row of this codeword
+    int drow;              // its decision row (the output row, but with per-stream tables the
+                           // logical index: the traceback then walks active codewords only)
     bool valid;
 };
 
@@ -82,7 +84,7 @@ __device__ __forceinline__ Src src_of(const VitJob &J, int logical, int32_t *row
     c.prof = 0;
     c.valid = logical < J.n_cw;
     if (!c.valid) logical = 0;
-    c.row = logical;
+    c.row = c.drow = logical;
     if constexpr (KIND == SRC_MOTHER) {
         c.base = J.src + (int64_t)logical * J.src_stride;
     } else if constexpr (KIND == SRC_FRAG) {
@@ -94,15 +96,37 @@ __device__ __forceinline__ Src src_of(const VitJob &J, int logical, int32_t *row
         c.base = (const int16_t *)((const char *)J.src +
                                    ESZ * ((int64_t)(slot < 0 ? 0 : slot) * FRAME_SOFT + (logical & 3) * 2304));
     } else {
-        const int cl = logical % J.ncif;
-        const int rest = logical / J.ncif;
-        const int sub = rest % J.nsub;
-        const int stream = rest / J.nsub;
+        int cl = logical % J.ncif;
+        int rest = logical / J.ncif;
+        int sub, stream, start;
+        int64_t since = 0;
+        if (J.ent_prof) {
+            // per-stream tables: the logical index runs over the active (stream, entry)
+            // pairs; profile, start offset and since_cif are the entry's own (wave-uniform)
+            c.valid = logical < J.n_acs;
+            if (!c.valid) cl = rest = 0;
+            const int e = __builtin_amdgcn_readfirstlane(J.act[rest]);
+            sub = e % J.nsub;
+            stream = e / J.nsub;
+            const int pr = __builtin_amdgcn_readfirstlane(J.ent_prof[e]);
+            c.valid = c.valid && pr >= 0;
+            c.prof = pr < 0 ? 0 : pr;
+            start = __builtin_amdgcn_readfirstlane(J.ent_start[e]);
+            const int64_t sc = J.ent_since[e];
+            since = ((int64_t)__builtin_amdgcn_readfirstlane((int)(sc >> 32)) << 32) |
+                    (uint32_t)__builtin_amdgcn_readfirstlane((int)sc);
+        } else {
+            sub = rest % J.nsub;
+            stream = rest / J.nsub;
+            c.prof = sub;
+            start = J.sub_start[sub];
+        }
         c.row = (stream * J.ncif + cl) * J.nsub + sub;
-        c.prof = sub;
+        c.drow = J.ent_prof ? logical : c.row;
         const int64_t cif = J.cif0s[stream] + cl;
-        // CIFs the stream delivered in this batch; dab-concurrent.cpp:172-175 warm-up
-        c.valid = c.valid && cl < J.ncifs[stream] && cif >= 16;
+        // CIFs the stream delivered in this batch; dab-concurrent.cpp:172-175 warm-up (of the
+        // entry's own dabConcurrent: 16 CIFs from since_cif)
+        c.valid = c.valid && cl < J.ncifs[stream] && cif - since >= 16;
         c.base = (const int16_t *)((const char *)J.src + ESZ * (int64_t)stream * J.ring * FRAME_SOFT);
         if (lane < 16) {
             // element idx of CIF n comes from CIF n - d[idx & 15] (dab-concurrent.cpp:42-43,162-169)
@@ -112,8 +136,8 @@ __device__ __forceinline__ Src src_of(const VitJob &J, int logical, int32_t *row
             int32_t ro = -1;                           // delay line still empty: zeros
             if (g >= 0) {
                 const int slot = (int)((g >> 2) % J.ring);
-                ro = (slot * NSYM + 3 + 18 * (int)(g & 3)) * SYMBITS + J.sub_start[sub];
-                const Profile &P = J.prof[sub];
+                ro = (slot * NSYM + 3 + 18 * (int)(g & 3)) * SYMBITS + start;
+                const Profile &P = J.prof[c.prof];
                 if (ro < 0 || (int64_t)ro + P.frag > (int64_t)J.ring * FRAME_SOFT) {
                     atomicOr(J.err, KERR_VITERBI);     // never read outside the stream's ring
                     ro = -1;
@@ -652,7 +676,7 @@ __device__ __forceinline__ void acs_body(const VitJob &J, int w, AcsLds<NP> &L) 
     for (int p = 0; p < NP; p++) x[p] = lane == 0 ? 0u : 0x003F003Fu;   // viterbi.cpp:360-371
 #pragma unroll
     for (int k = 0; k < 2 * NP; k++) {
-        rb[k] = c[k].valid ? dec_word_index(c[k].row, J.dec_nch) : -1;
+        rb[k] = c[k].valid ? dec_word_index(c[k].drow, J.dec_nch) : -1;
     }
     const int64_t cstride = 64 * 64;                    // words per chunk of a 64-row block
     const __amdgpu_buffer_rsrc_t drs = __builtin_amdgcn_make_buffer_rsrc((void *)J.dec, (short)0, -1, 0x00020000);
@@ -795,14 +819,29 @@ __device__ __forceinline__ void tb_body(const VitJob &J, int blk, uint32_t *stag
     const int lane = threadIdx.x, cw = blk * TB_CW + lane;
     bool act = lane < TB_CW && cw < J.n_cw;
     int N = 0, prof = 0;
+    int orow = cw;                                       // output row
+    if constexpr (KIND == SRC_MSC) {
+        if (J.ent_prof) act = lane < TB_CW && cw < J.n_acs;
+    }
     if (act) {
-        // validity and profile by output row (inverse of src_of's mapping)
+        // validity and profile by decision row (inverse of src_of's mapping)
         if constexpr (KIND == SRC_MSC) {
-            const int sub = cw % J.nsub;
-            const int cl = (cw / J.nsub) % J.ncif;
-            const int stream = cw / J.nsub / J.ncif;
+            int sub = cw % J.nsub;
+            int cl = (cw / J.nsub) % J.ncif;
+            int stream = cw / J.nsub / J.ncif;
             prof = sub;
-            act = cl < J.ncifs[stream] && J.cif0s[stream] + cl >= 16;
+            int64_t since = 0;
+            if (J.ent_prof) {                            // per-stream tables: decision row = the ACS's
+                cl = cw % J.ncif;                        // logical index (active pair, CIF) -- no lane
+                const int e = J.act[cw / J.ncif];        // spent on padding rows
+                sub = e % J.nsub;
+                stream = e / J.nsub;
+                orow = (stream * J.ncif + cl) * J.nsub + sub;
+                prof = J.ent_prof[e];
+                since = J.ent_since[e];
+            }
+            act = prof >= 0 && cl < J.ncifs[stream] && J.cif0s[stream] + cl - since >= 16;
+            if (!act) prof = 0;
         } else if constexpr (KIND == SRC_FRAG) {
             prof = J.cw_prof ? J.cw_prof[cw] : 0;
         } else if constexpr (KIND == SRC_FIC) {
@@ -819,7 +858,7 @@ __device__ __forceinline__ void tb_body(const VitJob &J, int blk, uint32_t *stag
     int smin = act ? steps : tmax;                       // chunks below smin are whole in every lane
     for (int o = 32; o > 0; o >>= 1) smin = min(smin, __shfl_xor(smin, o));
     smin = __builtin_amdgcn_readfirstlane(smin);
-    uint8_t *out = J.out + (act ? (int64_t)cw * J.out_stride : 0);
+    uint8_t *out = J.out + (act ? (int64_t)orow * J.out_stride : 0);
     const int nch = (tmax + WS - 1) / WS;
     // the energy-dispersal words in LDS: a vector load of them beside the decision
     // prefetches would wait for every outstanding load (vmcnt(0)) once per chunk
@@ -1083,11 +1122,14 @@ template <int KIND> struct TbK { static auto fn() { return k_traceback<KIND>; } 
 // wave, fewer waves) measured slower on MI355X for the C3 batch: 0.81 ms (NP=2) and
 // 1.14 ms (NP=3) vs 0.72 ms per launch -- thread-level parallelism hides the
 // DPP hazards and LDS latency better than instruction-level parallelism here.
+// codewords the ACS enumerates: the active (pair, CIF)s with per-stream tables, else every row
+static int acs_count(const VitJob &job) { return job.kind == SRC_MSC && job.ent_prof ? job.n_acs : job.n_cw; }
+
 hipError_t launch_acs(hipStream_t st, const VitJob &job) {
-    if (job.n_cw <= 0) return hipSuccess;
+    if (job.n_cw <= 0 || acs_count(job) <= 0) return hipSuccess;
     if (job.dec_ncw < dec_rows(job.n_cw) || job.dec_nch <= 0) return hipErrorInvalidValue;
     if (job.ring8) {                                   // the pipeline's RING8 soft-bit ring
-        const dim3 grid((job.n_cw + 1) / 2);
+        const dim3 grid((acs_count(job) + 1) / 2);
         if (job.kind == SRC_FIC) hipLaunchKernelGGL((k_acs<SRC_FIC, true>), grid, dim3(64), 0, st, job);
         else if (job.kind == SRC_MSC) hipLaunchKernelGGL((k_acs<SRC_MSC, true>), grid, dim3(64), 0, st, job);
         else return hipErrorInvalidValue;
@@ -1098,7 +1140,8 @@ hipError_t launch_acs(hipStream_t st, const VitJob &job) {
 hipError_t launch_traceback(hipStream_t st, const VitJob &job) {
     if (job.n_cw <= 0) return hipSuccess;
     if (job.dec_ncw < dec_rows(job.n_cw) || job.dec_nch <= 0) return hipErrorInvalidValue;
-    return launch_kind<TbK>(st, job, dim3((job.n_cw + TB_CW - 1) / TB_CW), tb_lds_bytes(job.dec_nch));
+    if (acs_count(job) <= 0) return hipSuccess;
+    return launch_kind<TbK>(st, job, dim3((acs_count(job) + TB_CW - 1) / TB_CW), tb_lds_bytes(job.dec_nch));
 }
 hipError_t launch_viterbi(hipStream_t st, const VitJob &job) {
     hipError_t e = launch_acs(st, job);
@@ -1112,8 +1155,10 @@ hipError_t launch_acs_msc_fic_range(hipStream_t st, const VitJob &a, const VitJo
     if (a.dec_ncw < dec_rows(a.n_cw) || b.dec_ncw < dec_rows(b.n_cw) || a.dec_nch <= 0 || b.dec_nch <= 0)
         return hipErrorInvalidValue;
     if (a.ring8 != b.ring8) return hipErrorInvalidValue;
-    const int nwa_all = (a.n_cw + 1) / 2, nwb = fic ? (b.n_cw + 1) / 2 : 0;
-    const int w0 = b0 * (TB_CW / 2), w1 = min(nwa_all, b1 * (TB_CW / 2));
+    const int nwa_all = (acs_count(a) + 1) / 2, nwb = fic ? (b.n_cw + 1) / 2 : 0;
+    // (with per-stream tables the ACS order is not the traceback's row order: no slices)
+    if (a.ent_prof && (b0 != 0 || b1 < (a.n_cw + TB_CW - 1) / TB_CW)) return hipErrorInvalidValue;
+    const int w0 = b0 * (TB_CW / 2), w1 = a.ent_prof ? nwa_all : min(nwa_all, b1 * (TB_CW / 2));
     if (b0 < 0 || w0 >= w1) return hipErrorInvalidValue;
     const int nwa = w1 - w0;
     if (a.ring8) hipLaunchKernelGGL((k_acs2<SRC_MSC, SRC_FIC, true>), dim3(nwa + nwb), dim3(64), 0, st, a, b, nwa, w0);
@@ -1122,7 +1167,7 @@ hipError_t launch_acs_msc_fic_range(hipStream_t st, const VitJob &a, const VitJo
 }
 hipError_t launch_traceback_msc_fic_range(hipStream_t st, const VitJob &a, const VitJob &b, int b0, int b1, bool fic) {
     if (a.kind != SRC_MSC || b.kind != SRC_FIC || a.n_cw <= 0 || b.n_cw <= 0) return hipErrorInvalidValue;
-    const int nba_all = (a.n_cw + TB_CW - 1) / TB_CW, nbb = fic ? (b.n_cw + TB_CW - 1) / TB_CW : 0;
+    const int nba_all = (acs_count(a) + TB_CW - 1) / TB_CW, nbb = fic ? (b.n_cw + TB_CW - 1) / TB_CW : 0;
     b1 = min(b1, nba_all);
     if (b0 < 0 || b0 >= b1) return hipErrorInvalidValue;
     hipLaunchKernelGGL((k_traceback2<SRC_MSC, SRC_FIC>), dim3(b1 - b0 + nbb), dim3(64),

@@ -51,6 +51,11 @@ class Frame(C.Structure):
                 ("phase_b", C.c_int32), ("out_slot", C.c_int32), ("flags", C.c_int32)]
 
 
+class PipeCaps(C.Structure):
+    _fields_ = [("max_subch", C.c_int32), ("max_bitrate", C.c_int32), ("max_dabplus", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class PipeCfg(C.Structure):
     _fields_ = [("n_streams", C.c_int32), ("n_frames", C.c_int32), ("n_subch", C.c_int32),
                 ("threshold", C.c_int16), ("freq_sync_method", C.c_int16), ("subch", C.POINTER(Subch))]
@@ -137,6 +142,10 @@ def lib() -> C.CDLL:
             "dabgpu_pipe_iq_display": ([vp, i32, i32, vp], i32),
             "dabgpu_pipe_set_profiling": ([vp, i32], i32),
             "dabgpu_pipe_timing": ([vp, vp, vp], i32),
+            "dabgpu_pipe_create_caps": ([vp, vp, vp, C.POINTER(vp)], i32),
+            "dabgpu_pipe_set_subch": ([vp, i32, vp, C.c_int32], i32),
+            "dabgpu_pipe_get_subch": ([vp, i32, vp, C.POINTER(C.c_int32), vp], i32),
+            "dabgpu_pipe_msc_entry_valid": ([vp, vp], i32),
         }
         for name, (args, res) in sig.items():
             try:
@@ -152,7 +161,9 @@ def lib() -> C.CDLL:
 
 def _chk(rc: int, what: str) -> None:
     if rc != 0:
-        raise DabError(f"{what} failed ({rc}): {lib().dabgpu_last_error().decode()}")
+        e = DabError(f"{what} failed ({rc}): {lib().dabgpu_last_error().decode()}")
+        e.code = rc                                          # the DABGPU_E_* code
+        raise e
 
 
 def _p(a: np.ndarray) -> C.c_void_p:
@@ -586,18 +597,34 @@ class Context:
 class Pipeline:
     """ofdmProcessor::run + ficHandler + mscHandler for n_streams ensembles
     (ofdm-processor.cpp:247-474, fic-handler.cpp:192-321, msc-handler.cpp:125-193,
-    dab-concurrent.cpp:144-193), n_frames frames per run() call."""
+    dab-concurrent.cpp:144-193), n_frames frames per run() call.
+
+    subch is every stream's initial table.  With any of max_subch / max_bitrate / max_dabplus
+    (dabgpu_pipe_create_caps; one left None is taken from subch) the pipeline is sized by
+    those caps and set_subch(stream, subs) may give each stream its own table between runs:
+    run() then returns msc [S, 4F, max_subch, stride] (entry k of a stream in row k) and
+    dabplus() records and bytes with max_dabplus slots."""
 
     def __init__(self, ctx: Context, n_streams: int, n_frames: int, subch: Sequence[Subch],
-                 threshold: int = 3, freq_sync_method: int = 1):
+                 threshold: int = 3, freq_sync_method: int = 1, max_subch: Optional[int] = None,
+                 max_bitrate: Optional[int] = None, max_dabplus: Optional[int] = None):
         self.ctx, self.S, self.F, self.subch = ctx, n_streams, n_frames, list(subch)
         self._arr = (Subch * max(1, len(self.subch)))(*self.subch)
         cfg = PipeCfg(n_streams, n_frames, len(self.subch), threshold, freq_sync_method,
                       C.cast(self._arr, C.POINTER(Subch)))
         h = C.c_void_p()
-        _chk(lib().dabgpu_pipe_create(ctx.h, C.byref(cfg), C.byref(h)), "dabgpu_pipe_create")
+        own = (len(self.subch), max([s.bitRate for s in self.subch] + [0]),
+               sum(1 for s in self.subch if s.flags & SUBCH_DABPLUS))
+        given = (max_subch, max_bitrate, max_dabplus)
+        self.max_subch, self.max_bitrate, self.max_dabplus = [o if g is None else int(g) for o, g in zip(own, given)]
+        if given == (None, None, None):
+            _chk(lib().dabgpu_pipe_create(ctx.h, C.byref(cfg), C.byref(h)), "dabgpu_pipe_create")
+        else:
+            caps = PipeCaps(self.max_subch, self.max_bitrate, self.max_dabplus, 0)
+            _chk(lib().dabgpu_pipe_create_caps(ctx.h, C.byref(cfg), C.byref(caps), C.byref(h)),
+                 "dabgpu_pipe_create_caps")
         self.h = h
-        self.msc_stride = max([24 * s.bitRate for s in self.subch] + [768])
+        self.msc_stride = max(24 * self.max_bitrate, 768)
         self.msc_stride = (self.msc_stride + 15) // 16 * 16
         self.msc_stride_packed = self.msc_stride // 8        # bytes per codeword with set_packed
         self.packed = False
@@ -606,16 +633,19 @@ class Pipeline:
         # consecutive runs decode concurrently on two back-end streams (dabgpu.h,
         # dabgpu_pipe_sync): outputs alternate between two buffer sets
         self._outs = [(ctx.buf(n_streams * n_frames * 4 * 768), ctx.buf(n_streams * n_frames * 12),
-                       ctx.buf(max(1, n_streams * 4 * n_frames * len(self.subch) * self.msc_stride)))
+                       ctx.buf(max(1, n_streams * 4 * n_frames * self.max_subch * self.msc_stride)))
                       for _ in range(2)]
         self._run = 0
         self.fic_d, self.crc_d, self.msc_d = self._outs[0]
         self.dp = [s for s in self.subch if s.flags & SUBCH_DABPLUS]
         self.sf_stride = max([110 * (s.bitRate // 8) for s in self.dp] + [16])
-        if self.dp:
+        if given != (None, None, None) and self.max_dabplus:
+            self.sf_stride = (110 * (self.max_bitrate // 8) + 15) // 16 * 16   # any DAB+ entry the caps allow
+        self._sf = []
+        if self.max_dabplus:
             # two sets as well: run r's records may still be copied out (fetch) while
             # run r+1's DAB+ layer writes
-            nrec = n_streams * 4 * n_frames * len(self.dp)
+            nrec = n_streams * 4 * n_frames * self.max_dabplus
             self._sf = [(ctx.buf(nrec * self.sf_stride), ctx.buf(nrec * C.sizeof(Superframe))) for _ in range(2)]
             self.sf_d, self.sfi_d = self._sf[0]
 
@@ -633,7 +663,7 @@ class Pipeline:
         self._run += 1
         ms = self.msc_stride_packed if self.packed else self.msc_stride
         rc = lib().dabgpu_pipe_run(self.h, iq.ptr, stride, _p(na), self.fic_d.ptr, self.crc_d.ptr,
-                                   self.msc_d.ptr if self.subch else None, ms, _p(valid))
+                                   self.msc_d.ptr if self.max_subch else None, ms, _p(valid))
         if not (partial and rc == -6):
             _chk(rc, "dabgpu_pipe_run")
         if not download:
@@ -641,8 +671,34 @@ class Pipeline:
         self.sync()
         fic = self.fic_d.download(np.uint8, (self.S, self.F, 4, 96 if self.fic_packed else 768))
         crc = self.crc_d.download(np.uint8, (self.S, self.F, 12))
-        msc = self.msc_d.download(np.uint8, (self.S, 4 * self.F, len(self.subch), ms)) if self.subch else None
+        msc = self.msc_d.download(np.uint8, (self.S, 4 * self.F, self.max_subch, ms)) if self.max_subch else None
         return fic, crc, msc, valid
+
+    def set_subch(self, stream: int, subs: Sequence[Subch]) -> None:
+        """replace the subchannel table of `stream` (-1: of every stream) for the runs that
+        follow (dabgpu_pipe_set_subch): unchanged entries go on, the others deliver from the
+        stream's current CIF + 16.  Call dabplus() for the last run before it."""
+        subs = list(subs)
+        arr = (Subch * max(1, len(subs)))(*subs)
+        _chk(lib().dabgpu_pipe_set_subch(self.h, int(stream), C.cast(arr, C.c_void_p), len(subs)),
+             "dabgpu_pipe_set_subch")
+
+    def get_subch(self, stream: int):
+        """(the stream's table as a list of Subch, since_cif of each entry)"""
+        arr = (Subch * max(1, self.max_subch))()
+        n = C.c_int32()
+        since = np.zeros(max(1, self.max_subch), np.int64)
+        _chk(lib().dabgpu_pipe_get_subch(self.h, int(stream), C.cast(arr, C.c_void_p), C.byref(n), _p(since)),
+             "dabgpu_pipe_get_subch")
+        return [Subch(a.startAddr, a.length, a.bitRate, a.protLevel, a.uepFlag, a.flags) for a in arr[:n.value]], \
+            [int(x) for x in since[:n.value]]
+
+    def msc_entry_valid(self) -> np.ndarray:
+        """[S, 4F, max_subch] uint8 of the last run: the stream delivered the CIF and it is
+        past the entry's own 16-CIF warm-up (dabgpu_pipe_msc_entry_valid)"""
+        v = np.zeros((self.S, 4 * self.F, max(1, self.max_subch)), np.uint8)
+        _chk(lib().dabgpu_pipe_msc_entry_valid(self.h, _p(v)), "dabgpu_pipe_msc_entry_valid")
+        return v[:, :, :self.max_subch]
 
     def set_dabplus_compact(self, on: bool = True) -> None:
         """compact superframe bytes (dabgpu_pipe_set_dabplus_compact): dabplus() then returns
@@ -664,7 +720,7 @@ class Pipeline:
         if not download:
             return None
         self.sync()
-        nd = len(self.dp)
+        nd = self.max_dabplus
         raw = self.sfi_d.download(np.uint8, self.S * 4 * self.F * nd * C.sizeof(Superframe))
         info = np.frombuffer(raw.tobytes(), dtype=SUPERFRAME_DTYPE).reshape(self.S, 4 * self.F, nd)
         if getattr(self, "dp_compact", False):
@@ -771,7 +827,7 @@ class Pipeline:
 
     def close(self) -> None:
         if self.h:
-            for o in self._outs + (self._sf if self.dp else []):
+            for o in self._outs + self._sf:
                 for b in o:
                     b.free()
             lib().dabgpu_pipe_destroy(self.h)

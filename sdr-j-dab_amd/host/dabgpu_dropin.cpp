@@ -240,33 +240,57 @@ ensembleDecoder::ensembleDecoder(const config &cfg) : cfg_(cfg) {
     pc.threshold = cfg.threshold;
     pc.freq_sync_method = 1;
     pc.subch = cfg.subch.data();
-    chk(dabgpu_pipe_create(thread_context(), &pc, &pipe_), "dabgpu_pipe_create");
-    int maxbits = 768, maxrs = 0;
-    for (size_t i = 0; i < cfg.subch.size(); i++) {
-        maxbits = std::max(maxbits, 24 * (int)cfg.subch[i].bitRate);
-        if (cfg.subch[i].flags & DABGPU_SUBCH_DABPLUS) {
-            dp_index_.push_back((int)i);
-            maxrs = std::max(maxrs, cfg.subch[i].bitRate / 8);
-        }
+    dabgpu_pipe_caps caps = {(int32_t)cfg.subch.size(), 0, 0, 0};        // what the table needs ...
+    for (const dabgpu_subch &sc : cfg.subch) {
+        caps.max_bitrate = std::max<int32_t>(caps.max_bitrate, sc.bitRate);
+        if (sc.flags & DABGPU_SUBCH_DABPLUS) caps.max_dabplus++;
     }
-    ndp_ = (int)dp_index_.size();
+    if (cfg.max_subch) caps.max_subch = cfg.max_subch;                    // ... or what the caller allows
+    if (cfg.max_bitrate) caps.max_bitrate = cfg.max_bitrate;
+    if (cfg.max_dabplus) caps.max_dabplus = cfg.max_dabplus;
+    chk(dabgpu_pipe_create_caps(thread_context(), &pc, &caps, &pipe_), "dabgpu_pipe_create_caps");
+    nsub_ = caps.max_subch;
+    ndp_ = caps.max_dabplus;
+    const int maxbits = std::max(768, 24 * (int)caps.max_bitrate);
+    tab_.assign(cfg.n_streams, cfg.subch);
+    if (cfg.auto_layout) {
+        fibs_.resize(cfg.n_streams);
+        parsed_.resize(cfg.n_streams);
+    }
     // the MSC and the FIBs leave the GPU packed (8 bits per byte, 1/8 of the bytes over
     // PCIe) and are unpacked here for the one-bit-per-byte consumers (dab-concurrent.cpp:191,
     // fibProcessor::process_FIB)
     chk(dabgpu_pipe_set_packed(pipe_, DABGPU_PACK_MSC | DABGPU_PACK_FIC), "dabgpu_pipe_set_packed");
     msc_stride_ = ((maxbits + 7) / 8 + 15) / 16 * 16;
     maxbits_ = maxbits;
-    sf_stride_ = std::max(16, 110 * maxrs);
+    sf_stride_ = std::max(16, 110 * (int)(caps.max_bitrate / 8));
     const size_t SF = (size_t)cfg.n_streams * cfg.n_frames;
     // only the superframes a run completes cross PCIe (DABGPU_SF_SLOTS per subchannel)
     if (ndp_) chk(dabgpu_pipe_set_dabplus_compact(pipe_, 1), "dabgpu_pipe_set_dabplus_compact");
     fic_.resize(SF * 4 * 96);
     crc_.resize(SF * 12);
-    msc_.resize(std::max<size_t>(1, SF * 4 * cfg.subch.size() * msc_stride_));
+    msc_.resize(std::max<size_t>(1, SF * 4 * nsub_ * msc_stride_));
     if (ndp_) {
         sf_.resize(SF * 4 * ndp_ * sf_stride_);
         sfi_.resize(SF * 4 * ndp_ * sizeof(dabgpu_superframe));
     }
+}
+
+void ensembleDecoder::set_subch(int stream, const std::vector<dabgpu_subch> &subch) {
+    chk(dabgpu_pipe_set_subch(pipe_, stream, subch.data(), (int32_t)subch.size()), "dabgpu_pipe_set_subch");
+    for (int s = 0; s < cfg_.n_streams; s++)
+        if (stream < 0 || s == stream) tab_[s] = subch;
+}
+
+std::vector<dabgpu_subch> ensembleDecoder::get_subch(int stream, std::vector<int64_t> *since_cif) const {
+    std::vector<dabgpu_subch> v(std::max(1, nsub_));
+    std::vector<int64_t> since(v.size());
+    int32_t n = 0;
+    chk(dabgpu_pipe_get_subch(pipe_, stream, v.data(), &n, since.data()), "dabgpu_pipe_get_subch");
+    v.resize(n);
+    since.resize(n);
+    if (since_cif) *since_cif = since;
+    return v;
 }
 
 ensembleDecoder::~ensembleDecoder() {
@@ -404,7 +428,7 @@ void ensembleDecoder::acquire() {
 }
 
 bool ensembleDecoder::step() {
-    const int S = cfg_.n_streams, F = cfg_.n_frames, NS = (int)cfg_.subch.size();
+    const int S = cfg_.n_streams, F = cfg_.n_frames, NS = nsub_;
     std::vector<uint8_t> valid((size_t)S * 4 * F);
     const int rc = dabgpu_pipe_run(pipe_, (const float *)iq_.get(), stride_, navail_.data(), (uint8_t *)fic_.get(),
                                    (uint8_t *)crc_.get(), NS ? (uint8_t *)msc_.get() : nullptr, msc_stride_,
@@ -420,29 +444,32 @@ bool ensembleDecoder::step() {
     fic_.download(fic.data(), fic.size());
     crc_.download(crc.data(), crc.size());
     uint8_t fib[256];
-    for (int s = 0; s < S && fib_cb_; s++)
+    for (int s = 0; s < S && (fib_cb_ || cfg_.auto_layout); s++)
         for (int f = 0; f < F; f++) {
             if (!fr[(size_t)s * F + f].committed) continue;
             for (int b = 0; b < 4; b++)
                 for (int k = 0; k < 3; k++) {
                     const uint8_t *pk = fic.data() + (((size_t)s * F + f) * 4 + b) * 96 + 32 * k;   // FIB bytes
                     for (int i = 0; i < 256; i++) fib[i] = (uint8_t)((pk[i >> 3] >> (7 - (i & 7))) & 1);
-                    fib_cb_(s, frames_done_[s] + f, b, fib, crc[((size_t)s * F + f) * 12 + 3 * b + k] != 0);
+                    const bool good = crc[((size_t)s * F + f) * 12 + 3 * b + k] != 0;
+                    if (cfg_.auto_layout && good) fibs_[s].process_FIB(fib, (uint16_t)b);
+                    if (fib_cb_) fib_cb_(s, frames_done_[s] + f, b, fib, good);
                 }
         }
     if (NS && msc_cb_) {
-        std::vector<uint8_t> msc((size_t)S * 4 * F * NS * msc_stride_), bits(maxbits_);
+        std::vector<uint8_t> msc((size_t)S * 4 * F * NS * msc_stride_), bits(maxbits_), ev((size_t)S * 4 * F * NS);
         msc_.download(msc.data(), msc.size());
+        // per entry: delivered and past the entry's own 16-CIF warm-up
+        chk(dabgpu_pipe_msc_entry_valid(pipe_, ev.data()), "dabgpu_pipe_msc_entry_valid");
         for (int s = 0; s < S; s++)
-            for (int c = 0; c < 4 * F; c++) {
-                if (!valid[(size_t)s * 4 * F + c]) continue;
-                for (int k = 0; k < NS; k++) {
+            for (int c = 0; c < 4 * F; c++)
+                for (int k = 0; k < (int)tab_[s].size(); k++) {
+                    if (!ev[((size_t)s * 4 * F + c) * NS + k]) continue;
                     const uint8_t *pk = msc.data() + (((size_t)s * 4 * F + c) * NS + k) * msc_stride_;
-                    const int nbits = 24 * cfg_.subch[k].bitRate;
+                    const int nbits = 24 * tab_[s][k].bitRate;
                     for (int i = 0; i < nbits; i++) bits[i] = (uint8_t)((pk[i >> 3] >> (7 - (i & 7))) & 1);
                     msc_cb_(s, 4 * frames_done_[s] + c, k, bits.data(), nbits);
                 }
-            }
     }
     if (NS && ndp_) {
         chk(dabgpu_pipe_dabplus(pipe_, (uint8_t *)sf_.get(), sf_stride_, (dabgpu_superframe *)sfi_.get()),
@@ -454,17 +481,23 @@ bool ensembleDecoder::step() {
             std::vector<uint8_t> bytes((size_t)S * ndp_ * slots * sf_stride_);
             sfi_.download(info.data(), info.size() * sizeof(dabgpu_superframe));
             sf_.download(bytes.data(), bytes.size());
+            // DAB+ slot d of a stream is its d-th entry flagged DABGPU_SUBCH_DABPLUS
+            std::vector<std::vector<int>> dpi(S);
+            for (int s = 0; s < S; s++)
+                for (int k = 0; k < (int)tab_[s].size(); k++)
+                    if (tab_[s][k].flags & DABGPU_SUBCH_DABPLUS) dpi[s].push_back(k);
             for (size_t r = 0; r < info.size(); r++) {
                 if (info[r].status < 0) continue;
                 const int d = (int)(r % ndp_);
                 const int c = (int)((r / ndp_) % (4 * F));
                 const int s = (int)(r / ndp_ / (4 * F));
-                const int k = dp_index_[d];
+                if (d >= (int)dpi[s].size()) continue;
+                const int k = dpi[s][d];
                 const int slot = info[r].reserved;           // compact output: the superframe's slot
                 const bool has = info[r].status == 3 && slot < slots;
                 sf_cb_(s, 4 * frames_done_[s] + c, k, info[r],
                        bytes.data() + (((size_t)s * ndp_ + d) * slots + (has ? slot : 0)) * sf_stride_,
-                       has ? 110 * (cfg_.subch[k].bitRate / 8) : 0);
+                       has ? 110 * (tab_[s][k].bitRate / 8) : 0);
             }
         }
     }
@@ -472,6 +505,17 @@ bool ensembleDecoder::step() {
         dabgpu_stream_state st;
         chk(dabgpu_pipe_state(pipe_, s, &st), "dabgpu_pipe_state");
         frames_done_[s] += st.frames_run;
+    }
+    // FIC first: a table parsed twice alike (two steps) and not yet applied is applied now
+    for (int s = 0; s < S && cfg_.auto_layout; s++) {
+        std::vector<dabgpu_subch> now;
+        for (const fib_subch &e : fibs_[s].subchannels())
+            now.push_back({e.startAddr, e.length, e.bitRate, e.protLevel, e.uepFlag, e.flags});
+        auto same = [](const std::vector<dabgpu_subch> &x, const std::vector<dabgpu_subch> &y) {
+            return x.size() == y.size() && (x.empty() || !std::memcmp(x.data(), y.data(), x.size() * sizeof(dabgpu_subch)));
+        };
+        if (!now.empty() && same(now, parsed_[s]) && !same(now, tab_[s])) set_subch(s, now);
+        parsed_[s] = now;
     }
     return ok;
 }

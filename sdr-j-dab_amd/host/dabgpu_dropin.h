@@ -472,7 +472,16 @@ public:
         int n_streams = 1;
         int n_frames = 8;                    // frames per step
         int16_t threshold = 3;               // gui.cpp:98-99
-        std::vector<dabgpu_subch> subch;     // decoded in every stream
+        std::vector<dabgpu_subch> subch;     // every stream's initial table (set_subch replaces a stream's)
+        // dabgpu_pipe_caps: table entries, largest bitRate and DAB+ entries a stream's table
+        // may hold (0: what subch needs)
+        int max_subch = 0, max_bitrate = 0, max_dabplus = 0;
+        // FIC first: each stream's table follows its own FIG 0/1 and 0/2 (a fib_processor per
+        // stream, fed its CRC-good FIBs).  At the end of a step() a stream's parsed table is
+        // applied (set_subch) when it is non-empty, equals the one parsed at the end of the
+        // previous step and differs from the applied one; one that exceeds the caps throws
+        // dabgpu::error.
+        bool auto_layout = false;
     };
     using fib_cb = std::function<void(int stream, int64_t frame, int ficno, const uint8_t *bits256, bool crc_ok)>;
     using msc_cb = std::function<void(int stream, int64_t cif, int subch, const uint8_t *bits, int nbits)>;
@@ -501,14 +510,23 @@ public:
     // ran out of samples (the frames it decoded were delivered)
     bool step();
     dabgpu_stream_state state(int stream) const;
+    // Replace the table of one stream (-1: of every stream) for the steps that follow
+    // (dabgpu_pipe_set_subch: unchanged entries go on, the others deliver from the stream's
+    // current CIF + 16).  The subch argument of msc_cb / sf_cb is the entry's index in its
+    // stream's table.
+    void set_subch(int stream, const std::vector<dabgpu_subch> &subch);
+    // the stream's table (dabgpu_pipe_get_subch); since_cif (optional) per entry
+    std::vector<dabgpu_subch> get_subch(int stream, std::vector<int64_t> *since_cif = nullptr) const;
 private:
     config cfg_;
     dabgpu_pipe *pipe_ = nullptr;
     devbuf iq_, fic_, crc_, msc_, sf_, sfi_;
     int64_t stride_ = 0;
     std::vector<int64_t> navail_;
-    int msc_stride_ = 0, sf_stride_ = 0, ndp_ = 0, maxbits_ = 0;
-    std::vector<int> dp_index_;
+    int msc_stride_ = 0, sf_stride_ = 0, ndp_ = 0, maxbits_ = 0, nsub_ = 0;
+    std::vector<std::vector<dabgpu_subch>> tab_;      // [stream] the applied tables
+    std::vector<fib_processor> fibs_;                 // auto_layout: [stream]
+    std::vector<std::vector<dabgpu_subch>> parsed_;   // auto_layout: [stream] parsed at the end of the last step
     std::vector<int64_t> frames_done_;     // frames delivered per stream
     fib_cb fib_cb_;
     msc_cb msc_cb_;

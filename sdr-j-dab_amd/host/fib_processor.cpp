@@ -154,6 +154,7 @@ int fib_processor::fig0_1(const uint8_t *d, int used) {
     int o = used * 8;
     const int id = (int)bits(d, o, 6);
     subchannel &s = sub_[id];
+    s.inUse = true;                                // (SubChId stays unset, as in the reference: fig0_14)
     s.StartAddr = (int32_t)bits(d, o + 6, 10);
     if (bits(d, o + 16, 1) == 0) {                 // short form: UEP table index
         const UepRow &r = uep_table()[bits(d, o + 18, 6)];
@@ -364,6 +365,22 @@ int fib_processor::bind(int8_t tmid, int32_t sid, int16_t compnr) {
     k.service = s;
     k.componentNr = compnr;
     return first_free;
+}
+
+std::vector<fib_subch> fib_processor::subchannels(std::vector<int> *ids) const {
+    std::vector<fib_subch> v;
+    if (ids) ids->clear();
+    for (int id = 0; id < 64; id++) {
+        const subchannel &s = sub_[id];
+        if (!s.inUse) continue;
+        fib_subch e = {(int16_t)s.StartAddr, (int16_t)s.Length, (int16_t)s.BitRate, (int16_t)s.protLevel,
+                          (int16_t)s.uepFlag, 0};
+        for (const component &c : components_)
+            if (c.inUse && c.TMid == 0 && c.subchannelId == id && c.ASCTy == 077) e.flags |= 1;   // DABGPU_SUBCH_DABPLUS
+        v.push_back(e);
+        if (ids) ids->push_back(id);
+    }
+    return v;
 }
 
 // fib-processor.cpp:1142-1163

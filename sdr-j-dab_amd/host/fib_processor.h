@@ -66,6 +66,11 @@ struct audiodata {
     int16_t language;
     int16_t programType;
 };
+// one sub-channel of fib_processor::subchannels(): the fields and layout of dabgpu_subch
+// (dabgpu.h; this header stands without the GPU library's), flags bit 0 = DABGPU_SUBCH_DABPLUS
+struct fib_subch {
+    int16_t startAddr, length, bitRate, protLevel, uepFlag, flags;
+};
 
 class fib_processor {
 public:
@@ -84,6 +89,12 @@ public:
     // false (and *d untouched) where the reference returns without filling it in
     bool dataforAudioService(const std::string &label, audiodata *d);
     bool dataforDataService(const std::string &label, packetdata *d);
+
+    // The FIG 0/1 sub-channels seen since clearEnsemble, ordered by SubChId, as the table
+    // dabgpu_pipe_set_subch takes: startAddr, length, bitRate, protLevel and uepFlag as the
+    // parser stores them; flags = DABGPU_SUBCH_DABPLUS where a bound audio component
+    // (FIG 0/2) on the sub-channel has ASCTy 63.  ids (optional) receives each entry's SubChId.
+    std::vector<fib_subch> subchannels(std::vector<int> *ids = nullptr) const;
 
     std::string ensembleName() const { return ensemble_; }
     std::vector<std::string> serviceLabels() const;
@@ -109,6 +120,7 @@ private:
     struct subchannel {
         int32_t SubChId = 0, StartAddr = 0, Length = 0, uepFlag = 0, protLevel = 0, BitRate = 0;
         int16_t language = 0, FEC_scheme = 0;
+        bool inUse = false;                    // a FIG 0/1 described it (subchannels())
     };
     void fig0(const uint8_t *d);
     void fig1(const uint8_t *d);
