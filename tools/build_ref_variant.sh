@@ -9,7 +9,7 @@ git -C "$ROOT" archive "$REV" sdr-j-dab_amd/csrc include | tar -x -C "$TMP"
 P=$TMP/sdr-j-dab_amd
 mkdir -p "$P/build" "$ROOT/sdr-j-dab_amd/lib/variants"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -w"
-for f in k_ofdm.hip k_demod.hip k_viterbi.hip k_dabplus.hip dabgpu_host.cpp; do
+for f in $(cd "$P/csrc" && ls *.hip *.cpp); do      # whatever the layout holds (the revision's, for a ref variant)
     extra=""; [ "$f" = k_demod.hip ] && extra="-fno-slp-vectorize"
     /opt/rocm/bin/hipcc $FLAGS $extra -x hip -c "$P/csrc/$f" -o "$P/build/$f.o" &
 done
