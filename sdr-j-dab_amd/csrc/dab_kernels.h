@@ -182,8 +182,6 @@ struct DpJob {
     int64_t sf_stride;
     dabgpu_superframe *info;        // [S][ncif][ndp]
     const uint8_t *tabs;            // DP_TAB_BYTES: GF exp, log, fire table, alpha^i multiply, CRC
-    int32_t *cand;                  // [S * ndp * ncif] queue of fire-code-passing candidates
-    int32_t *ncand;                 // its length (reset per launch)
     // compact output (dabgpu_pipe_set_dabplus_compact): the superframes that complete in
     // the run, per (stream, DAB+ subchannel) in CIF order, at sf_compact[(s*ndp+dp)*kmax+k]
     // (stride sf_stride); sf_out is then the pipeline's own sparse scratch

@@ -51,7 +51,6 @@ struct DabPlus {
     uint8_t *ring_d = nullptr;    // [S][NDP][120*DP_MAX_RS]
     DpState *state_d = nullptr;   // [S][NDP]
     uint8_t *code_d = nullptr;    // [S][NDP][4F] superframe verdict per candidate CIF
-    int32_t *cand_d = nullptr;    // [S*NDP*4F + 1] fire-code-passing candidates + count
     hipEvent_t ev = nullptr;      // the last superframe pass
     bool rec = false;
 };
@@ -429,7 +428,6 @@ int dabgpu_pipe_create_caps(dabgpu_ctx *c, const dabgpu_pipe_cfg *cfg, const dab
         A((void **)&p->dp.ring_d, nd * 120 * DP_MAX_RS);
         A((void **)&p->dp.state_d, sizeof(DpState) * nd);
         A((void **)&p->dp.code_d, nd * 4 * p->F);
-        A((void **)&p->dp.cand_d, sizeof(int32_t) * (nd * 4 * p->F + 1));
         if (!rc && (hipMemset(p->dp.ring_d, 0, nd * 120 * DP_MAX_RS) != hipSuccess ||
                     hipMemset(p->dp.state_d, 0, sizeof(DpState) * nd) != hipSuccess))
             rc = fail(DABGPU_E_HIP, "pipe DAB+ init failed");
@@ -469,7 +467,7 @@ int dabgpu_pipe_destroy(dabgpu_pipe *p) {
                     (void *)p->h_snr, (void *)p->h_desc, (void *)p->h_berr})
         if (h) (void)hipHostFree(h);
     for (void *x : {(void *)a.jobs_d, (void *)a.res_d, (void *)dp.sf_sparse_d, (void *)dp.sub_d, (void *)dp.br_d,
-                    (void *)dp.since_d, (void *)dp.ring_d, (void *)dp.state_d, (void *)dp.code_d, (void *)dp.cand_d,
+                    (void *)dp.since_d, (void *)dp.ring_d, (void *)dp.state_d, (void *)dp.code_d,
                     (void *)p->ficprof_d, (void *)p->ring, (void *)p->prof_d, (void *)p->inv_d, (void *)p->substart_d,
                     (void *)p->frames_d, (void *)p->si_d, (void *)p->corr_d, (void *)p->snr_d, (void *)p->fc_d,
                     (void *)p->fcpart_d, (void *)p->desc_d, (void *)p->berr_d, (void *)p->disp_d,
@@ -991,8 +989,6 @@ int dabgpu_pipe_dabplus(dabgpu_pipe *p, uint8_t *sf_bytes, int32_t sf_stride, da
     J.ring = p->dp.ring_d;
     J.state = p->dp.state_d;
     J.code = p->dp.code_d;
-    J.ncand = p->dp.cand_d;
-    J.cand = p->dp.cand_d + 1;
     J.sf_out = sf_bytes;
     J.sf_stride = sf_stride;
     if (p->dp.compact) {

@@ -2,17 +2,18 @@
 // processSuperframe (mp4processor.cpp:107-292) for every DAB+ subchannel of every
 // stream, over the CIFs one pipeline run decoded.
 //
-// Two kernels per run.  k_dp_superframe evaluates every superframe candidate of
-// the run in parallel -- one wave per (stream, subchannel, CIF): the fire code at
-// the oldest of the 5 blocks ending at that CIF and, where it holds, the RS(120,110)
-// decode of the RSDims interleaved codewords, the AU table and the AU CRCs.
-// k_dp_walk then runs the reference's sequential block counting (blocksInBuffer)
-// over the candidates' verdicts, which decides which of them the reference would
-// have evaluated, and carries the last 4 CIFs and the state to the next run.  The
-// RS decoder is a restatement of the reference's Karn-style decoder
+// One kernel, k_dp_layer, one workgroup per (stream, DAB+ subchannel), in three phases;
+// one launch per run of up to 512 frames.  Fire: every CIF of the run is a superframe candidate -- the 5 blocks ending
+// at it -- and one thread per CIF checks the fire code at the oldest block.  Decode: the
+// workgroup's waves take the passing candidates in turn, one wave per superframe: the
+// RS(120,110) decode of the RSDims interleaved codewords, the AU table and the AU
+// CRCs.  Walk: one wave runs the reference's sequential block counting
+// (blocksInBuffer) over the candidates' verdicts, which decides which of them the
+// reference would have evaluated, and carries the last 4 CIFs and the state to the
+// next run.  The RS decoder is a restatement of the reference's Karn-style decoder
 // (reed-solomon.cpp:143-399: syndromes, Berlekamp-Massey, Chien search over all 255
-// positions, Forney), so its return value (errors corrected, or -1) and
-// corrections match it exactly.
+// positions, Forney), so its return value (errors corrected, or -1) and corrections
+// match it exactly.  k_rs is that decoder on its own, one lane per codeword.
 #include "dab_device.h"
 #include "dab_kernels.h"
 
@@ -39,16 +40,11 @@ __device__ __forceinline__ int gdiv(const GfTabs &g, int a, int b) {
     return a ? g.exp[mod255(RS_NN + g.log[a] - g.log[b])] : 0;
 }
 
-// Syndrome i of a codeword whose byte m (m = 0..119, full-codeword position
-// 135 + m; the 135 leading pad bytes are zero and leave the Horner sum at zero)
-// is at src[m * step] (reed-solomon.cpp:231-266).
-__device__ __forceinline__ int rs_syndrome(const uint8_t *src, int step, int wrap, int start, int i, const GfTabs &g) {
-    int s = 0, o = start;
-    for (int m = 0; m < 120; m++) {
-        s = src[o] ^ g.mul[i][s];
-        o += step;
-        if (o >= wrap) o -= wrap;
-    }
+// Syndrome i of the codeword src[0..119] (byte m is full-codeword position 135 + m; the
+// 135 leading pad bytes are zero and leave the Horner sum at zero) (reed-solomon.cpp:231-266).
+__device__ __forceinline__ int rs_syndrome(const uint8_t *src, int i, const GfTabs &g) {
+    int s = 0;
+    for (int m = 0; m < 120; m++) s = src[m] ^ g.mul[i][s];
     return s;
 }
 
@@ -272,60 +268,13 @@ __device__ __forceinline__ uint32_t wave_xor(uint32_t v) {
     return v;
 }
 
-// Superframe candidates.  k_dp_fire, one wave per (stream, DAB+ subchannel), one lane
-// per CIF of the run: the fire code at the oldest block of the 5-CIF window ending at
-// that CIF (firecode-checker.cpp:76-94); a window that holds an undelivered CIF or
-// fails is marked 0, a passing one is queued (about one CIF in five once the
-// superframes are aligned).  k_dp_superframe then runs processSuperframe
-// (mp4processor.cpp:146-292) on the queued candidates only -- RS(120,110) over the
-// RSDims interleaved columns, AU table, AU CRCs -- as a grid of resident waves that load
-// the GF tables once and take candidates from the queue (round 1 launched one wave per
-// candidate, each copying the tables, four in five only to fail the fire code).  Which
-// candidates the reference actually evaluates depends on the superframe state
-// (blocksInBuffer), walked afterwards by k_dp_walk; the verdict of every candidate
-// (0 fire code failed, 2 rejected, 3 decoded) goes to J.code, the record and the
-// corrected bytes of a passing one to their slots.
-// The work of one superframe is spread over the wave: syndromes as direct sums
-// (lane = column x a slice of its rows), Berlekamp-Massey/Chien/Forney one column
-// per lane, each AU CRC in 64 slices joined by x^(8d) shifts (the CRC is linear).
-__global__ __launch_bounds__(64) void k_dp_fire(DpJob J) {
-    __shared__ uint16_t fire[256];
-    const int lane = threadIdx.x, sd = blockIdx.x;      // sd = stream * ndp + dp
-    const int stream = sd / J.ndp, dp = sd - stream * J.ndp;
-    const int br = J.dp_br[sd], sub = J.dp_sub[sd], nbytes = 3 * br;
-    if (sub < 0) return;                                 // absent slot: nothing queued (k_dp_walk writes its records)
-    const int64_t since = J.dp_since[sd];
-    const uint16_t *tf = (const uint16_t *)(J.tabs + offsetof(GfTabs, fire));
-    for (int i = lane; i < 256; i += 64) fire[i] = tf[i];
-    wave_sync();
-    const uint8_t *carry = J.ring + (int64_t)sd * (120 * DP_MAX_RS);
-    for (int c0 = 0; c0 < J.ncif; c0 += 64) {              // wave-uniform trip count
-        const int cl = c0 + lane;
-        bool ok = false;
-        if (cl < J.ncif) {
-            // a window holding an undelivered CIF (de-interleaver warm-up, or a CIF slot the
-            // stream did not fill in this run) is never evaluated
-            ok = !(cl >= J.ncifs[stream] || J.cif0s[stream] + cl - 4 - since < 16);
-            if (ok) {
-                uint32_t x[11];
-#pragma unroll
-                for (int p = 0; p < 11; p++) x[p] = window_byte(J, carry, stream, sub, nbytes, cl, p);
-                ok = fire_ok(x, fire);
-            }
-            J.code[(int64_t)sd * J.ncif + cl] = ok ? 1 : 0;
-        }
-        // one queue reservation per wave (same-address atomics serialise in L2)
-        const uint64_t bal = __ballot(ok);
-        int base = 0;
-        if (lane == 0 && bal) base = atomicAdd(J.ncand, (int)__popcll(bal));
-        base = __shfl(base, 0, 64);
-        if (ok) J.cand[base + __popcll(bal & ((1ull << lane) - 1ull))] = sd * J.ncif + cl;
-    }
-}
-
 // processSuperframe (mp4processor.cpp:146-292) of the candidate window ending at CIF cl of
 // (stream, DAB+ subchannel) sd, by one wave: RS(120,110) over the RSDims columns, the AU
-// table and AU CRCs; the verdict to J.code, the record and corrected bytes to their slots.
+// table and AU CRCs.  The verdict (2 rejected, 3 decoded) goes to J.code, the record and,
+// for a decoded one, the corrected bytes to their slots.  The work is spread over the
+// wave: syndromes as direct sums (lane = column x a slice of its rows), Berlekamp-Massey/
+// Chien/Forney one column per lane, each AU CRC in 64 slices joined by x^(8d) shifts (the
+// CRC is linear).
 // LDS: sfb [120 * DP_MAX_RS], syn_s [10 * DP_MAX_RS], rl [64 * 40], red [64] of the wave.
 __device__ void sf_decode(const DpJob &J, const GfTabs &g, int sd, int cl, uint8_t *sfb, uint32_t *syn_s,
                           uint8_t *rl, int32_t *red, int lane) {
@@ -450,30 +399,11 @@ __device__ void sf_decode(const DpJob &J, const GfTabs &g, int sd, int cl, uint8
     }
 }
 
-__global__ __launch_bounds__(64) void k_dp_superframe(DpJob J) {
-    __shared__ GfTabs g;
-    __shared__ __attribute__((aligned(16))) uint8_t sfb[120 * DP_MAX_RS];
-    __shared__ uint32_t syn_s[10 * DP_MAX_RS];
-    __shared__ uint8_t rl[64 * 40];
-    __shared__ int32_t red[64];
-    const int lane = threadIdx.x;
-    const uint32_t *tabs32 = (const uint32_t *)J.tabs;
-    for (int i = lane; i < (int)sizeof(GfTabs) / 4; i += 64) ((uint32_t *)&g)[i] = tabs32[i];
-    const int ncand = *J.ncand;                          // k_dp_fire's queue (same stream, before)
-    for (int ci = blockIdx.x; ci < ncand; ci += gridDim.x) {
-        wave_sync();                                         // the previous candidate's LDS reads are done
-        const int id = J.cand[ci];
-        sf_decode(J, g, id / J.ncif, id % J.ncif, sfb, syn_s, rl, red, lane);
-    }
-}
-
-// The superframe state machine of addtoFrame (mp4processor.cpp:107-145) over the
-// run's CIFs, one wave per (stream, DAB+ subchannel): blocksInBuffer decides which
-// candidates are evaluated; their verdicts come from k_dp_superframe.  Writes the
-// records of the CIFs without an evaluated superframe, the state, and the carry
-// (the run's last 4 CIFs as bytes) for the next run.
-// addtoFrame's block counting (mp4processor.cpp:107-145) over the run's CIFs of sd, by one
-// wave, and the carry (the run's last 4 CIFs) for the next run; nc: LDS [4 * 3 * 384]
+// The superframe state machine of addtoFrame (mp4processor.cpp:107-145) over the run's
+// CIFs of sd, by one wave: blocksInBuffer decides which candidates the reference
+// evaluates; their verdicts are in J.code.  Writes the records of the CIFs without an
+// evaluated superframe, the state, and the carry (the run's last 4 CIFs as bytes) for
+// the next run.  nc: LDS [4 * 3 * 384]
 __device__ void dp_walk(const DpJob &J, int sd, uint8_t *nc, int lane) {
     const int stream = sd / J.ndp, dp = sd - stream * J.ndp;
     const int br = J.dp_br[sd], sub = J.dp_sub[sd], nbytes = 3 * br;
@@ -550,39 +480,45 @@ __device__ void dp_walk(const DpJob &J, int sd, uint8_t *nc, int lane) {
     if (lane == 0) J.state[sd] = st;
 }
 
-__global__ __launch_bounds__(64) void k_dp_walk(DpJob J) {
-    __shared__ uint8_t nc[4 * 3 * 384];
-    dp_walk(J, blockIdx.x, nc, threadIdx.x);
-}
-
-// The whole layer for one (stream, DAB+ subchannel) in one workgroup of DP_WAVES waves: the
-// fire code of every CIF window (one thread per CIF), the passing candidates' superframes
-// (the waves take them in turn), then the walk -- one launch instead of a queue reset and
-// three dependent launches, the GF tables loaded once per workgroup.  The workgroup's own
-// verdicts are all the walk reads, so no grid-wide step.
+// The whole layer for one (stream, DAB+ subchannel) in one workgroup of DP_WAVES waves.
+// Fire: one thread per CIF checks the fire code at the oldest block of the 5-CIF window
+// ending at that CIF (firecode-checker.cpp:76-94); a window that holds an undelivered CIF
+// or fails is marked 0 in J.code, a passing one (about one CIF in five once the
+// superframes are aligned) is marked 1 and listed in LDS.  Decode: the waves take the
+// listed candidates in turn (sf_decode).  Walk: which candidates the reference actually
+// evaluates depends on the superframe state (dp_walk); the workgroup's own verdicts are all
+// it reads, so the kernel has no grid-wide step and the GF tables are loaded once per
+// workgroup.
+// The list holds DP_LIST CIFs.  A launch runs the fire and decode phases over the CIFs
+// [c0, c1) of the run, at most DP_LIST, and the launch of the run's last CIFs (`last`) then
+// walks the whole run: a run of up to 512 frames is one launch, a longer one takes one per
+// DP_LIST CIFs (launch_dabplus), the earlier launches' verdicts waiting in J.code.  (The same
+// blocks as a loop inside one launch measured 7 % slower for the usual single block, 0.099
+// against 0.092 ms for C5 alone: profiles/kernel_forms_ab.txt.)
 constexpr int DP_WAVES = 8;
-__global__ __launch_bounds__(64 * DP_WAVES) void k_dp_layer(DpJob J) {
+constexpr int DP_LIST = 4 * 512;            // CIFs per launch of the fire and decode phases
+__global__ __launch_bounds__(64 * DP_WAVES) void k_dp_layer(DpJob J, int c0, int c1, int last) {
     __shared__ __attribute__((aligned(16))) GfTabs g;
     __shared__ __attribute__((aligned(16))) uint8_t sfb[DP_WAVES][120 * DP_MAX_RS];
     __shared__ uint32_t syn_s[DP_WAVES][10 * DP_MAX_RS];
     __shared__ uint8_t rl[DP_WAVES][64 * 40];
     __shared__ int32_t red[DP_WAVES][64];
-    __shared__ int16_t cand[4 * 512];
-    __shared__ int32_t ncand;
+    __shared__ int16_t list[DP_LIST];                    // the passing CIFs, relative to c0
+    __shared__ int32_t nlist;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, sd = blockIdx.x;
     const int stream = sd / J.ndp, dp = sd - stream * J.ndp;
     const int br = J.dp_br[sd], sub = J.dp_sub[sd], nbytes = 3 * br;
     if (sub < 0) {                                       // absent slot (the whole workgroup): status -1 records
-        if (w == 0) dp_walk(J, sd, sfb[1], lane);
+        if (w == 0 && last) dp_walk(J, sd, sfb[1], lane);
         return;
     }
     const int64_t since = J.dp_since[sd];
     const uint32_t *tabs32 = (const uint32_t *)J.tabs;
     for (int i = t; i < (int)sizeof(GfTabs) / 4; i += 64 * DP_WAVES) ((uint32_t *)&g)[i] = tabs32[i];
-    if (t == 0) ncand = 0;
+    if (t == 0) nlist = 0;
     __syncthreads();
     const uint8_t *carry = J.ring + (int64_t)sd * (120 * DP_MAX_RS);
-    for (int cl = t; cl < J.ncif; cl += 64 * DP_WAVES) {
+    for (int cl = c0 + t; cl < c1; cl += 64 * DP_WAVES) {
         // a window holding an undelivered CIF (de-interleaver warm-up, or a CIF slot the
         // stream did not fill in this run) is never evaluated
         bool ok = !(cl >= J.ncifs[stream] || J.cif0s[stream] + cl - 4 - since < 16);
@@ -593,20 +529,22 @@ __global__ __launch_bounds__(64 * DP_WAVES) void k_dp_layer(DpJob J) {
             ok = fire_ok(x, g.fire);
         }
         J.code[(int64_t)sd * J.ncif + cl] = ok ? 1 : 0;
-        if (ok) cand[atomicAdd(&ncand, 1)] = (int16_t)cl;
+        if (ok) list[atomicAdd(&nlist, 1)] = (int16_t)(cl - c0);
     }
     __syncthreads();
-    const int nc = ncand;
+    const int nc = nlist;
     for (int ci = w; ci < nc; ci += DP_WAVES) {
-        sf_decode(J, g, sd, cand[ci], sfb[w], syn_s[w], rl[w], red[w], lane);
+        sf_decode(J, g, sd, c0 + list[ci], sfb[w], syn_s[w], rl[w], red[w], lane);
         wave_sync();                                     // this wave's LDS reads are done
     }
+    if (!last) return;
     __syncthreads();                                     // every verdict of sd written (J.code)
     if (w == 0) dp_walk(J, sd, sfb[1], lane);            // (the carry staging reuses an idle stage)
     if (!J.sf_compact) return;
     // compact output: the run's decoded superframes of sd in CIF order (after the walk,
     // status 3 marks exactly the ones the reference evaluated and decoded), slot k of the
-    // k-th; the record's `reserved` byte carries k (0xFF: not stored)
+    // k-th; the record's `reserved` byte carries k (0xFF: not stored).  The list now holds
+    // their CIFs (c0 = 0: launch_dabplus refuses a compact run past DP_LIST CIFs)
     __syncthreads();                                     // the walk's records are written
     if (w == 0) {
         int k = 0;
@@ -618,18 +556,18 @@ __global__ __launch_bounds__(64 * DP_WAVES) void k_dp_layer(DpJob J) {
             const int kk = k + __popcll(bal & ((1ull << lane) - 1ull));
             if (dec) {
                 r->reserved = (uint8_t)(kk < J.kmax ? kk : 0xFF);
-                if (kk < J.kmax) cand[kk] = (int16_t)cl;
+                if (kk < J.kmax) list[kk] = (int16_t)cl;
             } else if (r) {
                 r->reserved = 0xFF;
             }
             k += __popcll(bal);
         }
-        if (lane == 0) ncand = k < J.kmax ? k : J.kmax;
+        if (lane == 0) nlist = k < J.kmax ? k : J.kmax;
     }
     __syncthreads();
-    const int nk = ncand, end = 110 * (br / 8);
+    const int nk = nlist, end = 110 * (br / 8);
     for (int q = w; q < nk; q += DP_WAVES) {             // a wave per superframe, a byte per lane
-        const uint8_t *src = J.sf_out + (((int64_t)stream * J.ncif + cand[q]) * J.ndp + dp) * J.sf_stride;
+        const uint8_t *src = J.sf_out + (((int64_t)stream * J.ncif + list[q]) * J.ndp + dp) * J.sf_stride;
         uint8_t *dst = J.sf_compact + ((int64_t)sd * J.kmax + q) * J.sf_stride;
         for (int i = lane; i < end; i += 64) dst[i] = src[i];
     }
@@ -638,25 +576,14 @@ __global__ __launch_bounds__(64 * DP_WAVES) void k_dp_layer(DpJob J) {
 hipError_t launch_dabplus(hipStream_t st, const DpJob &job) {
     if (job.ndp <= 0 || job.nstreams <= 0) return hipSuccess;
     if (job.ncif < 4) return hipErrorInvalidValue;       // the carry holds the last 4 CIFs
-    static const bool split = [] { const char *e = getenv("DABGPU_DP_SPLIT"); return e && e[0] == '1'; }();   // A/B
-    if (job.sf_compact && job.ncif > 4 * 512) return hipErrorInvalidValue;   // the fused layer only
-    if (job.sf_compact || (!split && job.ncif <= 4 * 512)) {
-        hipLaunchKernelGGL(k_dp_layer, dim3(job.nstreams * job.ndp), dim3(64 * DP_WAVES), 0, st, job);
-        return hipGetLastError();
+    if (job.sf_compact && job.ncif > DP_LIST) return hipErrorInvalidValue;   // the list holds the run's superframes
+    for (int c0 = 0; c0 < job.ncif; c0 += DP_LIST) {
+        const int c1 = c0 + DP_LIST < job.ncif ? c0 + DP_LIST : job.ncif;
+        hipLaunchKernelGGL(k_dp_layer, dim3(job.nstreams * job.ndp), dim3(64 * DP_WAVES), 0, st, job, c0, c1,
+                           c1 == job.ncif ? 1 : 0);
     }
-    hipError_t e = hipMemsetAsync(job.ncand, 0, sizeof(int32_t), st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_dp_fire, dim3(job.nstreams * job.ndp), dim3(64), 0, st, job);
-    // resident waves (about 9 per CU at 16.5 KB of LDS each) draining the queue
-    const int nmax = job.nstreams * job.ndp * job.ncif;
-    hipLaunchKernelGGL(k_dp_superframe, dim3(nmax < 256 * 8 ? nmax : 256 * 8), dim3(64), 0, st, job);
-    hipLaunchKernelGGL(k_dp_walk, dim3(job.nstreams * job.ndp), dim3(64), 0, st, job);
     return hipGetLastError();
 }
-
-}  // namespace dab
-
-namespace dab {
 
 // reedSolomon::dec batched: one lane per codeword (the a19 operator on its own).
 __global__ __launch_bounds__(64) void k_rs(const uint8_t *__restrict__ in, int n, const uint8_t *__restrict__ tabs,
@@ -672,7 +599,7 @@ __global__ __launch_bounds__(64) void k_rs(const uint8_t *__restrict__ in, int n
     for (int k = 0; k < 120; k++) row[k] = in[(int64_t)cw * 120 + k];
     int sy[10];
 #pragma unroll
-    for (int i = 0; i < 10; i++) sy[i] = rs_syndrome(row, 1, 1 << 30, 0, i, g);
+    for (int i = 0; i < 10; i++) sy[i] = rs_syndrome(row, i, g);
     uint8_t *w = rl + lane * 40;
     int nf = 0;
     const int r = rs_solve(sy, g, w, w + 10, w + 20, w + 30, &nf);

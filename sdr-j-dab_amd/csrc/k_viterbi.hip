@@ -6,30 +6,46 @@
 //   strict ">" picks the upper predecessor; full chainback from state 0.
 //
 // gfx950 design
-//   k_acs       one wave64 per PAIR of codewords, one trellis state per lane, the two
-//               codewords' path metrics packed in the 16-bit halves of one VGPR
-//               (v_pk_add_u16 / v_pk_min_u16 do both).  Exactness of 16 bits: metric
-//               spread across states is <= 6 * 1020 (every state is reachable from the
-//               best one in 6 steps, branch metrics are in [0, 1020]), so subtracting a
-//               common offset every 30 steps keeps every metric in [0, 43860] and every
-//               comparison equal to the reference's uint32 one.
+//   k_acs, k_acs2
+//               One wave64 decodes one PAIR of codewords, one trellis state per lane, the
+//               two codewords' path metrics in the 16-bit halves of one VGPR.  (More pairs
+//               per wave, as independent chains interleaved step by step, measured slower
+//               on MI355X for the C3 batch: 0.81 ms with 2 pairs and 1.14 ms with 3
+//               against 0.72 ms per launch -- thread-level parallelism hides the DPP
+//               hazards and the LDS latency better than instruction-level parallelism.)
+//               Exactness of 16 bits: the metric spread across states is <= 6 * 1020 =
+//               6120 (every state is reachable from the best one in 6 steps, branch
+//               metrics are in [0, 1020]).  Every 30 steps renorm() subtracts lane 0's
+//               metric less 6120 from all states, which leaves lane 0 at <= 6120 and so
+//               every state at <= 12240; 30 steps add at most 30 * 1020, so every metric
+//               stays in [0, 42840], a candidate in [0, 43860] < 2^16, and every
+//               comparison equals the reference's uint32 one.
 //               States are relabelled every step (lane L holds state rotl6(L, t mod 6)),
-//               so a butterfly pairs lanes at xor distance 32,16,8,4,2,1.  Each lane
+//               so a butterfly pairs lanes at xor distance M = 32,16,8,4,2,1.  Each lane
 //               forms its two candidates as (metric of the LOWER lane of its pair) +
 //               row A and (metric of the UPPER lane) + row B, the rows chosen per lane
-//               so that the decision is "A > B" in every lane.  The broadcasts are DPP
-//               (quad_perm, row_shr/shl with bank masks) or one permlane16/32_swap.
-//               Both codewords' decisions come from one packed subtract (sign bits of
-//               B - A) and shift into one VGPR (dec_in); every 30 steps they are
-//               unpacked into one 30-bit word per codeword and stored: decisions never
-//               leave the VGPRs as scalar masks.  Branch metrics for 60 steps are built
-//               in LDS by the lanes at once (depuncturing + 16-CIF time de-interleave
-//               fused into that gather), both codewords packed per word.
-//   k_traceback one LANE per codeword, 64 chainbacks per wave in lock-step.  Decision
-//               words of a 30-step chunk for the wave's 64 codewords are staged in LDS
-//               (16 KB, register-prefetched 2 chunks ahead); each step reads the word of
-//               the lane that held the traced state, two steps per LDS round trip.
-//               Bits leave through 2-B stores with the energy-dispersal PRBS xor-ed in.
+//               so that the decision is "A > B" in every lane.  The lane moves (cand<M>):
+//               DPP operands of the adds for M <= 8 (quad_perm; row_shr/shl with bank
+//               masks), two ds_swizzle for M = 16, one v_permlane32_swap for M = 32.
+//               Both codewords' decisions are the sign bits of one packed subtract B - A;
+//               per pair of steps one v_perm and one v_bfi drop the four of them into a
+//               collector VGPR, and at the end of a 30-step word two v_perm unpack the
+//               collectors into one 30-bit word per codeword (bit dpos(k) = step k),
+//               which is stored: decisions never leave the VGPRs as scalar masks.
+//               Branch metrics for a tile of 60 steps are built in LDS by the lanes at
+//               once, both codewords packed per word; depuncturing and the 16-CIF time
+//               de-interleave are fused into the tile loader's gather (two loaders:
+//               input-major for the pipeline's ring, step-major for the operators), and
+//               the ACS reads each step's pair of metric rows ACS_PF steps ahead of use.
+//   k_traceback, k_traceback2
+//               One LANE per codeword, 64 chainbacks per wave in lock-step.  The decision
+//               words of a 30-step chunk of the wave's 64 codewords (16 KB) come through
+//               a 3-deep register ring of prefetched chunks (TB_RING) into one LDS
+//               staging buffer (rows padded to 65 words); each step reads the word of
+//               the lane that held the traced state, two steps per LDS round trip.  The
+//               energy-dispersal PRBS is xor-ed in from LDS, and the bits leave in groups
+//               of 8 chunks (240 bits per codeword): as 16-byte stores of one bit per
+//               byte, or as 2-byte stores when the output is packed.
 //
 // Decision layout (dab_kernels.h dec_word_index): 64-row blocks, each block's chunks
 // contiguous (a codeword's words then lie within 1.7 MB instead of one per 14 MB stride,
@@ -264,20 +280,13 @@ __device__ __forceinline__ uint32_t idx4_seg(int t, int bs, int ib, uint32_t m, 
 }
 // the 4 soft values of one step of one codeword into half H of s[] (erasures and
 // steps past the codeword's end read as 0)
-template <int KIND, int H>
-__device__ __forceinline__ void load4(const Src &c, const int32_t *rowoff, const int (&idx)[4], uint32_t keep,
-                                      u16x2 (&s)[4]) {
+template <int H>
+__device__ __forceinline__ void load4(const Src &c, const int (&idx)[4], uint32_t keep, u16x2 (&s)[4]) {
 #pragma unroll
     for (int e = 0; e < 4; e++) {
-        int off = idx[e];
-        bool k = (keep >> e) & 1u;
-        if constexpr (KIND == SRC_MSC) {
-            const int ro = rowoff[idx[e] & 15];
-            k = k && ro >= 0;                         // delay line still empty: zero
-            off = ro + idx[e];
-        }
+        const bool k = (keep >> e) & 1u;
         // erasures read past the buffer's end: the hardware returns 0
-        s[e][H] = __builtin_amdgcn_raw_buffer_load_b16(c.rs, k ? 2 * off : 0x7FFFFFF0, 0, 0);
+        s[e][H] = __builtin_amdgcn_raw_buffer_load_b16(c.rs, k ? 2 * idx[e] : 0x7FFFFFF0, 0, 0);
     }
 }
 
@@ -407,112 +416,87 @@ __device__ __forceinline__ uint32_t renorm(uint32_t x) {
     return as_u32(as_pk(x) - as_pk(c));
 }
 
-// ACS over one decision word (WS trellis steps, or nst < WS for the last one) for NP
-// codeword pairs (independent chains, interleaved step by step).  bm: this word's
-// half of the tile table.  The words are stored at chunk `ch`; rb[k]: word offset of
-// codeword k's chunk 0 in dec (wave-uniform; < 0: not stored).  One copy of this code
-// serves every word (small hot loop: the instruction cache holds it).
+// ACS of the wave's codeword pair over one decision word (WS trellis steps, or nst < WS
+// for the last one); x: the pair's packed path metrics, cw[k]: codeword k's word.  One
+// copy of this code serves every word (small hot loop: the instruction cache holds it).
 // Decisions: d = B - A per 16-bit half has its sign bit set iff A > B (|A - B| <=
 // spread + 1020 < 2^15), so one packed subtract yields both codewords' decisions;
-// they shift down their half of w (dec_in), 15 steps per half-word, and are
-// unpacked to one word per codeword (step k at bit k) at the end of the word.
+// they gather in two collectors (bits_put above) and are unpacked to one word per
+// codeword (step k at bit dpos(k)) at the end of the word.
 // rp[r]: this lane's branch-metric row of relabelling phase r in the tile table (set once
 // per kernel); U: the word's half of the tile -- each step's read is one ds_read_b64 at
 // an immediate offset, no address arithmetic per word
-template <int NP, bool FULL, int U>
-__device__ __forceinline__ void acs_word_cw(const uint32_t *const (&rp)[6], uint32_t (&x)[NP], int nst,
-                                            uint32_t (&cw)[2 * NP]) {
+template <bool FULL, int U>
+__device__ __forceinline__ void acs_word_cw(const uint32_t *const (&rp)[6], uint32_t &x, int nst, uint32_t (&cw)[2]) {
     static_assert(WS == 30, "two collectors of 8 and 7 step pairs per decision word");
-    uint32_t w[NP], w0[NP], dp[NP];
-#pragma unroll
-    for (int p = 0; p < NP; p++) w[p] = dp[p] = 0;
+    uint32_t w = 0, w0, dp = 0;
     // branch-metric pairs read ACS_PF steps ahead of their use (the LDS latency off the
     // metric chain)
     constexpr int PF = ACS_PF;
-    uint2 tq[NP][PF + 1];
-    auto ldt = [&](int jj, int p) { return *(const uint2 *)(rp[jj % 6] + U * 2 * WS + p * 8 * BRS + 2 * jj); };
+    uint2 tq[PF + 1];
+    auto ldt = [&](int jj) { return *(const uint2 *)(rp[jj % 6] + U * 2 * WS + 2 * jj); };
     sfor<0, PF>([&](auto jc) {
         constexpr int jj = decltype(jc)::value;
-#pragma unroll
-        for (int p = 0; p < NP; p++) tq[p][jj % (PF + 1)] = ldt(jj, p);
+        tq[jj % (PF + 1)] = ldt(jj);
     });
     sfor<0, WS>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
         constexpr int rho = j % 6;
-        uint32_t d[NP];
-        if constexpr (PF > 0 && j + PF < WS) {
-#pragma unroll
-            for (int p = 0; p < NP; p++) tq[p][(j + PF) % (PF + 1)] = ldt(j + PF, p);
-        }
+        uint32_t d = 0;                                  // past the codeword: keep the bit positions
+        if constexpr (PF > 0 && j + PF < WS) tq[(j + PF) % (PF + 1)] = ldt(j + PF);
         if (FULL || j < nst) {
-            sfor<0, NP>([&](auto pc) {
-                constexpr int p = decltype(pc)::value;
-                const uint2 t = PF > 0 ? tq[p][j % (PF + 1)] : ldt(j, p);
-                uint32_t A, B;
-                cand<(32 >> rho)>(x[p], t.x, t.y, A, B);
-                d[p] = as_u32(as_pk(B) - as_pk(A));
-                x[p] = as_u32(__builtin_elementwise_min(as_pk(A), as_pk(B)));
-            });
-        } else {
-#pragma unroll
-            for (int p = 0; p < NP; p++) d[p] = 0;        // past the codeword: keep the bit positions
+            const uint2 t = PF > 0 ? tq[j % (PF + 1)] : ldt(j);
+            uint32_t A, B;
+            cand<(32 >> rho)>(x, t.x, t.y, A, B);
+            d = as_u32(as_pk(B) - as_pk(A));
+            x = as_u32(__builtin_elementwise_min(as_pk(A), as_pk(B)));
         }
-#pragma unroll
-        for (int p = 0; p < NP; p++) {
-            if constexpr ((j & 1) == 0) dp[p] = d[p];
-            else w[p] = bits_put(0x01010101u << ((j >> 1) & 7), w[p], __builtin_amdgcn_perm(d[p], dp[p], 0x0B0A0908u));
-        }
+        if constexpr ((j & 1) == 0) dp = d;
+        else w = bits_put(0x01010101u << ((j >> 1) & 7), w, __builtin_amdgcn_perm(d, dp, 0x0B0A0908u));
         if constexpr (j == 15) {
-#pragma unroll
-            for (int p = 0; p < NP; p++) {
-                w0[p] = w[p];
-                w[p] = 0;
-            }
+            w0 = w;
+            w = 0;
         }
     });
-#pragma unroll
-    for (int p = 0; p < NP; p++) {
-        cw[2 * p] = __builtin_amdgcn_perm(w[p], w0[p], 0x06040200u);
-        cw[2 * p + 1] = __builtin_amdgcn_perm(w[p], w0[p], 0x07050301u);
-    }
-#pragma unroll
-    for (int p = 0; p < NP; p++) x[p] = renorm(x[p]);
+    cw[0] = __builtin_amdgcn_perm(w, w0, 0x06040200u);
+    cw[1] = __builtin_amdgcn_perm(w, w0, 0x07050301u);
+    x = renorm(x);
 }
-// ... and its words stored at chunk offset o (rb[k] < 0: codeword k not stored)
+// ... and its words stored at chunk offset o; rb[k]: word offset of codeword k's chunk 0
+// in dec (wave-uniform; < 0: not stored)
 // (through a buffer descriptor: the word's 32-bit offset is wave-uniform, so the store
 // carries one lane offset register instead of a 64-bit address per lane)
-template <int NP, bool FULL, int U>
-__device__ __forceinline__ void acs_word(const uint32_t *const (&rp)[6], uint32_t (&x)[NP], int nst,
-                                         __amdgpu_buffer_rsrc_t drs, const int64_t (&rb)[2 * NP], int64_t o, int lane) {
-    uint32_t cw[2 * NP];
-    acs_word_cw<NP, FULL, U>(rp, x, nst, cw);
+template <bool FULL, int U>
+__device__ __forceinline__ void acs_word(const uint32_t *const (&rp)[6], uint32_t &x, int nst,
+                                         __amdgpu_buffer_rsrc_t drs, const int64_t (&rb)[2], int64_t o, int lane) {
+    uint32_t cw[2];
+    acs_word_cw<FULL, U>(rp, x, nst, cw);
 #pragma unroll
-    for (int k = 0; k < 2 * NP; k++)
+    for (int k = 0; k < 2; k++)
         if (rb[k] >= 0)
             __builtin_amdgcn_raw_buffer_store_b32(cw[k], drs, 4 * lane, (int)(4 * (rb[k] + o)), 0);
 }
 // the two words of a tile [t0, t0 + VT)
-template <int NP>
-__device__ __forceinline__ void acs_tile(const uint32_t *const (&rp)[6], uint32_t (&x)[NP], int t0, int steps,
-                                         __amdgpu_buffer_rsrc_t drs, const int64_t (&rb)[2 * NP], int lane) {
+__device__ __forceinline__ void acs_tile(const uint32_t *const (&rp)[6], uint32_t &x, int t0, int steps,
+                                         __amdgpu_buffer_rsrc_t drs, const int64_t (&rb)[2], int lane) {
     const int64_t cstride = 64 * 64;                    // words per chunk of a 64-row block
     sfor<0, 2>([&](auto uc) {
         constexpr int u = decltype(uc)::value;
         const int tw = t0 + u * WS;
         if (tw < steps) {
             const int64_t o = (int64_t)(tw / WS) * cstride;
-            if (tw + WS <= steps) acs_word<NP, true, u>(rp, x, WS, drs, rb, o, lane);
-            else acs_word<NP, false, u>(rp, x, steps - tw, drs, rb, o, lane);
+            if (tw + WS <= steps) acs_word<true, u>(rp, x, WS, drs, rb, o, lane);
+            else acs_word<false, u>(rp, x, steps - tw, drs, rb, o, lane);
         }
     });
 }
 
-// NP pairs of codewords per wave: codewords 2*NP*w .. 2*NP*w + 2*NP - 1 (logical order).
-// LDS (kernel-owned, so two jobs in one launch share it): bm[NP*8*BRS], rowoff[2*NP][16]
-template <int NP> struct AcsLds {
-    uint32_t bm[NP * 8 * BRS];
-    int32_t rowoff[2 * NP][16];
-    int2 ro2[NP][16];               // SRC_MSC pair: both codewords' row byte offsets per idx & 15
+// A wave's LDS: its codeword pair is codewords 2w, 2w + 1 (logical order).  Kernel-owned,
+// so two jobs in one launch share it.
+struct AcsLds {
+    uint32_t bm[8 * BRS];           // the tile's branch-metric table (put_bm)
+    int32_t rowoff[2][16];          // SRC_MSC: each codeword's delay-line row offsets (src_of)
+    int2 ro2[16];                   // SRC_MSC pair: both codewords' row byte offsets per idx & 15
 };
 constexpr int32_t RO_EMPTY = 0x40000000;   // byte offset past any ring: the buffer load returns 0
 // Punctured inputs before mother-code position 4t (t wave-uniform: scalar arithmetic);
@@ -546,8 +530,7 @@ __device__ __forceinline__ int in_index(const ProfR &P, int t) {
 constexpr int IN_K = 4;                    // <= 4 * VT inputs per tile: 4 rounds of 64 lanes
 template <int KIND, bool B8>
 __device__ __forceinline__ void acs_tiles_in(const VitJob &J, const Src (&c)[2], int prof, const ProfR &P, int steps,
-                                             const uint32_t (&row)[6], uint32_t (&x)[1],
-                                             __amdgpu_buffer_rsrc_t drs, const int64_t (&rb)[2], uint32_t *bm,
+                                             const uint32_t (&row)[6], uint32_t &x, __amdgpu_buffer_rsrc_t drs, const int64_t (&rb)[2], uint32_t *bm,
                                              const int2 *ro2, int lane) {
     const int frag = __builtin_amdgcn_readfirstlane(J.prof[prof].frag);
     const int ioff = __builtin_amdgcn_readfirstlane(J.prof[prof].inv_off);
@@ -614,84 +597,21 @@ __device__ __forceinline__ void acs_tiles_in(const VitJob &J, const Src (&c)[2],
         put(t0);
         wave_sync();
         if (t0 + VT < steps) fetch(t0 + VT);
-        acs_tile<1>(rp, x, t0, steps, drs, rb, lane);
+        acs_tile(rp, x, t0, steps, drs, rb, lane);
         wave_sync();
     }
 }
 
-template <int KIND, int NP, bool B8 = false>
-__device__ __forceinline__ void acs_body(const VitJob &J, int w, AcsLds<NP> &L) {
-    uint32_t *bm = L.bm;
-    int32_t (*rowoff)[16] = L.rowoff;
-    const int lane = threadIdx.x;
-    Src c[2 * NP];
-    bool any = false;
-#pragma unroll
-    for (int k = 0; k < 2 * NP; k++) {
-        c[k] = src_of<KIND, B8>(J, 2 * NP * w + k, rowoff[k], lane);
-        any = any || c[k].valid;
-    }
-    if (!any) return;
-    if constexpr (KIND == SRC_MSC) {
-        // the pair's two delay-line row tables side by side, in bytes, an empty row (or
-        // an invalid codeword's) as an offset past the buffer: one LDS read and no
-        // compare per soft value pair in the tile loader
-        if (lane < 16) {
-#pragma unroll
-            for (int p = 0; p < NP; p++) {
-                const int32_t a = rowoff[2 * p][lane], b = rowoff[2 * p + 1][lane];
-                constexpr int ESZ = B8 ? 1 : 2;
-                L.ro2[p][lane] = make_int2(a >= 0 && c[2 * p].valid ? ESZ * a : RO_EMPTY,
-                                           b >= 0 && c[2 * p + 1].valid ? ESZ * b : RO_EMPTY);
-            }
-        }
-        wave_sync();
-    }
-    // profiles are wave-uniform: scalar loads, kept out of the vector memory queue
-    const ProfR p0 = prof_regs(J.prof + c[0].prof);
-    bool same = true;
-    int stp[2 * NP], steps = 0;
-#pragma unroll
-    for (int k = 0; k < 2 * NP; k++) {
-        same = same && c[k].prof == c[0].prof;
-        // wave-uniform by construction; readfirstlane keeps the tile/word loops scalar
-        // (a step count in a VGPR turns every loop exit into exec-mask juggling)
-        stp[k] = __builtin_amdgcn_readfirstlane(c[k].valid ? J.prof[c[k].prof].nbits + 6 : 0);
-        steps = max(steps, stp[k]);
-    }
-    same = __builtin_amdgcn_readfirstlane((int)same) != 0;
-    // per-lane LDS row of each relabelling phase (see header): q = output pattern of
-    // butterfly i = rotl6(lane, r) & 31; upper lanes of a pair swap the two rows
-    uint32_t row[6];
-#pragma unroll
-    for (int r = 0; r < 6; r++) {
-        const int i = rotl6(lane, r) & 31;
-        const int q = parity((2 * i) & 0155) | (parity((2 * i) & 0117) << 1) | (parity((2 * i) & 0123) << 2);
-        const bool upper = (lane >> (5 - r)) & 1;
-        row[r] = (uint32_t)((upper ? q ^ 7 : q) * BRS);
-    }
-    uint32_t x[NP];
-    int64_t rb[2 * NP];
-#pragma unroll
-    for (int p = 0; p < NP; p++) x[p] = lane == 0 ? 0u : 0x003F003Fu;   // viterbi.cpp:360-371
-#pragma unroll
-    for (int k = 0; k < 2 * NP; k++) {
-        rb[k] = c[k].valid ? dec_word_index(c[k].drow, J.dec_nch) : -1;
-    }
-    const int64_t cstride = 64 * 64;                    // words per chunk of a 64-row block
-    const __amdgpu_buffer_rsrc_t drs = __builtin_amdgcn_make_buffer_rsrc((void *)J.dec, (short)0, -1, 0x00020000);
-    if constexpr (KIND == SRC_MSC || KIND == SRC_FIC) {
-        // a pair always shares its profile here: SRC_FIC has one, and an SRC_MSC pair is
-        // two consecutive CIFs of one subchannel (ncif = 4F is even)
-        static_assert(NP == 1, "input-major loader: one codeword pair per wave");
-        acs_tiles_in<KIND, B8>(J, c, c[0].prof, p0, steps, row, x, drs, rb, bm, L.ro2[0], lane);
-    } else {
-    // step-major loader (SRC_MOTHER / SRC_FRAG: a pair may have two profiles)
-    // inputs of the next tile are loaded while the current one runs its ACS;
-    // lane < VT handles step t0 + lane
-    u16x2 s[NP][4];                                      // packed {A, B} soft values, per pair
-    // the depuncturing segments of profile 0 as plain scalars; the segment of a tile
-    // is a sum of boundary flags
+// Step-major tile loader (SRC_MOTHER / SRC_FRAG: a pair may have two profiles; P: codeword
+// 0's).  Lane l < VT loads the 4 soft values of step t0 + l of both codewords, at the input
+// indices of idx4, and builds that step's branch metrics; the inputs of the next tile are
+// loaded while the current one runs its ACS.  stp[k]: codeword k's steps.
+__device__ __forceinline__ void acs_tiles_step(const VitJob &J, const Src (&c)[2], const ProfR &P,
+                                               const int (&stp)[2], int steps, const uint32_t (&row)[6], uint32_t &x,
+                                               __amdgpu_buffer_rsrc_t drs, const int64_t (&rb)[2], uint32_t *bm,
+                                               int lane) {
+    const bool same = __builtin_amdgcn_readfirstlane((int)(c[1].prof == c[0].prof)) != 0;
+    u16x2 s[4];                                          // packed {A, B} soft values of this lane's step
     // tb: first step of the tile (wave-uniform); t: this lane's step
     auto fetch = [&](int tb, int t) {
         int i0[4];
@@ -699,41 +619,24 @@ __device__ __forceinline__ void acs_body(const VitJob &J, int w, AcsLds<NP> &L) 
         // one depuncturing segment for the whole tile (wave-uniform, scalar): the
         // segment search of idx4 on the tile's first and last blocks
         const int blo = (4 * tb) >> 7, bhi = (4 * (tb + VT - 1) + 3) >> 7;
-        int bs = 0, bs_hi = 0, ib = p0.in_base[0];
-        uint32_t m = p0.mask[0];
+        int bs = 0, bs_hi = 0, ib = P.in_base[0];
+        uint32_t m = P.mask[0];
 #pragma unroll
         for (int k = 1; k < 4; k++) {
-            if (k < p0.nseg && blo >= p0.blk_end[k - 1]) { bs = p0.blk_end[k - 1]; ib = p0.in_base[k]; m = p0.mask[k]; }
-            if (k < p0.nseg && bhi >= p0.blk_end[k - 1]) bs_hi = p0.blk_end[k - 1];
+            if (k < P.nseg && blo >= P.blk_end[k - 1]) { bs = P.blk_end[k - 1]; ib = P.in_base[k]; m = P.mask[k]; }
+            if (k < P.nseg && bhi >= P.blk_end[k - 1]) bs_hi = P.blk_end[k - 1];
         }
-        const bool useg = p0.nseg > 0 && bhi < p0.last_end && bs == bs_hi;
+        const bool useg = P.nseg > 0 && bhi < P.last_end && bs == bs_hi;
         if (t < stp[0] || (same && t < steps)) {
             if (useg) {
                 k0 = idx4_seg(t, bs, ib, m, i0);
             } else {
-                k0 = idx4(p0, t, i0);
+                k0 = idx4(P, t, i0);
             }
         } else {
             i0[0] = i0[1] = i0[2] = i0[3] = 0;
         }
-        if constexpr (KIND == SRC_MSC) {
-            if (same) {
-#pragma unroll
-                for (int p = 0; p < NP; p++) {
-                    const uint32_t ka = t < stp[2 * p] ? k0 : 0u, kb = t < stp[2 * p + 1] ? k0 : 0u;
-#pragma unroll
-                    for (int e = 0; e < 4; e++) {
-                        const int2 r = L.ro2[p][i0[e] & 15];
-                        const int32_t oa = ((ka >> e) & 1u) ? r.x + 2 * i0[e] : RO_EMPTY;
-                        const int32_t ob = ((kb >> e) & 1u) ? r.y + 2 * i0[e] : RO_EMPTY;
-                        s[p][e][0] = __builtin_amdgcn_raw_buffer_load_b16(c[2 * p].rs, oa, 0, 0);
-                        s[p][e][1] = __builtin_amdgcn_raw_buffer_load_b16(c[2 * p + 1].rs, ob, 0, 0);
-                    }
-                }
-                return;
-            }
-        }
-        sfor<0, 2 * NP>([&](auto kc) {
+        sfor<0, 2>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
             int ik[4];
             uint32_t kk;
@@ -746,12 +649,8 @@ __device__ __forceinline__ void acs_body(const VitJob &J, int w, AcsLds<NP> &L) 
                 ik[0] = ik[1] = ik[2] = ik[3] = 0;
                 if (t < stp[k]) kk = idx4(prof_regs(J.prof + c[k].prof), t, ik);
             }
-            load4<KIND, k & 1>(c[k], rowoff[k], ik, kk, s[k >> 1]);
+            load4<k>(c[k], ik, kk, s);
         });
-    };
-    auto put = [&]() {
-#pragma unroll
-        for (int p = 0; p < NP; p++) put_bm(bm + p * 8 * BRS, lane, s[p]);
     };
     const uint32_t *rp[6];
 #pragma unroll
@@ -759,12 +658,71 @@ __device__ __forceinline__ void acs_body(const VitJob &J, int w, AcsLds<NP> &L) 
     const bool mine = lane < VT;                         // lanes that build a step of the table
     fetch(0, mine ? lane : steps);
     for (int t0 = 0; t0 < steps; t0 += VT) {
-        if (mine) put();
+        if (mine) put_bm(bm, lane, s);
         wave_sync();
         fetch(t0 + VT, mine ? t0 + VT + lane : steps);
-        acs_tile<NP>(rp, x, t0, steps, drs, rb, lane);
+        acs_tile(rp, x, t0, steps, drs, rb, lane);
         wave_sync();
     }
+}
+
+// Wave w of job J decodes codewords 2w and 2w + 1: what both loaders start from -- the
+// pair's sources, its step counts, the lane's branch-metric rows, the start metrics and
+// the decision offsets -- then the job kind's tile loop.
+template <int KIND, bool B8 = false>
+__device__ __forceinline__ void acs_body(const VitJob &J, int w, AcsLds &L) {
+    const int lane = threadIdx.x;
+    Src c[2];
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        c[k] = src_of<KIND, B8>(J, 2 * w + k, L.rowoff[k], lane);
+        any = any || c[k].valid;
+    }
+    if (!any) return;
+    if constexpr (KIND == SRC_MSC) {
+        // the pair's two delay-line row tables side by side, in bytes, an empty row (or
+        // an invalid codeword's) as an offset past the buffer: one LDS read and no
+        // compare per soft value pair in the tile loader
+        if (lane < 16) {
+            const int32_t a = L.rowoff[0][lane], b = L.rowoff[1][lane];
+            constexpr int ESZ = B8 ? 1 : 2;
+            L.ro2[lane] = make_int2(a >= 0 && c[0].valid ? ESZ * a : RO_EMPTY,
+                                    b >= 0 && c[1].valid ? ESZ * b : RO_EMPTY);
+        }
+        wave_sync();
+    }
+    // profiles are wave-uniform: scalar loads, kept out of the vector memory queue
+    const ProfR p0 = prof_regs(J.prof + c[0].prof);
+    int stp[2], steps = 0;
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        // wave-uniform by construction; readfirstlane keeps the tile/word loops scalar
+        // (a step count in a VGPR turns every loop exit into exec-mask juggling)
+        stp[k] = __builtin_amdgcn_readfirstlane(c[k].valid ? J.prof[c[k].prof].nbits + 6 : 0);
+        steps = max(steps, stp[k]);
+    }
+    // per-lane LDS row of each relabelling phase (see header): q = output pattern of
+    // butterfly i = rotl6(lane, r) & 31; upper lanes of a pair swap the two rows
+    uint32_t row[6];
+#pragma unroll
+    for (int r = 0; r < 6; r++) {
+        const int i = rotl6(lane, r) & 31;
+        const int q = parity((2 * i) & 0155) | (parity((2 * i) & 0117) << 1) | (parity((2 * i) & 0123) << 2);
+        const bool upper = (lane >> (5 - r)) & 1;
+        row[r] = (uint32_t)((upper ? q ^ 7 : q) * BRS);
+    }
+    uint32_t x = lane == 0 ? 0u : 0x003F003Fu;           // viterbi.cpp:360-371
+    int64_t rb[2];
+#pragma unroll
+    for (int k = 0; k < 2; k++) rb[k] = c[k].valid ? dec_word_index(c[k].drow, J.dec_nch) : -1;
+    const __amdgpu_buffer_rsrc_t drs = __builtin_amdgcn_make_buffer_rsrc((void *)J.dec, (short)0, -1, 0x00020000);
+    if constexpr (KIND == SRC_MSC || KIND == SRC_FIC) {
+        // a pair always shares its profile here: SRC_FIC has one, and an SRC_MSC pair is
+        // two consecutive CIFs of one subchannel (ncif = 4F is even)
+        acs_tiles_in<KIND, B8>(J, c, c[0].prof, p0, steps, row, x, drs, rb, L.bm, L.ro2, lane);
+    } else {
+        acs_tiles_step(J, c, p0, stp, steps, row, x, drs, rb, L.bm, lane);
     }
 }
 
@@ -1030,17 +988,17 @@ __device__ __forceinline__ void tb_body(const VitJob &J, int blk, uint32_t *stag
 
 template <int KIND, bool B8 = false>
 __global__ __launch_bounds__(64, 8) void k_acs(VitJob J) {
-    __shared__ AcsLds<1> L;
-    acs_body<KIND, 1, B8>(J, xcd_order(blockIdx.x, gridDim.x), L);
+    __shared__ AcsLds L;
+    acs_body<KIND, B8>(J, xcd_order(blockIdx.x, gridDim.x), L);
 }
 // two jobs in one launch (the pipeline's MSC and FIC): blocks [0, nwa) run job A's waves,
 // the rest job B, so B's short waves fill the SIMDs A's last waves leave idle
 template <int KA, int KB, bool B8 = false>
 __global__ __launch_bounds__(64, 8) void k_acs2(VitJob A, VitJob B, int nwa) {
-    __shared__ AcsLds<1> L;
+    __shared__ AcsLds L;
     const int b = blockIdx.x;
-    if (b < nwa) acs_body<KA, 1, B8>(A, xcd_order(b, nwa), L);
-    else acs_body<KB, 1, B8>(B, xcd_order(b - nwa, gridDim.x - nwa), L);
+    if (b < nwa) acs_body<KA, B8>(A, xcd_order(b, nwa), L);
+    else acs_body<KB, B8>(B, xcd_order(b - nwa, gridDim.x - nwa), L);
 }
 // LDS (dynamic): the staging buffer, then tb_prbs_words(dec_nch) PRBS words
 template <int KIND>
@@ -1119,10 +1077,6 @@ static hipError_t launch_kind(hipStream_t st, const VitJob &job, dim3 grid, size
 template <int KIND> struct AcsK { static auto fn() { return k_acs<KIND>; } };
 template <int KIND> struct TbK { static auto fn() { return k_traceback<KIND>; } };
 
-// One codeword pair per wave (NP = 1).  NP > 1 (independent chains interleaved in one
-// wave, fewer waves) measured slower on MI355X for the C3 batch: 0.81 ms (NP=2) and
-// 1.14 ms (NP=3) vs 0.72 ms per launch -- thread-level parallelism hides the
-// DPP hazards and LDS latency better than instruction-level parallelism here.
 // codewords the ACS enumerates: the active (pair, CIF)s with per-stream tables, else every row
 static int acs_count(const VitJob &job) { return job.kind == SRC_MSC && job.ent_prof ? job.n_acs : job.n_cw; }
 

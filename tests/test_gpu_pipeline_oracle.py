@@ -923,3 +923,83 @@ def test_dabplus_compact_output_equals_sparse(ctx):
                         assert ib["reserved"][s, c, d] == 0xFF
                 assert k <= pb.sf_slots
     assert decoded >= S * nd * 2
+
+
+def test_dabplus_run_past_2048_cifs_equals_short_runs(ctx):
+    """a run of F = 520 frames (2,080 CIFs: the DAB+ layer's candidate list holds 2,048, so its
+    fire-code and superframe phases take two blocks, the second of 32 CIFs) decodes what 52 runs
+    of 10 frames decode: MSC bytes, every superframe record and the corrected bytes.  One stream,
+    FIC + one 8 kbit/s EEP-4A DAB+ subchannel (one RS codeword per superframe), at 8 dB, where RS
+    corrects bytes; the stream is a period of 10 frames (40 CIFs = 8 superframes) repeated,
+    assembled as PCM16 from the quantised period.  The count of decoded superframes is the
+    reference path's: the oracle decodes the first two periods, the second is the steady state."""
+    import dabamd
+    from dabamd.synth import Ensemble
+    sub = [(0, 4, 8, 0o104, 0, 1)]
+    P, F, runs, n_ref = 10, 10, 52, 20
+    NF = F * runs                                         # 520 frames, 2,080 CIFs
+    assert 4 * NF > 2048 and NF % P == 0
+    ens = Ensemble(NF + 1, subch=sub, snr_db=8.0, amplitude=_amp(S16))
+    per = pc.to_raw(pc.quantize(ens.generate_period(2, P, truth=False)["iq"], S16), S16)
+    raw = np.empty((1, 2 * ens.length), np.int16)
+    for p, q, m in ens.stream_pieces(P):
+        raw[0, 2 * p:2 * (p + m)] = per[2 * q:2 * (q + m)]
+    # the reference path over the first two periods
+    head = Ensemble(n_ref + 1, subch=sub).length
+    ref = orc.decode_stream(raw[0, :2 * head].astype(np.float32) / 32768.0, n_ref, sub)
+    assert ref["n"] == n_ref
+    mp4 = orc.MP4(8)
+    ref_sf = {c: mp4.add(ref["msc"][c, 0, :192]) for c in range(16, 4 * n_ref)}
+    ref3 = [c for c, o in ref_sf.items() if o["status"] == 3]
+    per_period = sum(1 for c in ref3 if c >= 4 * P)
+    assert per_period == 4 * P // 5                       # every superframe of the steady state decodes
+    assert sum(ref_sf[c]["n_corrected"] for c in ref3) > 0
+    predicted = len(ref3) + per_period * (NF // P - 2)    # the first period has the warm-up
+
+    lens = [ens.length]
+    diq = ctx.put(raw)
+    del raw
+    subs = [dabamd.Subch(sc[0], sc[1], sc[2], sc[3], 1, dabamd.SUBCH_DABPLUS) for sc in sub]
+    fields = ("status", "n_corrected", "num_aus", "au_start", "au_crc_ok")
+
+    def decode(F, runs):
+        pipe = dabamd.Pipeline(ctx, 1, F, subs)
+        try:
+            pipe.set_iq_format(S16)
+            pipe.set_packed(True)
+            pipe.control(dabamd.CTL_ACQ_SYNC)
+            msc, valid, info, sf = [], [], [], []
+            for r in range(runs):
+                _, _, m, v = pipe.run(diq, ens.length, lens, partial=True)
+                i, b = pipe.dabplus()
+                assert pipe.state(0).frames_run == F, (F, r)
+                msc.append(m[0, :, 0, :24].copy())
+                valid.append(v[0].copy())
+                info.append(i[0, :, 0].copy())
+                sf.append(b[0, :, 0, :110].copy())
+            return [np.concatenate(x) for x in (msc, valid, info, sf)]
+        finally:
+            pipe.close()
+
+    try:
+        ma, va, ia, ba = decode(NF, 1)
+        mb, vb, ib, bb = decode(F, runs)
+    finally:
+        diq.free()
+    assert np.array_equal(va, vb) and int(va.sum()) == 4 * NF - 16
+    assert np.array_equal(ma[va != 0], mb[vb != 0])
+    assert len(ia) == len(ib) == 4 * NF                   # every CIF's record is compared
+    for name in fields:
+        assert np.array_equal(ia[name], ib[name]), name
+    dec = ia["status"] == 3
+    print("records", len(ia), "decoded", int(dec.sum()), "predicted", predicted, "RS corrected bytes",
+          int(ia["n_corrected"][dec].sum()))
+    assert np.array_equal(ba[dec], bb[dec])
+    assert int(dec.sum()) == predicted >= 400
+    # the second block's superframes: the steady state's (2048 = 48 mod the period's 40 CIFs)
+    assert np.array_equal(dec[2048:], dec[48:80]) and int(dec[2048:].sum()) >= 32 // 5
+    assert int(ia["n_corrected"][dec].sum()) > 0
+    for c, o in ref_sf.items():                           # and the reference path's records of the head
+        assert ia["status"][c] == o["status"], c
+        if o["status"] == 3:
+            assert ia["n_corrected"][c] == o["n_corrected"] and np.array_equal(ba[c], o["out"][:110]), c
