@@ -110,6 +110,23 @@ __device__ __forceinline__ const void *iq_stream(const void *iq, int64_t base) {
     return (const char *)iq + base * IqFmt<FMT>::bps;
 }
 
+// ---- launchers: a runtime sample format or flag as a template argument.  f is a generic
+// lambda that gets a std::integral_constant and returns the launch's hipError_t; a format
+// that is none of the three is the launcher's hipErrorInvalidValue.
+template <class F>
+inline hipError_t with_fmt(int fmt, F &&f) {
+    switch (fmt) {
+    case DABGPU_IQ_F32: return f(std::integral_constant<int, DABGPU_IQ_F32>{});
+    case DABGPU_IQ_S16: return f(std::integral_constant<int, DABGPU_IQ_S16>{});
+    case DABGPU_IQ_U8: return f(std::integral_constant<int, DABGPU_IQ_U8>{});
+    default: return hipErrorInvalidValue;
+    }
+}
+template <class F>
+inline hipError_t with_bool(bool b, F &&f) {
+    return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
 // FFT-internal product (fused is fine inside the transform)
 __device__ __forceinline__ float2 cmul(float2 a, float wr, float wi) {
     return make_float2(fmaf(a.x, wr, -a.y * wi), fmaf(a.x, wi, a.y * wr));

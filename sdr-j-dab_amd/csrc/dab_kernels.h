@@ -13,7 +13,7 @@ constexpr int FRAME_SOFT = NSYM * SYMBITS;
 constexpr int INPUT_RATE = 2048000;
 
 // device tables for the OFDM kernels (built on the host with the reference's
-// own float expressions, see dabgpu.cpp: make_tables)
+// own float expressions, see dabgpu_ctx.cpp: HostTables)
 // The NCO without its 16 MB table: oscillatorTable[t] (ofdm-processor.cpp:79-81) is
 // float(e^{2 pi i t / 2048000}); with t = 16000 a + 128 b + c it is the float rounding
 // of A[a] (B[b] C[c]) in double (fma complex products), A[a] = e^{2 pi i a/128},

@@ -99,28 +99,12 @@ struct HostTables {
             for (int p = 0; p < 768; p++) sig[p] = 32 * rank[STAGE_COL[p]]++ + STAGE_COL[p];
             for (int r : rank) stage_ok = stage_ok && r == 24;        // a permutation of the 1536 words
             for (int p = 0; p < 768; p++) carrier_bin[4096 + p] = (int16_t)(2 * sig[p]);
-            // bin b of thread t is b0(t) + 64 k3 (k_demod.hip bin0_of); one store half-wave
-            // = 32 threads of one k3: its dump bins take the banks its carriers leave free
-            auto b0 = [](int t) { const int g = t >> 2, tq = t & 3; return (g >> 3) + 8 * (g & 7) + 512 * (((tq & 1) << 1) | (tq >> 1)); };
-            for (int h = 0; h < 8; h++)
-                for (int k3 = 0; k3 < 8; k3++) {
-                    bool used[32] = {};
-                    for (int l = 0; l < 32; l++) {
-                        const int b = b0(32 * h + l) + 64 * k3, cc = carrier_of_bin[b];
-                        if (cc < 0) continue;
-                        const int w = 2 * sig[cc >> 1] + (cc & 1);
-                        carrier_bin[2048 + b] = (int16_t)w;
-                        used[w & 31] = true;
-                    }
-                    int nb = 0;
-                    for (int l = 0; l < 32; l++) {
-                        const int b = b0(32 * h + l) + 64 * k3;
-                        if (carrier_of_bin[b] >= 0) continue;
-                        while (nb < 31 && used[nb]) nb++;
-                        used[nb] = true;
-                        carrier_bin[2048 + b] = (int16_t)(1536 + nb);
-                    }
-                }
+            // a carrier's word: its pair's, even carrier first; the demod stores carriers only
+            // (the other bins keep -1)
+            for (int b = 0; b < 2048; b++) {
+                const int c = carrier_of_bin[b];
+                if (c >= 0) carrier_bin[2048 + b] = (int16_t)(2 * sig[c >> 1] + (c & 1));
+            }
         }
         w2048.resize(2048);                    // k_demod twiddles
         for (int j = 0; j < 2048; j++) {

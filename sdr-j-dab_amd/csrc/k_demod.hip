@@ -12,15 +12,16 @@
 //   pass 1  n = t + 256 m        radix-8 over m, twiddle W2048^(t k1)  -> LDS
 //   pass 2  t = t' + 32 m        radix-8 over m, twiddle W256^(t' k2)  -> LDS
 //   pass 3  t' = t'' + 4 m       radix-8 over m, twiddle W32^(t'' k3)  (registers)
-//   pass 4  radix-4 over t'' across the 4 lanes of a quad (DPP, no LDS)
-// after which thread t (quad g = t>>2 = 8 k1 + k2, t'' = t&3) holds
-// X[k1 + 8 k2 + 64 k3 + 512 brev2(t'')] for k3 = 0..7.  About 110 VGPRs per thread
-// (4 waves per SIMD) instead of a whole FFT per wave: the next symbol's samples are
-// loaded into registers while the current one is transformed, and enough waves are
-// resident to cover HBM latency -- the kernel streams at the HBM roofline's pace.
-// DQPSK (r = X conj(P), q = -re/(|re|+|im|), int16 (q*127)) runs on the thread's own
-// bins; the previous symbol's bins stay in its registers.  Soft bits leave through a
-// 6 KB LDS stage as coalesced 8-byte stores.
+//   pass 4  radix-4 over t'', in registers after an exchange through LDS inside the quad
+// after which thread t (quad g = t>>2 = 8 k1 + k2, a = t&3) holds the two groups k3 = a and
+// a + 4: X[k1 + 8 k2 + 64 k3 + 512 K''], K'' = 0..3 (fft_bin).  One form of the transform
+// for every kernel of this file; the data symbols keep the 6 carriers of the 8 (slot_bin).
+// 116 to 128 VGPRs per thread (4 waves per SIMD) instead of a whole FFT per wave: the next
+// symbol's samples are loaded into registers while the current one is transformed, and
+// enough waves are resident to cover HBM latency -- the kernel streams at the HBM
+// roofline's pace.  DQPSK (r = X conj(P), q = -re/(|re|+|im|), int16 (q*127)) runs on the
+// thread's own carriers; the previous symbol's stay in its registers.  Soft bits leave
+// through a 6 KB LDS stage as coalesced 8-byte stores.
 #include "dab_device.h"
 #include "dab_kernels.h"
 
@@ -40,15 +41,6 @@ __device__ __forceinline__ int32_t nco_index2(int32_t lp0, int32_t phase, int64_
 __device__ __forceinline__ int32_t nco_mod(int64_t v) {
     const int64_t t = v % INPUT_RATE;
     return (int32_t)(t < 0 ? t + INPUT_RATE : t);
-}
-// x - d, x + d mod INPUT_RATE for x, d in [0, INPUT_RATE)
-__device__ __forceinline__ int32_t nco_sub(int32_t x, int32_t d) {
-    x -= d;
-    return x < 0 ? x + INPUT_RATE : x;
-}
-__device__ __forceinline__ int32_t nco_add(int32_t x, int32_t d) {
-    x += d;
-    return x >= INPUT_RATE ? x - INPUT_RATE : x;
 }
 typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
@@ -93,46 +85,6 @@ __device__ __forceinline__ void dft8(float2 (&a)[8]) {
     a[7] = csub(d[6], d[7]);
 }
 
-// radix-2 butterfly across lanes at xor distance M inside a quad:
-// lanes with bit M clear get v + partner, lanes with it set get partner - v
-// (a DPP move + fma; a v_mul + v_add_f32_dpp form measured 2 % slower in this kernel)
-template <int M>
-__device__ __forceinline__ float quad_bfly(float v, float sign) {
-    constexpr int ctrl = M == 2 ? 0x4E : 0xB1;          // quad_perm [2,3,0,1] / [1,0,3,2]
-    // every quad_perm source lane exists: bound_ctrl with full masks, so no old value
-    // (a zeroed destination per move) is needed
-    const float p = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), ctrl, 0xF, 0xF, true));
-    return fmaf(sign, v, p);
-}
-
-// the same butterfly with the lane's sign on the partner: own + sign * partner (upper lanes
-// get minus the butterfly's value; fft2048_wg<true> tracks that sign as tw.tau)
-// The compiler does not fold a DPP move into v_fmac_f32 (it folds add / mul), so the fused
-// form is written out: v_fmac_f32_dpp acc = dpp(src) * sign + acc with acc = src = v, one
-// VALU instead of a DPP move and an fma, the same single rounding.  The s_nop 1 is the two
-// wait states a DPP read needs after the VALU write of its source (the hazard recognizer
-// does not look inside inline assembly).
-// (GFX9 DPP syntax and wait states: gfx942 / gfx950 only; elsewhere -- and in the host
-// pass -- the same value as a DPP move and an fma.  Not volatile: the asm has no side
-// effect beyond its output, so the compiler may schedule around it.)
-template <int M>
-__device__ __forceinline__ float quad_bfly_s(float v, float sign) {
-#if defined(__gfx950__) || defined(__gfx942__)
-    float r;
-    if constexpr (M == 2)
-        asm("s_nop 1\n\tv_fmac_f32_dpp %0, %1, %2 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1"
-            : "=v"(r) : "v"(v), "v"(sign), "0"(v));
-    else
-        asm("s_nop 1\n\tv_fmac_f32_dpp %0, %1, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1"
-            : "=v"(r) : "v"(v), "v"(sign), "0"(v));
-    return r;
-#else
-    constexpr int ctrl = M == 2 ? 0x4E : 0xB1;
-    const float p = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), ctrl, 0xF, 0xF, true));
-    return fmaf(p, sign, v);
-#endif
-}
-
 // v[m] *= oscillatorTable[localPhase] sample by sample (ofdm-processor.cpp:186-201).
 // GEN: localPhase steps by -phase per sample, the table rebuilt from the factor tables
 // in LDS (nco_value; the 16 MB table itself would cost a cache line per sample);
@@ -156,12 +108,6 @@ __device__ __forceinline__ void mix(float2 (&v)[8], const float2 *__restrict__ o
         }
     }
 }
-template <bool GEN>
-__device__ __forceinline__ float2 mix1(float2 v, const float2 *__restrict__ osc, const double2 *ncl, int32_t lp0,
-                                       int32_t phase, int64_t pos, int64_t origin) {
-    if (!GEN || phase == 0) return cmul_exact(v, osc[lp0]);
-    return cmul_exact(v, nco_value(ncl, nco_index2(lp0, phase, pos - origin + 1)));
-}
 // the factor tables into LDS (GEN kernels only; callers __syncthreads before use)
 template <bool GEN>
 __device__ __forceinline__ void nco_setup(double2 *ncl, const OfdmTables &T, int t) {
@@ -169,25 +115,25 @@ __device__ __forceinline__ void nco_setup(double2 *ncl, const OfdmTables &T, int
         for (int i = t; i < NCO_USED; i += DT) ncl[i] = T.nco[i];
 }
 
-struct DemodTw {
-    const float2 *w1;             // LDS table W2048^(t k) at [(k - 1) * 256 + t], k = 1..7
-    const float2 *w2;             // LDS table W256^(t' k) at [(k - 1) * 32 + t']: consecutive lanes, no bank conflicts
-    const float2 *w3;             // LDS table W32^(t'' k) at [(k - 1) * 4 + t'']: a quad's 4 values in 4 different banks
-    float sg2, sg1;               // quad butterfly signs (+1 lower lane, -1 upper)
-    float tau;                    // fft2048_wg<true>'s output sign of this lane (t'' = 1, 2: -1)
-    bool rot;                     // lane t'' == 3 multiplies by -j between the two stages
+// twiddle tables of the FFT in LDS, laid out per pass so that a wave's reads are
+// conflict-free (the values are the W2048 table's entries: W256^j = W2048^(8 j),
+// W32^j = W2048^(64 j)); callers __syncthreads between tw_setup and the first transform
+struct TwLds {
+    float2 w1[7 * DT];      // pass 1: W2048^(t k) at [(k - 1) * 256 + t], k = 1..7 (LDS instead of 14 VGPRs)
+    float2 w2[7 * 32];      // pass 2: W256^(t' k) at [(k - 1) * 32 + t']: consecutive lanes, no bank conflicts
+    float2 w3[7 * 4];       // pass 3: W32^(t'' k) at [(k - 1) * 4 + t'']: a quad's 4 values in 4 different banks
 };
+__device__ __forceinline__ void tw_setup(TwLds &L, const OfdmTables &T, int t) {
+#pragma unroll
+    for (int k = 1; k < 8; k++) L.w1[(k - 1) * DT + t] = T.w2048[(t * k) & 2047];
+    if (t < 7 * 32) L.w2[t] = T.w2048[(8 * ((t & 31) * (t / 32 + 1))) & 2047];
+    if (t < 7 * 4) L.w3[t] = T.w2048[(64 * ((t & 3) * (t / 4 + 1))) & 2047];
+}
 
-// the FFT of the 8 samples a[] (n = t + 256 m) of every thread; ex: 2048 + pad float2 of LDS.
-// SIGNED: each lane's outputs come out times tw.tau (+-1, exact): pass 4's butterflies then
-// take the partner's value as the fma's multiplicand (own + sign * partner), which the
-// compiler folds into one v_fmac_f32_dpp per value and stage instead of a DPP move and an
-// fma.  For DQPSK the sign cancels (X_l conj(X_{l-1}) with both scaled by the same tau: the
-// same products, bit for bit), and |X| is unchanged; the callers that need X itself use
-// SIGNED = false.
-// passes 1-3 of fft2048_wg: afterwards thread t (quad g = t >> 2, t'' = t & 3) holds in a[k3]
-// the radix-4 input t'' of group (g, k3), twiddled by W32^(t'' k3)
-__device__ __forceinline__ void fft2048_p123(float2 (&a)[8], float2 *ex, const DemodTw &tw, int t) {
+// passes 1-3 of the FFT of the 8 samples a[] (n = t + 256 m) of every thread; ex: 2048 + pad
+// float2 of LDS.  Afterwards thread t (quad g = t >> 2, t'' = t & 3) holds in a[k3] the
+// radix-4 input t'' of group (g, k3), twiddled by W32^(t'' k3)
+__device__ __forceinline__ void fft2048_p123(float2 (&a)[8], float2 *ex, const TwLds &tw, int t) {
     // pass 1
     dft8(a);
 #pragma unroll
@@ -216,32 +162,12 @@ __device__ __forceinline__ void fft2048_p123(float2 (&a)[8], float2 *ex, const D
         for (int k = 1; k < 8; k++) a[k] = cmulw(a[k], tw.w3[(k - 1) * 4 + tq]);
     }
 }
-template <bool SIGNED = false>
-__device__ __forceinline__ void fft2048_wg(float2 (&a)[8], float2 *ex, const DemodTw &tw, int t) {
-    fft2048_p123(a, ex, tw, t);
-    // pass 4: radix-4 over the quad's t''; lane t'' ends with K'' = brev2(t'')
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        if constexpr (SIGNED) {
-            float2 v = make_float2(quad_bfly_s<2>(a[k].x, tw.sg2), quad_bfly_s<2>(a[k].y, tw.sg2));
-            if (tw.rot) v = make_float2(v.y, -v.x);
-            a[k] = make_float2(quad_bfly_s<1>(v.x, tw.sg1), quad_bfly_s<1>(v.y, tw.sg1));
-        } else {
-            float2 v = make_float2(quad_bfly<2>(a[k].x, tw.sg2), quad_bfly<2>(a[k].y, tw.sg2));
-            if (tw.rot) v = make_float2(v.y, -v.x);
-            a[k] = make_float2(quad_bfly<1>(v.x, tw.sg1), quad_bfly<1>(v.y, tw.sg1));
-        }
-    }
-}
 
-
-// The data symbols' FFT tail (round 6, k_demod_wg): instead of pass 4's DPP radix-4 across
-// the quad, pass 3's outputs go through LDS inside the quad that produced them -- the 4
-// values t'' = 0..3 of group (g, k3) at ex[g * ZROW + 4 k3 + t''], i.e. row g, which only
-// quad g reads or writes from pass 3 on (each lane overwrites the entries it read in pass 3),
-// so the wave's own program order is all the ordering needed -- and thread t = 4 g + a takes
-// the groups (g, a) and (g, a + 4): the radix-4 over t'' in registers, with the same
-// operations as pass 4 (x0 +- x2, x1 +- x3, -j, then the sums: the spectrum bit for bit).
+// Pass 4, the FFT's tail: pass 3's outputs go through LDS inside the quad that produced
+// them -- the 4 values t'' = 0..3 of group (g, k3) in row g of ex, which only quad g reads
+// or writes from pass 3 on, so the wave's own program order is all the ordering needed --
+// and thread t = 4 g + a takes the groups (g, a) and (g, a + 4): the radix-4 over t'' in
+// registers (x0 +- x2, x1 +- x3, -j, then the sums).
 // Of a group's outputs X[K''] (bin b0(g) + 64 k3 + 512 K''), K'' = 0 and 3 are carriers
 // (bins 1..511, 1536..2047), K'' = 1 only for k3 <= 3 (512..767) and K'' = 2 only for
 // k3 >= 4 (1280..1535): every thread holds exactly 6 carriers -- thread 0 the carrier at
@@ -301,7 +227,8 @@ __device__ __forceinline__ void tail_slots(const Quad4 &A, const Quad4 &B, int t
         if (t == 0) S[0] = b1;
     }
 }
-// all 8 outputs (get_snr, the display feed, the test hook): X[4 grp + K''] at tail_bin(t, grp, K'')
+// all 8 outputs: X[k] = the spectrum at fft_bin(t, k)
+__device__ __forceinline__ int fft_bin(int t, int k) { return tail_bin(t, k >> 2, k & 3); }
 __device__ __forceinline__ void tail_all(const Quad4 &A, const Quad4 &B, float2 (&X)[8]) {
 #pragma unroll
     for (int K = 0; K < 4; K++) {
@@ -309,36 +236,15 @@ __device__ __forceinline__ void tail_all(const Quad4 &A, const Quad4 &B, float2 
         X[4 + K] = r4_out(B, K);
     }
 }
+// the whole transform where every bin is wanted (findIndex, block 0, the one-symbol operator):
+// a[k] = X[fft_bin(t, k)].  The tail reads ex: a barrier before ex is written again.
+__device__ __forceinline__ void fft2048_wg(float2 (&a)[8], float2 *ex, const TwLds &tw, int t) {
+    fft2048_p123(a, ex, tw, t);
+    Quad4 qa, qb;
+    fft2048_tail(a, ex, t, qa, qb);
+    tail_all(qa, qb, a);
+}
 
-// twiddle tables of fft2048_wg in LDS, laid out per pass so that a wave's reads are
-// conflict-free (the values are the W2048 table's entries: W256^j = W2048^(8 j),
-// W32^j = W2048^(64 j))
-struct TwLds {
-    float2 w1[7 * DT];      // pass 1: LDS instead of 14 VGPRs (room for the guard prefetch)
-    float2 w2[7 * 32];
-    float2 w3[7 * 4];
-};
-__device__ __forceinline__ DemodTw tw_setup(TwLds &L, const OfdmTables &T, int t) {
-#pragma unroll
-    for (int k = 1; k < 8; k++) L.w1[(k - 1) * DT + t] = T.w2048[(t * k) & 2047];
-    if (t < 7 * 32) L.w2[t] = T.w2048[(8 * ((t & 31) * (t / 32 + 1))) & 2047];
-    if (t < 7 * 4) L.w3[t] = T.w2048[(64 * ((t & 3) * (t / 4 + 1))) & 2047];
-    DemodTw tw;
-    const int tq = t & 3;
-    tw.w1 = L.w1;
-    tw.w2 = L.w2;
-    tw.w3 = L.w3;
-    tw.sg2 = (tq & 2) ? -1.0f : 1.0f;
-    tw.sg1 = (tq & 1) ? -1.0f : 1.0f;
-    tw.tau = (tq == 1 || tq == 2) ? -1.0f : 1.0f;
-    tw.rot = tq == 3;
-    return tw;
-}
-// FFT bin held in a[k3] by thread t after fft2048_wg
-__device__ __forceinline__ int bin0_of(int t) {
-    const int g = t >> 2, tq = t & 3, k1 = g >> 3, k2 = g & 7;
-    return k1 + 8 * k2 + 512 * (((tq & 1) << 1) | (tq >> 1));
-}
 
 // workgroup reductions (4 waves): sum of floats; max with the lowest index on ties
 struct RedLds {
@@ -374,15 +280,14 @@ __device__ __forceinline__ void wg_argmax(float &best, int &bidx, RedLds &R, int
 // X = FFT(x); r = IFFT(X conj(ref)) = conj(FFT(conj(X conj(ref)))) / 2048; argmax |r|
 // with the first index on ties; -|Max / mean| - 1 when Max < level * mean.
 // Returns startIndex on every thread.
-__device__ __forceinline__ int32_t prs_corr_wg(float2 (&a)[8], float2 *ex, const DemodTw &tw, int t,
+__device__ __forceinline__ int32_t prs_corr_wg(float2 (&a)[8], float2 *ex, const TwLds &tw, int t,
                                                const float2 *__restrict__ ref, int level, RedLds &R,
                                                float &maxv, float &sumv) {
     fft2048_wg(a, ex, tw, t);
-    const int b0 = bin0_of(t);
-    __syncthreads();                                     // pass 3 of the FFT read ex
+    __syncthreads();                                     // the FFT's tail read ex
 #pragma unroll
     for (int k = 0; k < 8; k++) {
-        const int b = b0 + 64 * k;
+        const int b = fft_bin(t, k);
         const float2 r = cmul_conj_exact(a[k], ref[b]);
         ex[b] = make_float2(r.x, -r.y);
     }
@@ -395,10 +300,11 @@ __device__ __forceinline__ int32_t prs_corr_wg(float2 (&a)[8], float2 *ex, const
     float sum = 0.0f, best = -10000.0f;
     int bidx = 0x7fffffff;
 #pragma unroll
-    for (int k = 0; k < 8; k++) {                        // increasing time index per thread
+    for (int k = 0; k < 8; k++) {                        // a thread's time indices are not in order:
         const float v = hypotf(a[k].x * scale, -a[k].y * scale);
+        const int i = fft_bin(t, k);                     // the reference's strict >, so the lower one on ties
         sum += v;
-        if (v > best) { best = v; bidx = b0 + 64 * k; }
+        if (v > best || (v == best && i < bidx)) { best = v; bidx = i; }
     }
     sum = wg_sum(sum, R, t, 1);
     wg_argmax(best, bidx, R, t);
@@ -408,18 +314,17 @@ __device__ __forceinline__ int32_t prs_corr_wg(float2 (&a)[8], float2 *ex, const
     return bidx;
 }
 
-// get_snr (ofdm-decoder.cpp:212-230) of the block-0 spectrum in a[] (bins b0 + 64 k):
+// get_snr (ofdm-decoder.cpp:212-230) of the block-0 spectrum in a[] (bins fft_bin(t, k)):
 // noise = mean |X| over bins 1034..1259 and 788..1013, signal = mean over 1664..2047 and
 // 0..383; get_db(signal) - get_db(noise) with get_db(x) = 20 log10((x + 1) / 256)
 // (dab-constants.h:107-109).  The sums are workgroup trees (the reference adds in bin
 // order): a display value, equal to the sequential one except within float rounding
-// of a dB boundary.
-template <class BinOf>
-__device__ __forceinline__ int16_t snr_wg_b(const float2 (&a)[8], BinOf bin_of, RedLds &R, int t, float unscale) {
+// of a dB boundary -- and the same value from every kernel, which all sum in this order.
+__device__ __forceinline__ int16_t snr_wg(const float2 (&a)[8], int t, RedLds &R, float unscale = 1.0f) {
     float noise = 0.0f, signal = 0.0f;
 #pragma unroll
     for (int k = 0; k < 8; k++) {
-        const int b = bin_of(k);
+        const int b = fft_bin(t, k);
         const float v = hypotf(a[k].x * unscale, a[k].y * unscale);      // (a power of two: exact)
         if ((b >= 1034 && b < 1260) || (b >= 788 && b < 1014)) noise += v;
         if (b >= 1664 || b < 384) signal += v;
@@ -431,10 +336,6 @@ __device__ __forceinline__ int16_t snr_wg_b(const float2 (&a)[8], BinOf bin_of, 
     const float db_s = 20 * log10f((signal / 768 + 1) / (float)256);
     const float db_n = 20 * log10f((noise + 1) / (float)256);
     return (int16_t)(db_s - db_n);
-}
-__device__ __forceinline__ int16_t snr_wg(const float2 (&a)[8], int t, RedLds &R, float unscale = 1.0f) {
-    const int b0 = bin0_of(t);
-    return snr_wg_b(a, [&](int k) { return b0 + 64 * k; }, R, t, unscale);
 }
 
 // (int16_t)((double)q * 127.0) for q = RN(-re / ab1) and the same for im -- the
@@ -478,9 +379,48 @@ __device__ __forceinline__ void soft_pair(float2 r1, float ab1, int &ir, int &ii
 // keeps carriers in pairs at host-chosen words (T.stage_of_bin, T.stage_pair;
 // stage_layout.h): the de-interleave's scattered stores then hit distinct banks in each
 // 32-lane half (3 two-way collisions per symbol, the lower bound, instead of 158 extra
-// cycles), and each pair read covers the 64 banks.  Bins that carry nothing write to 32
-// dump words, each store half-wave's at banks its carriers leave free.
-constexpr int STG = K + 32;
+// cycles), and each pair read covers the 64 banks.  Every slot a thread stores is a carrier
+// (slot_bin), so the stage is the K words and nothing else.
+constexpr int STG = K;
+
+// DQPSK of a carrier against the previous symbol's: r1 = X conj(P) and ab1 = |re| + |im|,
+// the soft bits' common divisor (ofdm-decoder.cpp:185-187)
+struct Dqpsk { float2 r1; float ab1; };
+__device__ __forceinline__ Dqpsk dqpsk(float2 x, float2 p) {
+    const float2 r1 = cmul_conj_exact(x, p);
+    return {r1, fabsf(r1.x) + fabsf(r1.y)};
+}
+
+// frame descriptor checks (the caller guarantees the descriptor; a bad one sets KERR_FRAME):
+// the T_u sync window, resp. `len` samples from block 0, inside the stream
+__device__ __forceinline__ bool lp_ok(int32_t lp) { return lp >= 0 && lp < INPUT_RATE; }
+__device__ __forceinline__ bool window_ok(const dabgpu_frame &fr) {
+    return fr.window >= 0 && fr.window + TU <= fr.n_samples && lp_ok(fr.lp_window);
+}
+__device__ __forceinline__ bool frame_ok(const dabgpu_frame &fr, int64_t len) {
+    return fr.window >= 0 && fr.block0 >= fr.window && fr.block0 + len <= fr.n_samples && lp_ok(fr.lp_window);
+}
+constexpr int64_t FRAME_LEN = TU + (int64_t)NSYM * TS;    // block 0 and the data symbols
+
+// findIndex of the frame's sync window (segment A of the NCO); frame f's startIndex, Max and
+// sum |r| go out through aux when `report`.  Returns startIndex on every thread.
+template <bool GEN, int FMT>
+__device__ __forceinline__ int32_t find_index_wg(const void *s, const dabgpu_frame &fr, const OfdmTables &T,
+                                                 const double2 *ncl, float2 *ex, const TwLds &tw, RedLds &R,
+                                                 int t, const DemodAux &aux, int f, bool report) {
+    float2 a[8];
+#pragma unroll
+    for (int m = 0; m < 8; m++) a[m] = iq_at<FMT>(s, fr.window + t + 256 * m);
+    mix<GEN>(a, T.osc, ncl, fr.lp_window, fr.phase_a, fr.window + t, fr.window);
+    float mx, sm;
+    const int32_t si = prs_corr_wg(a, ex, tw, t, T.ref, aux.level, R, mx, sm);
+    if (report && t == 0) {
+        aux.si[f] = si;
+        if (aux.maxv) aux.maxv[f] = mx;
+        if (aux.sumv) aux.sumv[f] = sm;
+    }
+    return si;
+}
 
 template <bool GEN, bool SYNC, bool R8, int FMT, bool DUMP>
 __global__ __launch_bounds__(DT, DEMOD_WG_PER_SIMD) void k_demod_wg(const void *__restrict__ iq,
@@ -501,7 +441,7 @@ __global__ __launch_bounds__(DT, DEMOD_WG_PER_SIMD) void k_demod_wg(const void *
     // loop's recurrences need them only at a chunk's start, and 6 KB less LDS per workgroup
     // (34 KB) leaves room on a CU beside four workgroups for a traceback wave
     const double2 *ncl = T.nco;
-    const DemodTw tw = tw_setup(twl, T, t);
+    tw_setup(twl, T, t);
     __syncthreads();
     const int item = blockIdx.x;
     const int fi = item / nchunks, ch = item % nchunks;
@@ -515,31 +455,20 @@ __global__ __launch_bounds__(DT, DEMOD_WG_PER_SIMD) void k_demod_wg(const void *
         // ofdm-processor.cpp:344-368): every chunk of the frame correlates the window
         // itself, chunk 0 reports.  A frame whose sync fails, or whose symbols are not
         // all there yet, is skipped (the host's replay does not commit it).
-        if (fr.window < 0 || fr.window + TU > fr.n_samples || fr.lp_window < 0 || fr.lp_window >= INPUT_RATE) {
+        if (!window_ok(fr)) {
             if (t == 0) {
                 atomicOr(T.err, KERR_FRAME);
                 if (ch == 0) aux.si[fi] = -1;
             }
             skip = true;
         } else {
-            float2 a[8];
-#pragma unroll
-            for (int m = 0; m < 8; m++) a[m] = iq_at<FMT>(s, fr.window + t + 256 * m);
-            mix<GEN>(a, T.osc, ncl, fr.lp_window, fr.phase_a, fr.window + t, fr.window);
-            float mx, sm;
-            const int32_t si = prs_corr_wg(a, ex, tw, t, T.ref, aux.level, red, mx, sm);
-            if (ch == 0 && t == 0) {
-                aux.si[fi] = si;
-                if (aux.maxv) aux.maxv[fi] = mx;
-                if (aux.sumv) aux.sumv[fi] = sm;
-            }
+            const int32_t si = find_index_wg<GEN, FMT>(s, fr, T, ncl, ex, twl, red, t, aux, fi, ch == 0);
             if (si < 0) {
                 skip = true;
             } else {
                 fr.block0 = fr.window + si;
-                const int64_t m = ((int64_t)fr.lp_window - ((int64_t)TU + si) * (int64_t)fr.phase_a) % INPUT_RATE;
-                fr.lp_data = (int32_t)(m < 0 ? m + INPUT_RATE : m);
-                skip = fr.block0 + TU + (int64_t)NSYM * TS > fr.n_samples;
+                fr.lp_data = nco_mod((int64_t)fr.lp_window - ((int64_t)TU + si) * (int64_t)fr.phase_a);
+                skip = fr.block0 + FRAME_LEN > fr.n_samples;
             }
             __syncthreads();                             // ex reused below
         }
@@ -547,9 +476,7 @@ __global__ __launch_bounds__(DT, DEMOD_WG_PER_SIMD) void k_demod_wg(const void *
     const int per = (NSYM + nchunks - 1) / nchunks;
     const int l0 = 1 + ch * per, l1 = min(NSYM + 1, l0 + per);
     float2 fc = make_float2(0.0f, 0.0f);
-    // frame_ok: every read inside the stream (the caller guarantees the descriptor)
-    const bool ok = fr.window >= 0 && fr.block0 >= fr.window && fr.block0 + TU + (int64_t)NSYM * TS <= fr.n_samples &&
-                    fr.lp_window >= 0 && fr.lp_window < INPUT_RATE && fr.lp_data >= 0 && fr.lp_data < INPUT_RATE;
+    const bool ok = frame_ok(fr, FRAME_LEN) && lp_ok(fr.lp_data);      // every read inside the stream
     if (!ok && !skip && t == 0) atomicOr(T.err, KERR_FRAME);
     if (l0 <= NSYM && ok && !skip) {
         const int64_t dorg = fr.block0 + TU;           // first sample of segment B
@@ -604,14 +531,14 @@ __global__ __launch_bounds__(DT, DEMOD_WG_PER_SIMD) void k_demod_wg(const void *
             ng7 = ld(ov - 256 * BPS);
 #pragma unroll
             for (int m = 0; m < 8; m++) nx[m] = ld(ov + 256 * BPS * m);
-            fft2048_p123(x, ex, tw, t);
+            fft2048_p123(x, ex, twl, t);
             Quad4 qa, qb;
             fft2048_tail(x, ex, t, qa, qb);
             tail_slots(qa, qb, t, B);
             if (l0 == 1 && aux.snr) {                   // processBlock_0's get_snr (ofdm-decoder.cpp:93)
                 float2 X[8];
                 tail_all(qa, qb, X);
-                const int16_t v = snr_wg_b(X, [&](int k) { return tail_bin(t, k >> 2, k & 3); }, red, t, Fmt::unscale);
+                const int16_t v = snr_wg(X, t, red, Fmt::unscale);
                 if (t == 0) aux.snr[fi] = v;
             }
         }
@@ -696,7 +623,7 @@ __global__ __launch_bounds__(DT, DEMOD_WG_PER_SIMD) void k_demod_wg(const void *
 #pragma unroll
                 for (int m = 0; m < 8; m++) mp[t + 256 * m] = make_float2(a[m].x * Fmt::unscale, a[m].y * Fmt::unscale);
             }
-            fft2048_p123(a, ex, tw, t);
+            fft2048_p123(a, ex, twl, t);
             Quad4 qa, qb;
             fft2048_tail(a, ex, t, qa, qb);
             tail_slots(qa, qb, t, S);
@@ -708,13 +635,13 @@ __global__ __launch_bounds__(DT, DEMOD_WG_PER_SIMD) void k_demod_wg(const void *
                     float2 *sp = aux.spec + ((int64_t)fr.out_slot * NSYM + (l - 1)) * TU;
 #pragma unroll
                     for (int k = 0; k < 8; k++)
-                        sp[tail_bin(t, k >> 2, k & 3)] = make_float2(X[k].x * Fmt::unscale, X[k].y * Fmt::unscale);
+                        sp[fft_bin(t, k)] = make_float2(X[k].x * Fmt::unscale, X[k].y * Fmt::unscale);
                 }
                 if (disp) {                            // the display token's carriers (ofdm-decoder.cpp:197-205)
                     float2 *dp = aux.disp + (int64_t)fr.out_slot * K;
 #pragma unroll
                     for (int k = 0; k < 8; k++) {
-                        const int b = tail_bin(t, k >> 2, k & 3);
+                        const int b = fft_bin(t, k);
                         const float2 v = make_float2(X[k].x * Fmt::unscale, X[k].y * Fmt::unscale);
                         if (b < K / 2) dp[b] = v;
                         else if (b >= TU - 1 - K / 2 && b < TU - 1) dp[b - (TU - 1 - K)] = v;
@@ -729,22 +656,19 @@ __global__ __launch_bounds__(DT, DEMOD_WG_PER_SIMD) void k_demod_wg(const void *
             bool risky = false;
 #pragma unroll
             for (int k = 0; k < 6; k++) {
-                const float2 r1 = cmul_conj_exact(S[k], P[k]);
-                // ibits = (int16_t)(q * 127.0), q = -re / ab1 (IEEE float division) and
-                // ab1 = |re| + |im| (ofdm-decoder.cpp:185-189)
-                const float ab1 = fabsf(r1.x) + fabsf(r1.y);
+                // ibits = (int16_t)(q * 127.0), q = -re / ab1 (IEEE float division, ofdm-decoder.cpp:188-189)
+                const Dqpsk d = dqpsk(S[k], P[k]);
                 int ir, ii;
-                risky |= soft_fast<FMT != DABGPU_IQ_F32>(r1, ab1, ir, ii);
+                risky |= soft_fast<FMT != DABGPU_IQ_F32>(d.r1, d.ab1, ir, ii);
                 *(uint32_t *)((char *)st + cb[k]) = spair(ir, ii);
             }
             if (risky) {
 #pragma unroll
                 for (int k = 0; k < 6; k++) {
-                    const float2 r1 = cmul_conj_exact(S[k], P[k]);
-                    const float ab1 = fabsf(r1.x) + fabsf(r1.y);
+                    const Dqpsk d = dqpsk(S[k], P[k]);
                     int ir, ii;
-                    if (soft_fast<FMT != DABGPU_IQ_F32>(r1, ab1, ir, ii))
-                        *(uint32_t *)((char *)st + cb[k]) = spair(trunc127d(-r1.x / ab1), trunc127d(-r1.y / ab1));
+                    if (soft_fast<FMT != DABGPU_IQ_F32>(d.r1, d.ab1, ir, ii))
+                        *(uint32_t *)((char *)st + cb[k]) = spair(trunc127d(-d.r1.x / d.ab1), trunc127d(-d.r1.y / d.ab1));
                 }
             }
             if (softf) {                               // parity tests only: the float soft values
@@ -752,10 +676,9 @@ __global__ __launch_bounds__(DT, DEMOD_WG_PER_SIMD) void k_demod_wg(const void *
 #pragma unroll
                 for (int k = 0; k < 6; k++) {
                     const int c = T.carrier_of_bin[slot_bin(t, k)];
-                    const float2 r1 = cmul_conj_exact(S[k], P[k]);
-                    const float ab1 = fabsf(r1.x) + fabsf(r1.y);
-                    sf[c] = -r1.x / ab1;
-                    sf[K + c] = -r1.y / ab1;
+                    const Dqpsk d = dqpsk(S[k], P[k]);
+                    sf[c] = -d.r1.x / d.ab1;
+                    sf[K + c] = -d.r1.y / d.ab1;
                 }
             }
             __syncthreads();
@@ -823,29 +746,18 @@ __global__ __launch_bounds__(DT) void k_prs_wg(const void *__restrict__ iq, cons
     __shared__ RedLds red;
     const int t = threadIdx.x, f = blockIdx.x;
     __shared__ double2 ncl[GEN ? NCO_USED : 1];
-    const DemodTw tw = tw_setup(twl, T, t);
+    tw_setup(twl, T, t);
     nco_setup<GEN>(ncl, T, t);
     __syncthreads();
     const dabgpu_frame fr = frames[f];
-    if (fr.window < 0 || fr.window + TU > fr.n_samples || fr.lp_window < 0 || fr.lp_window >= INPUT_RATE) {
+    if (!window_ok(fr)) {
         if (t == 0) {
             atomicOr(T.err, KERR_FRAME);
             aux.si[f] = -1;
         }
         return;
     }
-    const void *s = iq_stream<FMT>(iq, fr.iq_base);
-    float2 a[8];
-#pragma unroll
-    for (int m = 0; m < 8; m++) a[m] = iq_at<FMT>(s, fr.window + t + 256 * m);
-    mix<GEN>(a, T.osc, ncl, fr.lp_window, fr.phase_a, fr.window + t, fr.window);
-    float mx, sm;
-    const int32_t si = prs_corr_wg(a, ex, tw, t, T.ref, aux.level, red, mx, sm);
-    if (t == 0) {
-        aux.si[f] = si;
-        if (aux.maxv) aux.maxv[f] = mx;
-        if (aux.sumv) aux.sumv[f] = sm;
-    }
+    find_index_wg<GEN, FMT>(iq_stream<FMT>(iq, fr.iq_base), fr, T, ncl, ex, twl, red, t, aux, f, true);
 }
 
 // processBlock_0 (ofdm-decoder.cpp:85-162), one workgroup per frame: FFT of block 0
@@ -864,12 +776,11 @@ __global__ __launch_bounds__(DT) void k_block0_wg(const void *__restrict__ iq, c
     __shared__ float cv[96];                             // method 1: correlationVector
     const int t = threadIdx.x, f = blockIdx.x;
     __shared__ double2 ncl[GEN ? NCO_USED : 1];
-    const DemodTw tw = tw_setup(twl, T, t);
+    tw_setup(twl, T, t);
     nco_setup<GEN>(ncl, T, t);
     __syncthreads();
     const dabgpu_frame fr = frames[f];
-    if (fr.window < 0 || fr.block0 < fr.window || fr.block0 + TU > fr.n_samples || fr.lp_window < 0 ||
-        fr.lp_window >= INPUT_RATE) {
+    if (!frame_ok(fr, TU)) {
         if (t == 0) {
             atomicOr(T.err, KERR_FRAME);
             correction[f] = 0;
@@ -882,7 +793,7 @@ __global__ __launch_bounds__(DT) void k_block0_wg(const void *__restrict__ iq, c
 #pragma unroll
     for (int m = 0; m < 8; m++) a[m] = iq_at<FMT>(s, fr.block0 + t + 256 * m);
     mix<GEN>(a, T.osc, ncl, fr.lp_window, fr.phase_a, fr.block0 + t, fr.window);
-    fft2048_wg(a, ex, tw, t);
+    fft2048_wg(a, ex, twl, t);
     {
         const int16_t v = snr_wg(a, t, red);
         if (t == 0 && snr) snr[f] = v;
@@ -891,13 +802,12 @@ __global__ __launch_bounds__(DT) void k_block0_wg(const void *__restrict__ iq, c
         if (t == 0) correction[f] = 0;
         return;
     }
-    __syncthreads();
-    const int b0 = bin0_of(t);
+    __syncthreads();                                     // the FFT's tail read ex
 #pragma unroll
-    for (int k = 0; k < 8; k++) ex[b0 + 64 * k] = a[k];  // natural bin order
+    for (int k = 0; k < 8; k++) ex[fft_bin(t, k)] = a[k];  // natural bin order
     if (method == 0) {
 #pragma unroll
-        for (int k = 0; k < 8; k++) val[b0 + 64 * k] = hypotf(a[k].x, a[k].y);
+        for (int k = 0; k < 8; k++) val[fft_bin(t, k)] = hypotf(a[k].x, a[k].y);
     }
     __syncthreads();
     auto argpair = [&](int i, int j) -> float {          // arg (X[i] conj(X[j]))
@@ -969,23 +879,22 @@ __global__ __launch_bounds__(DT) void k_symbol_wg(const float2 *__restrict__ smp
     __shared__ float2 ex[EXN];
     __shared__ TwLds twl;
     const int t = threadIdx.x;
-    const DemodTw tw = tw_setup(twl, T, t);
+    tw_setup(twl, T, t);
     __syncthreads();
     const float2 *x = smp + (kind ? TG : 0);
     float2 a[8];
 #pragma unroll
     for (int m = 0; m < 8; m++) a[m] = x[t + 256 * m];
-    fft2048_wg(a, ex, tw, t);
-    const int b0 = bin0_of(t);
+    fft2048_wg(a, ex, twl, t);
 #pragma unroll
     for (int k = 0; k < 8; k++) {
-        const int b = b0 + 64 * k;
+        const int b = fft_bin(t, k);
         if (kind) {
             const int c = T.carrier_of_bin[b];
             if (c >= 0) {
-                const float2 r1 = cmul_conj_exact(a[k], spec[b]);
+                const Dqpsk d = dqpsk(a[k], spec[b]);
                 int ir, ii;
-                soft_pair(r1, fabsf(r1.x) + fabsf(r1.y), ir, ii);
+                soft_pair(d.r1, d.ab1, ir, ii);
                 ibits[c] = (int16_t)ir;
                 ibits[K + c] = (int16_t)ii;
             }
@@ -998,10 +907,10 @@ __global__ __launch_bounds__(DT) void k_symbol_wg(const float2 *__restrict__ smp
 // ofdmDecoder::get_snr drop-in, the same workgroup reduction as the fused kernels'
 __global__ __launch_bounds__(DT) void k_snr_wg(const float2 *__restrict__ spec, int16_t *__restrict__ out) {
     __shared__ RedLds red;
-    const int t = threadIdx.x, b0 = bin0_of(t);
+    const int t = threadIdx.x;
     float2 a[8];
 #pragma unroll
-    for (int k = 0; k < 8; k++) a[k] = spec[b0 + 64 * k];
+    for (int k = 0; k < 8; k++) a[k] = spec[fft_bin(t, k)];
     const int16_t v = snr_wg(a, t, red);
     if (t == 0) *out = v;
 }
@@ -1034,46 +943,34 @@ hipError_t launch_demod(hipStream_t st, const void *iq, const dabgpu_frame *fr, 
     if (n <= 0) return hipSuccess;
     const dim3 grid(n * nchunks), block(DT);
     float2 *fp = (float2 *)fcpart;
-#define DEMOD_GO(G, S, R, F, D) \
-    hipLaunchKernelGGL((k_demod_wg<G, S, R, F, D>), grid, block, 0, st, iq, fr, nchunks, T, soft, softf, fp, aux)
-#define DEMOD_GS(R, F)                                              \
-    do {                                                            \
-        if (aux.si) { if (general) DEMOD_GO(true, true, R, F, false); else DEMOD_GO(false, true, R, F, false); } \
-        else { if (general) DEMOD_GO(true, false, R, F, false); else DEMOD_GO(false, false, R, F, false); }     \
-    } while (0)
-    if (aux.mix) {                                     // the NCO / FFT test hook (GEN kernels only)
-        if (!general || !aux.spec) return hipErrorInvalidValue;
-        if (!aux.si) {                                 // the operator form: cf32 in, int16 out
-            if (aux.ring8 || aux.fmt != DABGPU_IQ_F32) return hipErrorInvalidValue;
-            DEMOD_GO(true, false, false, DABGPU_IQ_F32, true);
-        } else {                                       // the pipeline's form: findIndex, RING8, any format
-            if (!aux.ring8) return hipErrorInvalidValue;
-            if (aux.fmt == DABGPU_IQ_S16) DEMOD_GO(true, true, true, DABGPU_IQ_S16, true);
-            else if (aux.fmt == DABGPU_IQ_U8) DEMOD_GO(true, true, true, DABGPU_IQ_U8, true);
-            else if (aux.fmt == DABGPU_IQ_F32) DEMOD_GO(true, true, true, DABGPU_IQ_F32, true);
-            else return hipErrorInvalidValue;
-        }
-    } else if (aux.ring8) {                            // the pipeline's RING8 ring, any sample format
-        if (aux.fmt == DABGPU_IQ_S16) DEMOD_GS(true, DABGPU_IQ_S16);
-        else if (aux.fmt == DABGPU_IQ_U8) DEMOD_GS(true, DABGPU_IQ_U8);
-        else if (aux.fmt == DABGPU_IQ_F32) DEMOD_GS(true, DABGPU_IQ_F32);
-        else return hipErrorInvalidValue;
-    } else {                                           // the operators: cf32 in, int16 out
-        if (aux.fmt != DABGPU_IQ_F32) return hipErrorInvalidValue;
-        DEMOD_GS(false, DABGPU_IQ_F32);
-    }
-#undef DEMOD_GS
-#undef DEMOD_GO
-    return hipGetLastError();
+    const bool sync = aux.si != nullptr, r8 = aux.ring8 != 0, dump = aux.mix != nullptr;
+    if (dump && !aux.spec) return hipErrorInvalidValue;
+    return with_fmt(aux.fmt, [&](auto F) {
+        return with_bool(general, [&](auto G) {
+            return with_bool(sync, [&](auto S) {
+                return with_bool(r8, [&](auto R) {
+                    return with_bool(dump, [&](auto D) {
+                        // The forms that are built; any other combination is an invalid call.
+                        // Soft bits: RING8 (the pipeline's ring) from any sample format, int16
+                        // (the operators) from cf32 only.  The NCO / FFT test hook (DUMP): GEN
+                        // kernels, as the operator (frames given, int16) or as the pipeline
+                        // runs it (findIndex, RING8).
+                        constexpr int f = decltype(F)::value;
+                        constexpr bool g = decltype(G)::value, s = decltype(S)::value, r = decltype(R)::value,
+                                       d = decltype(D)::value;
+                        if constexpr ((r || f == DABGPU_IQ_F32) && (!d || (g && s == r))) {
+                            hipLaunchKernelGGL((k_demod_wg<g, s, r, f, d>), grid, block, 0, st, iq, fr, nchunks, T, soft,
+                                               softf, fp, aux);
+                            return hipGetLastError();
+                        } else {
+                            return hipErrorInvalidValue;
+                        }
+                    });
+                });
+            });
+        });
+    });
 }
-
-#define FMT_DISPATCH(fmt, GO)                                       \
-    do {                                                            \
-        if ((fmt) == DABGPU_IQ_F32) GO(DABGPU_IQ_F32);              \
-        else if ((fmt) == DABGPU_IQ_S16) GO(DABGPU_IQ_S16);         \
-        else if ((fmt) == DABGPU_IQ_U8) GO(DABGPU_IQ_U8);           \
-        else return hipErrorInvalidValue;                           \
-    } while (0)
 
 hipError_t launch_prs_sync(hipStream_t st, const void *iq, int fmt, const dabgpu_frame *fr, int n, const OfdmTables &T,
                            int level, int32_t *si, float *mx, float *sm, bool general) {
@@ -1083,28 +980,24 @@ hipError_t launch_prs_sync(hipStream_t st, const void *iq, int fmt, const dabgpu
     aux.maxv = mx;
     aux.sumv = sm;
     aux.level = level;
-#define PRS_GO(F)                                                                                   \
-    do {                                                                                            \
-        if (general) hipLaunchKernelGGL((k_prs_wg<true, F>), dim3(n), dim3(DT), 0, st, iq, fr, T, aux);  \
-        else hipLaunchKernelGGL((k_prs_wg<false, F>), dim3(n), dim3(DT), 0, st, iq, fr, T, aux);         \
-    } while (0)
-    FMT_DISPATCH(fmt, PRS_GO);
-#undef PRS_GO
-    return hipGetLastError();
+    return with_fmt(fmt, [&](auto F) {
+        return with_bool(general, [&](auto G) {
+            hipLaunchKernelGGL((k_prs_wg<decltype(G)::value, decltype(F)::value>), dim3(n), dim3(DT), 0, st, iq, fr, T, aux);
+            return hipGetLastError();
+        });
+    });
 }
 
 hipError_t launch_block0(hipStream_t st, const void *iq, int fmt, const dabgpu_frame *fr, int n, const OfdmTables &T,
                          int method, int16_t *corr, int16_t *snr, bool general) {
     if (n <= 0) return hipSuccess;
-#define B0_GO(F)                                                                                                 \
-    do {                                                                                                         \
-        if (general) hipLaunchKernelGGL((k_block0_wg<true, F>), dim3(n), dim3(DT), 0, st, iq, fr, T, method, corr, snr); \
-        else hipLaunchKernelGGL((k_block0_wg<false, F>), dim3(n), dim3(DT), 0, st, iq, fr, T, method, corr, snr);        \
-    } while (0)
-    FMT_DISPATCH(fmt, B0_GO);
-#undef B0_GO
-    return hipGetLastError();
+    return with_fmt(fmt, [&](auto F) {
+        return with_bool(general, [&](auto G) {
+            hipLaunchKernelGGL((k_block0_wg<decltype(G)::value, decltype(F)::value>), dim3(n), dim3(DT), 0, st, iq, fr, T,
+                               method, corr, snr);
+            return hipGetLastError();
+        });
+    });
 }
-#undef FMT_DISPATCH
 
 }  // namespace dab

@@ -312,16 +312,11 @@ hipError_t launch_fc_reduce(hipStream_t st, const float *part, int nchunks, int 
 hipError_t launch_acquire(hipStream_t st, const void *iq, int fmt, const AcqJob *jobs, int n, const float2 *osc,
                           AcqResult *res) {
     if (n <= 0) return hipSuccess;
-    if (fmt == DABGPU_IQ_F32) hipLaunchKernelGGL(k_acquire<DABGPU_IQ_F32>, dim3(n), dim3(64), 0, st, iq, jobs, n, osc, res);
-    else if (fmt == DABGPU_IQ_S16) hipLaunchKernelGGL(k_acquire<DABGPU_IQ_S16>, dim3(n), dim3(64), 0, st, iq, jobs, n, osc, res);
-    else if (fmt == DABGPU_IQ_U8) hipLaunchKernelGGL(k_acquire<DABGPU_IQ_U8>, dim3(n), dim3(64), 0, st, iq, jobs, n, osc, res);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return with_fmt(fmt, [&](auto F) {
+        hipLaunchKernelGGL(k_acquire<decltype(F)::value>, dim3(n), dim3(64), 0, st, iq, jobs, n, osc, res);
+        return hipGetLastError();
+    });
 }
-
-}  // namespace dab
-
-namespace dab {
 
 // Recorded IQ to cf32 (dabgpu.h, DABGPU_IQ_*): one thread per 16 input values, 16-byte
 // loads (u8) / 2 x 16-byte loads (s16) and 4 x 16-byte stores; HBM-bound
@@ -359,10 +354,14 @@ hipError_t launch_iq_convert(hipStream_t st, int format, const void *src, int64_
     if (n_values <= 0) return hipSuccess;
     const int64_t threads = (n_values + 15) / 16;
     const dim3 grid((unsigned)((threads + 255) / 256));
-    if (format == DABGPU_IQ_U8) hipLaunchKernelGGL(k_iq_convert<DABGPU_IQ_U8>, grid, dim3(256), 0, st, src, n_values, dst);
-    else if (format == DABGPU_IQ_S16) hipLaunchKernelGGL(k_iq_convert<DABGPU_IQ_S16>, grid, dim3(256), 0, st, src, n_values, dst);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return with_fmt(format, [&](auto F) {
+        if constexpr (decltype(F)::value == DABGPU_IQ_F32) {       // cf32 needs no conversion: not a source format
+            return hipErrorInvalidValue;
+        } else {
+            hipLaunchKernelGGL(k_iq_convert<decltype(F)::value>, grid, dim3(256), 0, st, src, n_values, dst);
+            return hipGetLastError();
+        }
+    });
 }
 
 // ---- device -> pinned host copy (dabgpu_pipe_fetch): a few waves stream 16-byte pieces

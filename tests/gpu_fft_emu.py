@@ -1,10 +1,14 @@
 """TEST INFRASTRUCTURE (a checker, not product): the GPU demod's FFT (k_demod.hip
-fft2048_wg: radix-8 / W2048 twiddles, radix-8 / W256, radix-8 / W32 and the quad's DPP
-radix-4, fma twiddle products, and the fma the compiler contracts inside the radix-8
-butterfly) restated in numpy float32, operation for operation.
+fft2048_p123 + fft2048_tail: radix-8 / W2048 twiddles, radix-8 / W256, radix-8 / W32 and
+the quad's radix-4, fma twiddle products, and the fma the compiler contracts inside the
+radix-8 butterfly) restated in numpy float32, operation for operation.  Pass 4 is written
+here as two butterfly stages across the quad's lanes, own * (+-1) + partner: the kernel
+forms the same x0 +- x2, x1 +- x3, -j and sums in one thread's registers, and a product
+by +-1 is exact, so the values are the same bit for bit.
 tests/test_gpu_parity.py::test_demod_fft_equals_restated_transform pins it bit for bit to
-the fused demod's spectra; tools/soft_floor.py compares its rounding with other fp32
-transforms on the CPU."""
+the fused demod's spectra, test_fft2048_wg_equals_restated_transform to the transform of
+findIndex, block 0 and the one-symbol operator (the same code with all 8 outputs kept);
+tools/soft_floor.py compares its rounding with other fp32 transforms on the CPU."""
 import numpy as np
 f32 = np.float32
 W = np.exp(-2j*np.pi*np.arange(2048)/2048)
@@ -57,7 +61,7 @@ def dft8(ar, ai):  # ar, ai: lists of 8 arrays
         o_r[b]=dr[x]-dr[y]; o_i[b]=di[x]-di[y]
     return o_r, o_i
 def gpu_fft(x):
-    """x: complex64 [..., 2048] -> complex64 X as fft2048_wg computes it"""
+    """x: complex64 [..., 2048] -> complex64 X as k_demod.hip's FFT computes it"""
     xr = x.real.astype(f32); xi = x.imag.astype(f32)
     sh = x.shape[:-1]
     t = np.arange(256)

@@ -473,8 +473,8 @@ def test_demod_nco_values_equal_oscillator_table_recorded(ctx, cfo, fmt):
 
 @pytest.mark.parametrize("fmt", ["f32", "s16", "u8"])
 def test_demod_fft_equals_restated_transform(ctx, fmt):
-    """fft2048_wg as the demod runs it (the SIGNED form: pass 4 as v_fmac_f32_dpp, each
-    lane's outputs times tau = +-1, taken out exactly by the hook), bit for bit against its
+    """The FFT as the demod's symbol loop runs it (fft2048_p123 + fft2048_tail: pass 4 as a
+    radix-4 in registers after the in-quad LDS exchange), bit for bit against its
     operation-for-operation restatement in numpy float32 (tests/gpu_fft_emu.py: radix-8 with
     W2048 twiddles, radix-8 with W256, radix-8 with W32, the quad's radix-4; twiddle
     products as fmas, exact fma emulation).  This pins "the GPU's soft-value deviation is
@@ -502,9 +502,10 @@ def test_demod_fft_equals_restated_transform(ctx, fmt):
 
 
 def test_fft2048_wg_equals_restated_transform(ctx):
-    """fft2048_wg in its plain form -- pass 4 as DPP moves + fmas, the transform of findIndex
-    (phasereference.cpp:60-88), processBlock_0 (ofdm-decoder.cpp:85-162) and the one-symbol
-    drop-in -- bit for bit against tests/gpu_fft_emu.py, through dabgpu_ofdm_symbol (kind 0):
+    """fft2048_wg -- the same passes and tail with all 8 outputs of a thread kept (fft_bin),
+    the transform of findIndex (phasereference.cpp:60-88), processBlock_0
+    (ofdm-decoder.cpp:85-162) and the one-symbol drop-in -- bit for bit against
+    tests/gpu_fft_emu.py, through dabgpu_ofdm_symbol (kind 0):
     complex Gaussian vectors at several scales, a pure carrier, an impulse, zeros, and
     mixed Mode-I symbols"""
     import gpu_fft_emu
@@ -522,6 +523,60 @@ def test_fft2048_wg_equals_restated_transform(ctx):
         want = gpu_fft_emu.gpu_fft(v[None, :])[0]
         neq = (got.real != want.real) | (got.imag != want.imag)
         assert not neq.any(), (i, int(neq.sum()), np.flatnonzero(neq)[:4].tolist())
+
+
+def _tied_prs_window(s):
+    """a sync window whose correlation with the PRS has two bitwise-equal maxima, at s and
+    s + 1024: the time-domain PRS (x 64), rolled by s and folded to period 1024, twice.  The
+    odd bins of its transform are exactly zero (h[n] - h[n] in pass 1), so r[i] and
+    r[i + 1024] are the same sums.  Followed by zeros up to a whole frame."""
+    import dabamd
+    ref = dabamd.host_table(dabamd.TABLE_PRS).astype(np.float64)
+    x = np.roll(np.fft.ifft(ref[:, 0] + 1j * ref[:, 1]) * 64, s)
+    h = (x[:1024] + x[1024:]).astype(np.complex64)
+    iq = np.zeros((196608, 2), np.float32)
+    iq[:2048, 0] = np.tile(h.real, 2)
+    iq[:2048, 1] = np.tile(h.imag, 2)
+    return iq.reshape(-1)
+
+
+def test_find_index_keeps_the_first_of_equal_maxima(ctx):
+    """findIndex (phasereference.cpp:74-82) scans the correlation in index order with a strict
+    >, so of equal maxima it returns the first.  A thread of prs_corr_wg holds both i and
+    i + 1024, and not in increasing order: on a window where |r[i]| == |r[i + 1024]| bit for
+    bit (_tied_prs_window; max / mean is about 197, far above level 3), findIndex alone and
+    the fused kernel's both return s, not s + 1024."""
+    import dabamd
+    fr = dabamd.Frame(iq_base=0, n_samples=196608, window=0, block0=0, out_slot=0, flags=0, lp_window=0, phase_a=0,
+                      lp_data=0, phase_b=0)
+    for s in (0, 5, 700, 1023):
+        iq = ctx.put(_tied_prs_window(s))
+        si, mx, sm = ctx.prs_sync(iq, [fr])
+        si2 = ctx.sync_demod(iq, [fr])[0]
+        iq.free()
+        print(f"s {s}: prs_sync {si[0]}, sync_demod {si2[0]}, max / mean {mx[0] / (sm[0] / 2048):.1f}")
+        assert si[0] == s and si2[0] == s, (s, si[0], si2[0])
+
+
+def test_block0_snr_equals_the_fused_kernels(ctx):
+    """get_snr of block 0 from the fused kernel (one launch) and from processBlock_0's own
+    kernel (the three-launch pass while a coarse AFC is pending) is the same function over
+    the same spectrum and the same thread-to-bin map, summed in the same order: the two
+    passes report the same dB value for a frame, not values a rounding boundary apart."""
+    for cfo in (1300.0, 0.0):
+        g, x, frs = _cfo_frames(cfo)
+        iq = ctx.put(g["iq"])
+        si, snr = ctx.sync_demod(iq, frs)[:2]
+        assert (si >= 0).all(), (cfo, si.tolist())
+        placed = []
+        for fr, i in zip(frs, si):
+            fr = type(fr).from_buffer_copy(fr)
+            fr.block0 = fr.window + int(i)
+            placed.append(fr)
+        _, snr0 = ctx.block0(iq, placed, with_snr=True)
+        iq.free()
+        print(f"cfo {cfo}: startIndex {si.tolist()} snr fused {snr.tolist()} block0 {snr0.tolist()}")
+        assert np.array_equal(snr, snr0), (cfo, snr.tolist(), snr0.tolist())
 
 
 # ---------------------------------------------------------------- pipeline
