@@ -6,6 +6,7 @@
 #include <cstring>
 #include <cstdarg>
 #include <string>
+#include <memory>
 #include <algorithm>
 #include "dabgpu_internal.h"
 #include "stage_layout.h"
@@ -304,15 +305,12 @@ std::vector<uint8_t> dab::make_inv(const Profile &P) {
 
 // ----------------------------------------------------------------- context
 int dab::scratch(dabgpu_ctx *c, int slot, size_t bytes, void **p) {
-    if (c->scratch_sz[slot] < bytes) {
-        if (c->scratch[slot]) HIPCHK(hipFree(c->scratch[slot]));
-        c->scratch[slot] = nullptr;
-        c->scratch_sz[slot] = 0;
-        size_t sz = std::max<size_t>(bytes, 4096);
-        HIPCHK(hipMalloc(&c->scratch[slot], sz));
-        c->scratch_sz[slot] = sz;
+    DevBuf<uint8_t> &b = c->scratch[slot];
+    if (b.n < bytes) {
+        b.reset();
+        HIPCHK(b.alloc(std::max<size_t>(bytes, 4096)));
     }
-    *p = c->scratch[slot];
+    *p = b.ptr;
     return 0;
 }
 
@@ -323,6 +321,9 @@ int dab::kernel_errors(dabgpu_ctx *c) {
     const int32_t e = *c->h_err;
     if (!e) return 0;
     HIPCHK(hipMemsetAsync(c->err, 0, sizeof(int32_t), c->stream));
+    return bounds_error(e);
+}
+int dab::bounds_error(int32_t e) {
     return fail(DABGPU_E_BOUNDS, "kernel refused out-of-bounds work:%s%s", (e & KERR_FRAME) ? " frame descriptor" : "",
                 (e & KERR_VITERBI) ? " viterbi source" : "");
 }
@@ -357,13 +358,6 @@ int dab::demod_chunks(int n, int extra) {
         if (cost < best_cost - 1e-9) { best_cost = cost; best = c; }
     }
     return best;
-}
-
-template <class T>
-static int upload(dabgpu_ctx *c, T **dst, const std::vector<T> &v) {
-    HIPCHK(hipMalloc((void **)dst, v.size() * sizeof(T)));
-    HIPCHK(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
 }
 
 extern "C" {
@@ -425,30 +419,28 @@ int dabgpu_ctx_create(int device, dabgpu_ctx **out) {
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(DABGPU_E_NODEV, "device %d is %s, this build targets gfx950", device, prop.gcnArchName);
     HIPCHK(hipSetDevice(device));
-    auto *c = new dabgpu_ctx();
+    auto c = std::make_unique<dabgpu_ctx>();
     c->device = device;
     // the context stream carries the OFDM front end: highest priority, so a streaming
     // pipeline's next front end takes the SIMDs the Viterbi tail leaves idle
-    {
-        int least = 0, greatest = 0;
-        HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIPCHK(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, greatest));
-    }
-    for (auto &e : c->ev) HIPCHK(hipEventCreate(&e));
+    int least = 0, greatest = 0;
+    HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    HIPCHK(c->stream.create(greatest));
+    for (Event &e : c->ev) HIPCHK(e.create(hipEventDefault));
     const HostTables &t = host_tables();
-    if (!t.stage_ok) {
-        dabgpu_ctx_destroy(c);
-        return fail(DABGPU_E_STATE, "stage_layout.h: STAGE_COL is not 24 pairs per colour");
-    }
-    int rc = 0;
-    if ((rc = upload(c, &c->osc, t.osc)) || (rc = upload(c, &c->nco, t.nco)) || (rc = upload(c, &c->ref, t.ref)) ||
-        (rc = upload(c, &c->w2048, t.w2048)) || (rc = upload(c, &c->carrier_bin, t.carrier_bin)) ||
-        (rc = upload(c, &c->prbs, t.prbs_words)) ||
-        (rc = upload(c, &c->refarg, t.refarg)) || (rc = upload(c, &c->dptab, t.dptab)) ||
-        (rc = upload(c, &c->fic_inv, make_inv(fic_profile())))) {
-        dabgpu_ctx_destroy(c);
-        return rc;
-    }
+    if (!t.stage_ok) return fail(DABGPU_E_STATE, "stage_layout.h: STAGE_COL is not 24 pairs per colour");
+    HIPCHK(c->osc.put(t.osc));
+    HIPCHK(c->nco.put(t.nco));
+    HIPCHK(c->ref.put(t.ref));
+    HIPCHK(c->w2048.put(t.w2048));
+    HIPCHK(c->carrier_bin.put(t.carrier_bin));
+    HIPCHK(c->prbs.put(t.prbs_words));
+    HIPCHK(c->refarg.put(t.refarg));
+    HIPCHK(c->dptab.put(t.dptab));
+    HIPCHK(c->fic_inv.put(make_inv(fic_profile())));
+    HIPCHK(c->err.alloc(1));
+    HIPCHK(hipMemset(c->err, 0, sizeof(int32_t)));
+    HIPCHK(c->h_err.alloc(1));
     c->T.osc = c->osc;
     c->T.nco = c->nco;
     c->T.ref = c->ref;
@@ -457,27 +449,12 @@ int dabgpu_ctx_create(int device, dabgpu_ctx **out) {
     c->T.stage_of_bin = c->carrier_bin + 2048;
     c->T.stage_pair = c->carrier_bin + 4096;
     c->T.refarg = c->refarg;
-    if (hipMalloc((void **)&c->err, sizeof(int32_t)) != hipSuccess || hipMemset(c->err, 0, sizeof(int32_t)) != hipSuccess ||
-        hipHostMalloc((void **)&c->h_err, sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
-        dabgpu_ctx_destroy(c);
-        return fail(DABGPU_E_HIP, "error word alloc");
-    }
     c->T.err = c->err;
-    *out = c;
+    *out = c.release();
     return 0;
 }
 
 int dabgpu_ctx_destroy(dabgpu_ctx *c) {
-    if (!c) return 0;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (void *p : {(void *)c->osc, (void *)c->nco, (void *)c->ref, (void *)c->w2048, (void *)c->carrier_bin, (void *)c->prbs,
-                    (void *)c->refarg, (void *)c->err, (void *)c->dptab, (void *)c->fic_inv})
-        if (p) (void)hipFree(p);
-    if (c->h_err) (void)hipHostFree(c->h_err);
-    for (auto p : c->scratch) if (p) (void)hipFree(p);
-    for (auto e : c->ev) if (e) (void)hipEventDestroy(e);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return 0;
 }
@@ -548,13 +525,13 @@ int dabgpu_kernel_errors(dabgpu_ctx *c) {
 
 int dabgpu_event_record(dabgpu_ctx *c, int slot) {
     if (!c || slot < 0 || slot >= 16) return fail(DABGPU_E_ARG, "bad event slot");
-    HIPCHK(hipEventRecord(c->ev[slot], c->stream));
+    HIPCHK(c->ev[slot].record(c->stream));
     return 0;
 }
 int dabgpu_event_elapsed(dabgpu_ctx *c, int a, int b, float *ms) {
     if (!c || a < 0 || a >= 16 || b < 0 || b >= 16 || !ms) return fail(DABGPU_E_ARG, "bad event slot");
-    HIPCHK(hipEventSynchronize(c->ev[b]));
-    HIPCHK(hipEventElapsedTime(ms, c->ev[a], c->ev[b]));
+    HIPCHK(c->ev[b].sync());
+    HIPCHK(hipEventElapsedTime(ms, c->ev[a].e, c->ev[b].e));
     return 0;
 }
 

@@ -2,7 +2,7 @@
 // ofdmProcessor::run + ficHandler + mscHandler for many ensembles at once (its receiver logic: front_replay.h)
 #include <cstdlib>
 #include <cstring>
-#include <functional>
+#include <memory>
 #include <algorithm>
 #include "dabgpu_internal.h"
 #include "front_replay.h"
@@ -16,26 +16,31 @@ using front::StreamSt;
 // stream so run r+1's demod and MSC never touch a slot run r's MSC still reads; run r+2's
 // front end waits for run r's ACS.  The caller gives consecutive runs different output
 // buffers (or syncs).
+//
+// Destruction order, for every struct below: members go in reverse order of declaration, so
+// each struct declares its stream last and dabgpu_pipe declares `back` and `acq` after its
+// buffers -- a stream has drained and gone before the memory its kernels used is freed.
 struct BackSlot {
-    hipStream_t stream = nullptr;
-    uint32_t *dec = nullptr;         // Viterbi decisions: the MSC's, then the FIC's
-    hipEvent_t ev_copy = nullptr;    // the descriptor block's upload done (before its staging is reused)
-    hipEvent_t ev_back = nullptr;    // the run's back end done
-    hipEvent_t ev_acs = nullptr;     // the run's ACS done (the ring's last reader)
-    bool copy_rec = false, back_rec = false, acs_rec = false;
+    DevBuf<uint32_t> dec;            // Viterbi decisions: the MSC's, then the FIC's
+    Event ev_copy;                   // the descriptor block's upload done (before its staging is reused)
+    Event ev_back;                   // the run's back end done
+    Event ev_acs;                    // the run's ACS done (the ring's last reader)
+    Stream stream;
 };
 // Background null search (DABGPU_CTL_ACQ_ASYNC, the default since round 6): a stream that
 // loses sync after an acquisition is searched on its own low-priority stream while the
 // others keep decoding; its results are taken by the first dabgpu_pipe_run after they arrive
 struct AcqBg {
     bool async = false;              // set true by dabgpu_pipe_create
-    bool inflight = false;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev = nullptr;
-    AcqJob *jobs_d = nullptr, *h_jobs = nullptr;     // [S], and its pinned staging
-    AcqResult *res_d = nullptr, *h_res = nullptr;    // [S]
+    bool inflight = false;           // results pending (the event alone says recorded, not taken)
+    Event ev;
+    DevBuf<AcqJob> jobs_d;           // [S], and its pinned staging
+    PinBuf<AcqJob> h_jobs;
+    DevBuf<AcqResult> res_d;         // [S]
+    PinBuf<AcqResult> h_res;
     std::vector<int> who;
     std::vector<char> acquiring;                     // [S]
+    Stream stream;
 };
 // DAB+ superframe layer (mp4Processor per DAB+ subchannel and stream)
 struct DabPlus {
@@ -43,16 +48,14 @@ struct DabPlus {
     // compact superframe output (dabgpu_pipe_set_dabplus_compact): the layer decodes into
     // this sparse scratch and stores the run's superframes in CIF order for the caller
     bool compact = false;
-    uint8_t *sf_sparse_d = nullptr;
-    size_t sf_sparse_bytes = 0;
-    int32_t *sub_d = nullptr;
-    int16_t *br_d = nullptr;
-    int64_t *since_d = nullptr;   // [S][NDP]
-    uint8_t *ring_d = nullptr;    // [S][NDP][120*DP_MAX_RS]
-    DpState *state_d = nullptr;   // [S][NDP]
-    uint8_t *code_d = nullptr;    // [S][NDP][4F] superframe verdict per candidate CIF
-    hipEvent_t ev = nullptr;      // the last superframe pass
-    bool rec = false;
+    DevBuf<uint8_t> sf_sparse_d;
+    DevBuf<int32_t> sub_d;
+    DevBuf<int16_t> br_d;
+    DevBuf<int64_t> since_d;      // [S][NDP]
+    DevBuf<uint8_t> ring_d;       // [S][NDP][120*DP_MAX_RS]
+    DevBuf<DpState> state_d;      // [S][NDP]
+    DevBuf<uint8_t> code_d;       // [S][NDP][4F] superframe verdict per candidate CIF
+    Event ev;                     // the last superframe pass
 };
 
 struct dabgpu_pipe {
@@ -72,25 +75,26 @@ struct dabgpu_pipe {
     // descriptor tables below and the list of active pairs (rebuild_tables)
     bool uniform = true;
     int n_act = 0;
-    int32_t *ent_prof_d = nullptr, *ent_start_d = nullptr, *act_d = nullptr;
-    int64_t *ent_since_d = nullptr;
+    DevBuf<int32_t> ent_prof_d, ent_start_d, act_d;
+    DevBuf<int64_t> ent_since_d;
     std::vector<uint8_t> entry_valid;   // [S][4F][NSUB] of the last run (dabgpu_pipe_msc_entry_valid)
     std::vector<StreamSt> st;
-    uint8_t *ring = nullptr;         // [S][R][75][3072] RING8 bytes (soft bit + 127, dab_kernels.h)
-    Profile *prof_d = nullptr;       // [NSUB]
-    Profile *ficprof_d = nullptr;
-    uint8_t *inv_d = nullptr;        // the subchannel profiles' inverse depuncturing tables
-    int32_t *substart_d = nullptr;   // [NSUB]
-    dabgpu_frame *frames_d = nullptr;
-    int32_t *si_d = nullptr;
-    int16_t *corr_d = nullptr, *snr_d = nullptr;
-    float *fc_d = nullptr, *fcpart_d = nullptr;
+    DevBuf<uint8_t> ring;            // [S][R][75][3072] RING8 bytes (soft bit + 127, dab_kernels.h)
+    DevBuf<Profile> prof_d;          // [NSUB]
+    DevBuf<Profile> ficprof_d;
+    DevBuf<uint8_t> inv_d;           // the subchannel profiles' inverse depuncturing tables
+    DevBuf<int32_t> substart_d;      // [NSUB]
+    DevBuf<dabgpu_frame> frames_d;
+    DevBuf<int32_t> si_d;
+    DevBuf<int16_t> corr_d, snr_d;
+    DevBuf<float> fc_d, fcpart_d;    // [S*F] float2, [S*F][kMaxChunks] float2
     // the back end's per-run descriptors, one block per back-end stream (parity), uploaded
     // with ONE copy per run (each runtime copy is a kernel of its own on the back-end
     // stream, ~6 us, in front of the ACS): [S] int64 CIF index of each stream's first CIF
     // slot | [S] int32 CIFs each stream delivered | [S * F] int32 FIC ring slots;
     // h_desc: their pinned staging, BackSlot::ev_copy marks the upload done before reuse
-    uint8_t *desc_d = nullptr, *h_desc = nullptr;
+    DevBuf<uint8_t> desc_d;
+    PinBuf<uint8_t> h_desc;
     size_t desc_sz = 0;
     int64_t *cif0_dev(int par) const { return (int64_t *)(desc_d + par * desc_sz); }
     int32_t *ncif_dev(int par) const { return (int32_t *)(desc_d + par * desc_sz + 8 * (size_t)S); }
@@ -98,24 +102,24 @@ struct dabgpu_pipe {
     int64_t *h_cif0(int par) const { return (int64_t *)(h_desc + par * desc_sz); }
     int32_t *h_ncif(int par) const { return (int32_t *)(h_desc + par * desc_sz + 8 * (size_t)S); }
     int32_t *h_slots(int par) const { return (int32_t *)(h_desc + par * desc_sz + 12 * (size_t)S); }
-    BackSlot back[2];
     int cur = 0;                     // back-end stream of the last run
     int64_t run_idx = 0;
     int64_t dec_fic_off = 0;         // FIC decisions: words after the MSC's
     // pinned host staging of the front end's per-pass copies (frame descriptors in,
     // startIndex / FreqCorr out): DMA without the pageable bounce, each pass syncs
     // before the buffers are touched again
-    dabgpu_frame *h_frames = nullptr;
-    int32_t *h_si = nullptr;
-    float2 *h_fc = nullptr;
-    int16_t *h_snr = nullptr;
+    PinBuf<dabgpu_frame> h_frames;
+    PinBuf<int32_t> h_si;
+    PinBuf<float2> h_fc;
+    PinBuf<int16_t> h_snr;
     // the back-end streams' own error words (the front end's is the context's): the
     // Viterbi jobs of run r set berr_d[r & 1], which the back end publishes into
     // h_berr[r & 1] (and clears) as its last step; read once back[r & 1].ev_back completed
-    int32_t *berr_d = nullptr, *h_berr = nullptr;
+    DevBuf<int32_t> berr_d;
+    PinBuf<int32_t> h_berr;
     // speculative back end (dabgpu_pipe_run): queued behind the first front pass
     bool speculate = true;                      // env DABGPU_NO_SPECULATE=1: off (A/B)
-    hipEvent_t ev_front = nullptr;
+    Event ev_front;
     bool ev_front_demod = false;     // ev_front marks this pass's demod (the speculative back end's gate)
     std::vector<dabgpu_frame> last_frames;   // [S][F]
     std::vector<dabgpu_frame_info> last_info;   // [S][F] observables of the last run
@@ -124,21 +128,28 @@ struct dabgpu_pipe {
     int32_t last_msc_stride = 0;
     bool last_msc_packed = false;
     // the iqBuffer feed (dabgpu_pipe_set_display): symbol 2's display carriers per ring slot
-    float2 *disp_d = nullptr;        // [S][R][K]
+    DevBuf<float2> disp_d;           // [S][R][K]
     bool display = false;
     int disp_token = 2;              // the display feed's symbol (ofdm-decoder.cpp:61 displayToken)
     bool packed = false;             // MSC output 8 bits per byte (dabgpu_pipe_set_packed)
     bool fic_packed = false;         // FIC output as FIB bytes (DABGPU_PACK_FIC)
     int iq_fmt = DABGPU_IQ_F32;      // sample format of the streams (dabgpu_pipe_set_iq_format)
-    AcqBg acq;
     // fault injection (DABGPU_CTL_INJECT_BOUNDS): the next run's MSC job gets a subchannel
     // table whose first entry points past the ring, which the Viterbi loader refuses
     bool inject_bounds = false;
-    int32_t *substart_bad_d = nullptr;
+    DevBuf<int32_t> substart_bad_d;
     // optional per-stage kernel timing (HIP events on the stage's stream)
     int profiling = 0;                          // 1: last run, 2: every run since enabled, 3: 2 + stages alone
-    std::vector<hipEvent_t> ev_pool;
+    std::vector<Event> ev_pool;
     std::vector<std::pair<int, int>> ev_rec;   // (stage, index of start event; end = +1)
+    // the streams (of the back ends and the background null search) after every buffer above
+    BackSlot back[2];
+    AcqBg acq;
+    ~dabgpu_pipe() {                 // the front end's stream is the context's: wait for it here
+        if (c) (void)c->stream.sync();
+        for (BackSlot &b : back) (void)b.stream.sync();
+        (void)acq.stream.sync();     // a background null search still running
+    }
 };
 
 static hipError_t prof_mark(dabgpu_pipe *p, int stage, bool start) {
@@ -151,16 +162,16 @@ static hipError_t prof_mark(dabgpu_pipe *p, int stage, bool start) {
     if (start) {
         size_t need = 2 * (p->ev_rec.size() + 1);
         while (p->ev_pool.size() < need) {
-            hipEvent_t e;
-            hipError_t r = hipEventCreate(&e);
+            Event e;
+            hipError_t r = e.create(hipEventDefault);
             if (r != hipSuccess) return r;
-            p->ev_pool.push_back(e);
+            p->ev_pool.push_back(std::move(e));
         }
         int idx = (int)(2 * p->ev_rec.size());
         p->ev_rec.push_back({stage, idx});
-        return hipEventRecord(p->ev_pool[idx], st);
+        return p->ev_pool[idx].record(st);
     }
-    hipError_t r = hipEventRecord(p->ev_pool[p->ev_rec.back().second + 1], st);
+    hipError_t r = p->ev_pool[p->ev_rec.back().second + 1].record(st);
     if (r == hipSuccess && p->profiling == 3) r = hipDeviceSynchronize();
     return r;
 }
@@ -170,9 +181,9 @@ static hipError_t prof_mark(dabgpu_pipe *p, int stage, bool start) {
 // query -- and reported once
 static int back_errors(dabgpu_pipe *p, bool wait) {
     for (int par = 0; par < 2; par++) {
-        if (!p->back[par].back_rec) continue;
+        if (!p->back[par].ev_back.recorded()) continue;
         if (!wait) {
-            const hipError_t q = hipEventQuery(p->back[par].ev_back);
+            const hipError_t q = p->back[par].ev_back.query();
             if (q == hipErrorNotReady) continue;
             if (q != hipSuccess) return fail(DABGPU_E_HIP, "back-end stream %d: %s", par, hipGetErrorString(q));
         }
@@ -188,9 +199,14 @@ static int back_errors(dabgpu_pipe *p, bool wait) {
 
 // wait for everything the pipeline has enqueued on its front-end and back-end streams
 static int sync_streams(dabgpu_pipe *p) {
-    HIPCHK(hipStreamSynchronize(p->c->stream));
-    for (BackSlot &b : p->back) HIPCHK(hipStreamSynchronize(b.stream));
+    HIPCHK(p->c->stream.sync());
+    for (BackSlot &b : p->back) HIPCHK(b.stream.sync());
     return 0;
+}
+
+// the streams a control call names: [first, end) -- one stream, or every stream for -1
+static std::pair<int, int> stream_range(const dabgpu_pipe *p, int stream) {
+    return stream < 0 ? std::make_pair(0, p->S) : std::make_pair(stream, stream + 1);
 }
 
 extern "C" {
@@ -200,12 +216,12 @@ static int acq_async_setup(dabgpu_pipe *p) {
     if (p->acq.stream) return 0;
     int lo = 0, hi = 0;
     HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    HIPCHK(hipStreamCreateWithPriority(&p->acq.stream, hipStreamNonBlocking, lo));
-    HIPCHK(hipEventCreateWithFlags(&p->acq.ev, hipEventDisableTiming));
-    HIPCHK(hipMalloc((void **)&p->acq.jobs_d, sizeof(AcqJob) * p->S));
-    HIPCHK(hipMalloc((void **)&p->acq.res_d, sizeof(AcqResult) * p->S));
-    HIPCHK(hipHostMalloc((void **)&p->acq.h_res, sizeof(AcqResult) * p->S, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void **)&p->acq.h_jobs, sizeof(AcqJob) * p->S, hipHostMallocDefault));
+    HIPCHK(p->acq.stream.create(lo));
+    HIPCHK(p->acq.ev.create(hipEventDisableTiming));
+    HIPCHK(p->acq.jobs_d.alloc(p->S));
+    HIPCHK(p->acq.res_d.alloc(p->S));
+    HIPCHK(p->acq.h_res.alloc(p->S));
+    HIPCHK(p->acq.h_jobs.alloc(p->S));
     p->acq.acquiring.assign(p->S, 0);
     return 0;
 }
@@ -307,24 +323,21 @@ static int rebuild_tables(dabgpu_pipe *p) {
             p->dp.max_rs = std::max(p->dp.max_rs, p->tab[s][k].bitRate / 8);
         }
     }
-    for (void **x : {(void **)&p->prof_d, (void **)&p->inv_d, (void **)&p->substart_d, (void **)&p->ent_prof_d,
-                     (void **)&p->ent_start_d, (void **)&p->ent_since_d, (void **)&p->act_d, (void **)&p->substart_bad_d}) {
-        if (*x) HIPCHK(hipFree(*x));
-        *x = nullptr;
-    }
-    auto up = [&](void **dst, const void *src, size_t bytes) -> int {
-        HIPCHK(hipMalloc(dst, std::max<size_t>(bytes, 256)));
-        HIPCHK(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-        return 0;
-    };
-    if (int rc = up((void **)&p->prof_d, profs.data(), sizeof(Profile) * profs.size())) return rc;
-    if (int rc = up((void **)&p->inv_d, inv.data(), inv.size())) return rc;
-    if (int rc = up((void **)&p->substart_d, ss.data(), sizeof(int32_t) * ss.size())) return rc;
+    // put() replaces a table; the per-entry tables of a non-uniform set and the injected
+    // table go (an empty buffer is assigned) and are built again when needed
+    HIPCHK(p->prof_d.put(profs));
+    HIPCHK(p->inv_d.put(inv));
+    HIPCHK(p->substart_d.put(ss));
+    p->ent_prof_d = {};
+    p->ent_start_d = {};
+    p->ent_since_d = {};
+    p->act_d = {};
+    p->substart_bad_d = {};
     if (!p->uniform) {
-        if (int rc = up((void **)&p->ent_prof_d, eprof.data(), sizeof(int32_t) * eprof.size())) return rc;
-        if (int rc = up((void **)&p->ent_start_d, estart.data(), sizeof(int32_t) * estart.size())) return rc;
-        if (int rc = up((void **)&p->ent_since_d, esince.data(), sizeof(int64_t) * esince.size())) return rc;
-        if (int rc = up((void **)&p->act_d, act.data(), sizeof(int32_t) * act.size())) return rc;
+        HIPCHK(p->ent_prof_d.put(eprof));
+        HIPCHK(p->ent_start_d.put(estart));
+        HIPCHK(p->ent_since_d.put(esince));
+        HIPCHK(p->act_d.put(act));
     }
     if (p->NDP) {
         HIPCHK(hipMemcpy(p->dp.sub_d, dps.data(), sizeof(int32_t) * nd, hipMemcpyHostToDevice));
@@ -357,7 +370,7 @@ int dabgpu_pipe_create_caps(dabgpu_ctx *c, const dabgpu_pipe_cfg *cfg, const dab
     if (cfg->freq_sync_method < 0 || cfg->freq_sync_method > 2)
         return fail(DABGPU_E_UNSUP, "freqSyncMethod %d (0, 1 or 2: ofdm-decoder.cpp:103-161)", cfg->freq_sync_method);
     if (int rc = check_table(cfg->subch, cfg->n_subch, caps->max_subch, caps->max_bitrate, caps->max_dabplus)) return rc;
-    auto *p = new dabgpu_pipe();
+    auto p = std::make_unique<dabgpu_pipe>();
     p->c = c;
     p->S = cfg->n_streams;
     p->F = cfg->n_frames;
@@ -371,109 +384,63 @@ int dabgpu_pipe_create_caps(dabgpu_ctx *c, const dabgpu_pipe_cfg *cfg, const dab
     p->since.assign(p->S, std::vector<int64_t>(cfg->n_subch, 0));
     p->st.assign(p->S, StreamSt());
     p->max_nbits = std::max(768, 24 * p->max_bitrate);
-    const size_t SF = (size_t)p->S * p->F;
-    int rc = 0;
-    auto A = [&](void **ptr, size_t bytes) {
-        if (rc) return;
-        if (hipMalloc(ptr, std::max<size_t>(bytes, 256)) != hipSuccess) rc = fail(DABGPU_E_NOMEM, "pipe alloc %zu", bytes);
-    };
-    A((void **)&p->ring, (size_t)p->S * p->R * FRAME_SOFT);
-    A((void **)&p->frames_d, sizeof(dabgpu_frame) * SF);
-    A((void **)&p->si_d, sizeof(int32_t) * SF);
-    A((void **)&p->corr_d, sizeof(int16_t) * SF);
-    A((void **)&p->snr_d, sizeof(int16_t) * SF);
-    A((void **)&p->fc_d, sizeof(float2) * SF);
-    A((void **)&p->fcpart_d, sizeof(float2) * SF * kMaxChunks);
-    p->desc_sz = (12 * (size_t)p->S + 4 * (size_t)SF + 15) / 16 * 16;
-    if (!rc && (hipHostMalloc((void **)&p->h_frames, sizeof(dabgpu_frame) * SF, hipHostMallocDefault) != hipSuccess ||
-                hipHostMalloc((void **)&p->h_si, sizeof(int32_t) * SF, hipHostMallocDefault) != hipSuccess ||
-                hipHostMalloc((void **)&p->h_fc, sizeof(float2) * SF, hipHostMallocDefault) != hipSuccess ||
-                hipHostMalloc((void **)&p->h_snr, sizeof(int16_t) * SF, hipHostMallocDefault) != hipSuccess ||
-                hipHostMalloc((void **)&p->h_desc, 2 * p->desc_sz, hipHostMallocDefault) != hipSuccess ||
-                hipHostMalloc((void **)&p->h_berr, sizeof(int32_t) * 2, hipHostMallocDefault) != hipSuccess))
-        rc = fail(DABGPU_E_NOMEM, "pipe pinned staging");
-    A((void **)&p->berr_d, sizeof(int32_t) * 2);
-    if (!rc && (hipMemset(p->berr_d, 0, sizeof(int32_t) * 2) != hipSuccess)) rc = fail(DABGPU_E_HIP, "pipe error words");
-    if (!rc) p->h_berr[0] = p->h_berr[1] = 0;
     if (const char *e = getenv("DABGPU_NO_SPECULATE")) p->speculate = !(e[0] == '1');
-    A((void **)&p->desc_d, 2 * p->desc_sz);
+    const size_t SF = (size_t)p->S * p->F;
+    const size_t ring_bytes = (size_t)p->S * p->R * FRAME_SOFT;
+    HIPCHK(p->ring.alloc(ring_bytes));
+    HIPCHK(hipMemset(p->ring, RING8_BIAS, ring_bytes));
+    HIPCHK(p->frames_d.alloc(SF));
+    HIPCHK(p->si_d.alloc(SF));
+    HIPCHK(p->corr_d.alloc(SF));
+    HIPCHK(p->snr_d.alloc(SF));
+    HIPCHK(p->fc_d.alloc(2 * SF));
+    HIPCHK(p->fcpart_d.alloc(2 * SF * kMaxChunks));
+    HIPCHK(p->h_frames.alloc(SF));
+    HIPCHK(p->h_si.alloc(SF));
+    HIPCHK(p->h_fc.alloc(SF));
+    HIPCHK(p->h_snr.alloc(SF));
+    p->desc_sz = (12 * (size_t)p->S + 4 * (size_t)SF + 15) / 16 * 16;
+    HIPCHK(p->desc_d.alloc(2 * p->desc_sz));
+    HIPCHK(p->h_desc.alloc(2 * p->desc_sz));
+    HIPCHK(p->berr_d.alloc(2));
+    HIPCHK(hipMemset(p->berr_d, 0, sizeof(int32_t) * 2));
+    HIPCHK(p->h_berr.alloc(2));
+    p->h_berr[0] = p->h_berr[1] = 0;
+    HIPCHK(p->ficprof_d.put({fic_profile()}));
     // MSC decisions, then the FIC's (both jobs of one run decode in one launch)
     const int64_t msc_words = p->NSUB > 0 ? dec_bytes(SF * 4 * p->NSUB, p->max_nbits) / 4 : 0;
     p->dec_fic_off = msc_words;
-    const size_t dec_sz = (size_t)(4 * msc_words + dec_bytes(SF * 4, 768));
-    A((void **)&p->ficprof_d, sizeof(Profile));
+    const size_t dec_words = (size_t)(msc_words + dec_bytes(SF * 4, 768) / 4);
     int prio_least = 0, prio_greatest = 0;
-    if (!rc && hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) rc = fail(DABGPU_E_HIP, "priority range");
+    HIPCHK(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
     for (BackSlot &b : p->back) {
-        A((void **)&b.dec, dec_sz);
-        if (!rc && (hipStreamCreateWithPriority(&b.stream, hipStreamNonBlocking, prio_least) != hipSuccess ||
-                    hipEventCreateWithFlags(&b.ev_copy, hipEventDisableTiming) != hipSuccess ||
-                    hipEventCreateWithFlags(&b.ev_back, hipEventDisableTiming) != hipSuccess ||
-                    hipEventCreateWithFlags(&b.ev_acs, hipEventDisableTiming) != hipSuccess))
-            rc = fail(DABGPU_E_HIP, "pipe stream/event create failed");
+        HIPCHK(b.dec.alloc(dec_words));
+        HIPCHK(b.stream.create(prio_least));
+        for (Event *e : {&b.ev_copy, &b.ev_back, &b.ev_acs}) HIPCHK(e->create(hipEventDisableTiming));
     }
-    if (!rc && (hipEventCreateWithFlags(&p->dp.ev, hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&p->ev_front, hipEventDisableTiming) != hipSuccess))
-        rc = fail(DABGPU_E_HIP, "pipe stream/event create failed");
-    if (!rc) {
-        const Profile fp = fic_profile();
-        if (hipMemcpy(p->ficprof_d, &fp, sizeof fp, hipMemcpyHostToDevice) != hipSuccess)
-            rc = fail(DABGPU_E_HIP, "pipe FIC profile upload failed");
-    }
+    HIPCHK(p->dp.ev.create(hipEventDisableTiming));
+    HIPCHK(p->ev_front.create(hipEventDisableTiming));
     if (p->NDP) {
         const size_t nd = (size_t)p->S * p->NDP;
-        A((void **)&p->dp.sub_d, sizeof(int32_t) * nd);
-        A((void **)&p->dp.br_d, sizeof(int16_t) * nd);
-        A((void **)&p->dp.since_d, sizeof(int64_t) * nd);
-        A((void **)&p->dp.ring_d, nd * 120 * DP_MAX_RS);
-        A((void **)&p->dp.state_d, sizeof(DpState) * nd);
-        A((void **)&p->dp.code_d, nd * 4 * p->F);
-        if (!rc && (hipMemset(p->dp.ring_d, 0, nd * 120 * DP_MAX_RS) != hipSuccess ||
-                    hipMemset(p->dp.state_d, 0, sizeof(DpState) * nd) != hipSuccess))
-            rc = fail(DABGPU_E_HIP, "pipe DAB+ init failed");
+        HIPCHK(p->dp.sub_d.alloc(nd));
+        HIPCHK(p->dp.br_d.alloc(nd));
+        HIPCHK(p->dp.since_d.alloc(nd));
+        HIPCHK(p->dp.ring_d.alloc(nd * 120 * DP_MAX_RS));
+        HIPCHK(p->dp.state_d.alloc(nd));
+        HIPCHK(p->dp.code_d.alloc(nd * 4 * p->F));
+        HIPCHK(hipMemset(p->dp.ring_d, 0, nd * 120 * DP_MAX_RS));
+        HIPCHK(hipMemset(p->dp.state_d, 0, sizeof(DpState) * nd));
     }
-    if (!rc) rc = rebuild_tables(p);
-    if (!rc && hipMemset(p->ring, RING8_BIAS, (size_t)p->S * p->R * FRAME_SOFT) != hipSuccess)
-        rc = fail(DABGPU_E_HIP, "pipe init copy failed");
+    if (int rc = rebuild_tables(p.get())) return rc;
     // the default re-acquisition mode: a stream that loses sync is searched in the
     // background (DABGPU_CTL_ACQ_ASYNC; DABGPU_CTL_ACQ_SYNC restores the in-run search)
-    if (!rc && !(rc = acq_async_setup(p))) p->acq.async = true;
-    if (rc) {
-        dabgpu_pipe_destroy(p);
-        return rc;
-    }
-    *out = p;
+    if (int rc = acq_async_setup(p.get())) return rc;
+    p->acq.async = true;
+    *out = p.release();
     return 0;
 }
 
 int dabgpu_pipe_destroy(dabgpu_pipe *p) {
-    if (!p) return 0;
-    (void)hipStreamSynchronize(p->c->stream);
-    for (BackSlot &b : p->back) if (b.stream) (void)hipStreamSynchronize(b.stream);
-    for (auto e : p->ev_pool) (void)hipEventDestroy(e);
-    for (BackSlot &b : p->back) {
-        for (hipEvent_t e : {b.ev_copy, b.ev_back, b.ev_acs}) if (e) (void)hipEventDestroy(e);
-        if (b.stream) (void)hipStreamDestroy(b.stream);
-        if (b.dec) (void)hipFree(b.dec);
-    }
-    AcqBg &a = p->acq;
-    if (a.stream) {                                 // a background null search still running
-        (void)hipStreamSynchronize(a.stream);
-        (void)hipStreamDestroy(a.stream);
-    }
-    const DabPlus &dp = p->dp;
-    for (hipEvent_t e : {p->ev_front, dp.ev, a.ev}) if (e) (void)hipEventDestroy(e);
-    for (void *h : {(void *)a.h_res, (void *)a.h_jobs, (void *)p->h_frames, (void *)p->h_si, (void *)p->h_fc,
-                    (void *)p->h_snr, (void *)p->h_desc, (void *)p->h_berr})
-        if (h) (void)hipHostFree(h);
-    for (void *x : {(void *)a.jobs_d, (void *)a.res_d, (void *)dp.sf_sparse_d, (void *)dp.sub_d, (void *)dp.br_d,
-                    (void *)dp.since_d, (void *)dp.ring_d, (void *)dp.state_d, (void *)dp.code_d,
-                    (void *)p->ficprof_d, (void *)p->ring, (void *)p->prof_d, (void *)p->inv_d, (void *)p->substart_d,
-                    (void *)p->frames_d, (void *)p->si_d, (void *)p->corr_d, (void *)p->snr_d, (void *)p->fc_d,
-                    (void *)p->fcpart_d, (void *)p->desc_d, (void *)p->berr_d, (void *)p->disp_d,
-                    (void *)p->substart_bad_d, (void *)p->ent_prof_d, (void *)p->ent_start_d, (void *)p->ent_since_d,
-                    (void *)p->act_d})
-        if (x) (void)hipFree(x);
     delete p;
     return 0;
 }
@@ -519,7 +486,7 @@ static int acquire_streams_async(dabgpu_pipe *p, const void *iq, int64_t stride,
     HIPCHK(hipMemcpyAsync(p->acq.jobs_d, p->acq.h_jobs, sizeof(AcqJob) * n, hipMemcpyHostToDevice, p->acq.stream));
     HIPCHK(launch_acquire(p->acq.stream, iq, p->iq_fmt, p->acq.jobs_d, (int)n, p->c->osc, p->acq.res_d));
     HIPCHK(hipMemcpyAsync(p->acq.h_res, p->acq.res_d, sizeof(AcqResult) * n, hipMemcpyDeviceToHost, p->acq.stream));
-    HIPCHK(hipEventRecord(p->acq.ev, p->acq.stream));
+    HIPCHK(p->acq.ev.record(p->acq.stream));
     p->acq.who = who;
     for (int s : who) p->acq.acquiring[s] = 1;
     p->acq.inflight = true;
@@ -527,7 +494,7 @@ static int acquire_streams_async(dabgpu_pipe *p, const void *iq, int64_t stride,
 }
 static int acq_collect(dabgpu_pipe *p, bool wait) {
     if (!p->acq.inflight) return 0;
-    const hipError_t q = wait ? hipEventSynchronize(p->acq.ev) : hipEventQuery(p->acq.ev);
+    const hipError_t q = wait ? p->acq.ev.sync() : p->acq.ev.query();
     if (q == hipErrorNotReady) return 0;
     if (q != hipSuccess) return fail(DABGPU_E_HIP, "background null search: %s", hipGetErrorString(q));
     for (size_t i = 0; i < p->acq.who.size(); i++) {
@@ -559,51 +526,57 @@ extern "C" int dabgpu_pipe_acquire(dabgpu_pipe *p, const void *iq, int64_t strid
 // windows (startIndex = last one) and correctors (unchanged), run the batched kernels on
 // the prediction, then replay ofdmProcessor::run's sequential logic with the measured
 // values and commit the longest correctly predicted prefix of each stream.  All of that
-// logic is front_replay.h's; here are the staging, the launches and the error checks.
-// P is the caller's: after_launch (the speculative back end) reads the prediction.
-static int pipe_front_pass(dabgpu_pipe *p, const void *iq, int64_t stride, const int64_t *n_avail,
-                           std::vector<int> &done, std::vector<StreamSt> &cur, front::Pass &P, bool &progress,
-                           bool &lost, const std::function<int()> &after_launch = nullptr) {
+// logic is front_replay.h's; here are the staging, the launches and the error checks, in
+// two halves: front_launch predicts and makes the pass's first launches, front_finish
+// waits for them and does the rest.  Between the two dabgpu_pipe_run queues the speculative
+// back end, which reads the prediction in P (the caller's).
+
+// the pipeline's demod, on either path
+static DemodAux pipe_demod_aux(const dabgpu_pipe *p) {
+    DemodAux aux{};
+    aux.disp = p->display ? p->disp_d.ptr : nullptr;
+    aux.disp_token = p->disp_token;
+    aux.ring8 = 1;
+    aux.fmt = p->iq_fmt;
+    return aux;
+}
+
+// gate: record ev_front behind the demod, for a speculative back end queued after this call
+static int front_launch(dabgpu_pipe *p, const void *iq, int64_t stride, const int64_t *n_avail,
+                        const std::vector<int> &done, const std::vector<StreamSt> &cur, front::Pass &P, bool gate) {
     dabgpu_ctx *c = p->c;
     front::predict(P, cur, done, p->F, p->R, stride, n_avail);
     const int n = P.n();
-    progress = false;
     if (n == 0) return 0;
     // Steady state (no stream runs the coarse AFC of processBlock_0): ONE launch per
     // pass -- every predicted frame's workgroup runs findIndex on its window, places
     // the frame at the startIndex it finds, reports get_snr of block 0 and demodulates
     // the 75 symbols (k_demod_wg<.., SYNC>); one host round trip per pass.  Frames the
-    // replay below does not commit are re-predicted and decoded again.  While a
+    // replay does not commit are re-predicted and decoded again.  While a
     // stream's coarse AFC is pending the host needs startIndex and processBlock_0's
     // correction first: findIndex, block 0 and the demod run as three launches.
-    const bool fast = P.fast;
     memcpy(p->h_frames, P.fr.data(), sizeof(dabgpu_frame) * n);
     HIPCHK(hipMemcpyAsync(p->frames_d, p->h_frames, sizeof(dabgpu_frame) * n, hipMemcpyHostToDevice, c->stream));
-    DemodAux aux{};                                 // the pipeline's demod, either way
-    aux.disp = p->display ? p->disp_d : nullptr;
-    aux.disp_token = p->disp_token;
-    aux.ring8 = 1;
-    aux.fmt = p->iq_fmt;
-    if (fast) {
-        DemodAux sync = aux;
+    if (P.fast) {
+        DemodAux sync = pipe_demod_aux(p);
         sync.si = p->si_d;
         sync.snr = p->snr_d;
         sync.level = p->threshold;
         HIPCHK(prof_mark(p, DABGPU_STAGE_DEMOD, true));
         const int kChunks = demod_chunks(n, 2);
-        HIPCHK(launch_demod(c->stream, iq, p->frames_d, n, kChunks, c->T, (int16_t *)p->ring, nullptr, p->fcpart_d, P.general, sync));
+        HIPCHK(launch_demod(c->stream, iq, p->frames_d, n, kChunks, c->T, (int16_t *)p->ring.ptr, nullptr, p->fcpart_d, P.general, sync));
         HIPCHK(prof_mark(p, DABGPU_STAGE_DEMOD, false));
-        // the speculative back end (after_launch, queued below) waits for the demod only:
+        // the speculative back end waits for the demod only:
         // the publish feeds the host, not the decoders -- one kernel and its dispatch off
         // the ACS's critical path (profiles/r05_back_gate_ab.txt).  The publish is still
         // launched first, so the ACS's waves do not take the slot it needs before the host
         // can read the pass.
-        if (after_launch) {
-            HIPCHK(hipEventRecord(p->ev_front, c->stream));
+        if (gate) {
+            HIPCHK(p->ev_front.record(c->stream));
             p->ev_front_demod = true;
         }
         // the host's values and the error word straight into pinned memory (no copies)
-        HIPCHK(launch_front_publish(c->stream, p->fcpart_d, kChunks, n, (float *)p->fc_d, (float *)p->h_fc, p->si_d,
+        HIPCHK(launch_front_publish(c->stream, p->fcpart_d, kChunks, n, p->fc_d, (float *)p->h_fc.ptr, p->si_d,
                                     p->h_si, p->snr_d, p->h_snr, c->err, c->h_err));
     } else {
         HIPCHK(prof_mark(p, DABGPU_STAGE_PRS, true));
@@ -611,14 +584,20 @@ static int pipe_front_pass(dabgpu_pipe *p, const void *iq, int64_t stride, const
         HIPCHK(prof_mark(p, DABGPU_STAGE_PRS, false));
         HIPCHK(hipMemcpyAsync(p->h_si, p->si_d, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
     }
-    if (after_launch)
-        if (int rc = after_launch()) return rc;
+    return 0;
+}
+
+static int front_finish(dabgpu_pipe *p, const void *iq, const int64_t *n_avail, std::vector<int> &done,
+                        std::vector<StreamSt> &cur, front::Pass &P, bool &progress, bool &lost) {
+    dabgpu_ctx *c = p->c;
+    const int n = P.n();
+    const bool fast = P.fast;
+    progress = false;
+    if (n == 0) return 0;
     if (fast) {
         HIPCHK(hipStreamSynchronize(c->stream));
-        if (const int32_t e = *(volatile int32_t *)c->h_err)
-            return fail(DABGPU_E_BOUNDS, "kernel refused out-of-bounds work:%s%s", (e & KERR_FRAME) ? " frame descriptor" : "",
-                        (e & KERR_VITERBI) ? " viterbi source" : "");
-        for (int i = 0; i < n; i++) {                           // demodulated and measured above
+        if (const int32_t e = *(volatile int32_t *)c->h_err.ptr) return bounds_error(e);
+        for (int i = 0; i < n; i++) {                           // demodulated and measured by front_launch
             P.e[i].fc = front::FreqCorr{p->h_fc[i].x, p->h_fc[i].y};
             P.e[i].snr = p->h_snr[i];
         }
@@ -651,7 +630,8 @@ static int pipe_front_pass(dabgpu_pipe *p, const void *iq, int64_t stride, const
         HIPCHK(hipMemcpyAsync(p->frames_d, sel.data(), sizeof(dabgpu_frame) * n3, hipMemcpyHostToDevice, c->stream));
         HIPCHK(prof_mark(p, DABGPU_STAGE_DEMOD, true));
         const int kChunks = demod_chunks(n3);
-        HIPCHK(launch_demod(c->stream, iq, p->frames_d, n3, kChunks, c->T, (int16_t *)p->ring, nullptr, p->fcpart_d, P.general, aux));
+        HIPCHK(launch_demod(c->stream, iq, p->frames_d, n3, kChunks, c->T, (int16_t *)p->ring.ptr, nullptr, p->fcpart_d, P.general,
+                            pipe_demod_aux(p)));
         HIPCHK(prof_mark(p, DABGPU_STAGE_DEMOD, false));
         HIPCHK(launch_fc_reduce(c->stream, p->fcpart_d, kChunks, n3, p->fc_d));
         HIPCHK(hipMemcpyAsync(fc.data(), p->fc_d, sizeof(float2) * n3, hipMemcpyDeviceToHost, c->stream));
@@ -680,7 +660,7 @@ static VitJob ring_job(const dabgpu_pipe *p, int par, int32_t kind, int n_cw, in
     memset(&J, 0, sizeof J);
     J.kind = kind;
     J.n_cw = n_cw;
-    J.src = (const int16_t *)p->ring;
+    J.src = (const int16_t *)p->ring.ptr;
     J.ring8 = 1;
     J.src_len = (int64_t)p->S * p->R * FRAME_SOFT;
     J.err = p->berr_d + par;
@@ -738,7 +718,7 @@ static int enqueue_back(dabgpu_pipe *p, int par, const RunOut &o, const std::vec
     const bool fic = o.fic_bits != nullptr, msc = o.do_msc;
     // per stream: CIF index of its first CIF slot and the CIFs it delivered (the
     // staging half is reused only once its previous uploads have executed)
-    if (b.copy_rec) HIPCHK(hipEventSynchronize(b.ev_copy));
+    HIPCHK(b.ev_copy.sync());
     for (int s = 0; s < S; s++) {
         p->h_cif0(par)[s] = p->st[s].cif_count;
         p->h_ncif(par)[s] = 4 * dn[s];
@@ -747,8 +727,7 @@ static int enqueue_back(dabgpu_pipe *p, int par, const RunOut &o, const std::vec
     // one upload of the block (the FIC slots only when the FIC is decoded)
     HIPCHK(hipMemcpyAsync(p->cif0_dev(par), p->h_cif0(par), 12 * (size_t)S + (fic ? 4 * (size_t)S * F : 0),
                           hipMemcpyHostToDevice, bs));
-    HIPCHK(hipEventRecord(b.ev_copy, bs));
-    b.copy_rec = true;
+    HIPCHK(b.ev_copy.record(bs));
     // the small upload above runs on the back-end stream while the front end still
     // works; only the decoders wait for it.
     // What the back end may read of the front end's output: the soft-bit ring (p->ring,
@@ -757,9 +736,9 @@ static int enqueue_back(dabgpu_pipe *p, int par, const RunOut &o, const std::vec
     // the demod alone (ev_front_demod), before the publish.  A back-end reader of those
     // must wait for an event recorded after the publish.  (Measured: launching run r's traceback beside
     // run r+1's ACS instead of beside run r+1's demod is 2 % slower -- the ACS loses more than the demod gains.)
-    if (!p->ev_front_demod) HIPCHK(hipEventRecord(p->ev_front, c->stream));
+    if (!p->ev_front_demod) HIPCHK(p->ev_front.record(c->stream));
     p->ev_front_demod = false;
-    HIPCHK(hipStreamWaitEvent(bs, p->ev_front, 0));
+    HIPCHK(p->ev_front.wait_on(bs));
     if (!fic && !msc) return 0;
     // ACS (joint, FIC only or MSC only) -> ev_acs -> traceback -> FIB CRCs.  Stage times:
     // the MSC's stages take the joint kernels; the FIC stage is the FIB CRCs beside an MSC,
@@ -769,8 +748,7 @@ static int enqueue_back(dabgpu_pipe *p, int par, const RunOut &o, const std::vec
     HIPCHK(prof_mark(p, msc ? DABGPU_STAGE_MSC_ACS : DABGPU_STAGE_FIC, true));
     HIPCHK(fic && msc ? launch_acs_msc_fic(bs, JM, JF) : launch_acs(bs, msc ? JM : JF));
     if (msc) HIPCHK(prof_mark(p, DABGPU_STAGE_MSC_ACS, false));
-    HIPCHK(hipEventRecord(b.ev_acs, bs));
-    b.acs_rec = true;
+    HIPCHK(b.ev_acs.record(bs));
     if (msc) HIPCHK(prof_mark(p, DABGPU_STAGE_MSC_TB, true));
     HIPCHK(fic && msc ? launch_traceback_msc_fic(bs, JM, JF) : launch_traceback(bs, msc ? JM : JF));
     if (msc) HIPCHK(prof_mark(p, DABGPU_STAGE_MSC_TB, false));
@@ -800,11 +778,17 @@ static int bail(dabgpu_pipe *p, int par, const Spec &sp, int rc) {
     if (sp.sent) {
         BackSlot &b = p->back[par];
         (void)launch_take_error(b.stream, p->berr_d + par, p->h_berr + par);
-        (void)hipEventRecord(b.ev_back, b.stream);
-        b.back_rec = true;
-        (void)hipStreamSynchronize(b.stream);
+        (void)b.ev_back.record(b.stream);
+        (void)b.stream.sync();
     }
     return rc;
+}
+// the back end's last step: publish (and clear) its error word, mark the run's back end done
+static int finish_back(dabgpu_pipe *p, int par) {
+    BackSlot &b = p->back[par];
+    HIPCHK(launch_take_error(b.stream, p->berr_d + par, p->h_berr + par));
+    HIPCHK(b.ev_back.record(b.stream));
+    return 0;
 }
 
 // Streams that need the null search: in the background (DABGPU_CTL_ACQ_ASYNC, the
@@ -870,7 +854,7 @@ int dabgpu_pipe_run(dabgpu_pipe *p, const void *iq, int64_t stride, const int64_
     // profiles/r04_front_gate_ab.txt)
     const int par = (int)(p->run_idx & 1);
     BackSlot &b = p->back[par];
-    if (b.acs_rec) HIPCHK(hipStreamWaitEvent(c->stream, b.ev_acs, 0));
+    HIPCHK(b.ev_acs.wait_on(c->stream));
     std::vector<int> done(S, 0);
     std::vector<StreamSt> cur = p->st;
     p->cur = par;
@@ -886,17 +870,17 @@ int dabgpu_pipe_run(dabgpu_pipe *p, const void *iq, int64_t stride, const int64_
         int found = 0;
         if (int rc = acquire_pending(p, iq, stride, n_avail, done, cur, found)) return bail(p, par, sp, rc);
         bool progress = false, lost = false;
-        std::function<int()> after;
-        if (sp.on && it == 0 && found == 0)
-            after = [&]() -> int {               // the frames this pass predicted whole, decoded behind it
-                front::predicted_whole(P, S, F, n_avail, sp.pred, sp.pred_slot);
-                sp.sent = true;
-                sp.rec0 = p->ev_rec.size();
-                const int rc = enqueue_back(p, par, out, sp.pred, sp.pred_slot);
-                sp.rec1 = p->ev_rec.size();
-                return rc;
-            };
-        if (int rc = pipe_front_pass(p, iq, stride, n_avail, done, cur, P, progress, lost, after)) return bail(p, par, sp, rc);
+        const bool spec = sp.on && it == 0 && found == 0;
+        if (int rc = front_launch(p, iq, stride, n_avail, done, cur, P, spec)) return bail(p, par, sp, rc);
+        if (spec && P.n()) {                     // the frames this pass predicted whole, decoded behind it
+            front::predicted_whole(P, S, F, n_avail, sp.pred, sp.pred_slot);
+            sp.sent = true;
+            sp.rec0 = p->ev_rec.size();
+            const int rc = enqueue_back(p, par, out, sp.pred, sp.pred_slot);
+            sp.rec1 = p->ev_rec.size();
+            if (rc) return bail(p, par, sp, rc);
+        }
+        if (int rc = front_finish(p, iq, n_avail, done, cur, P, progress, lost)) return bail(p, par, sp, rc);
         if (P.n()) passes++;                     // (a pass with nothing to predict launches nothing)
         if (!progress && !lost && !found) break;
     }
@@ -916,9 +900,7 @@ int dabgpu_pipe_run(dabgpu_pipe *p, const void *iq, int64_t stride, const int64_
         for (size_t i = sp.rec0; i < sp.rec1; i++) p->ev_rec[i].first = -1;
         if (int rc = enqueue_back(p, par, out, done, slot)) return bail(p, par, sp, rc);
     }
-    HIPCHK(launch_take_error(b.stream, p->berr_d + par, p->h_berr + par));
-    HIPCHK(hipEventRecord(b.ev_back, b.stream));
-    b.back_rec = true;
+    if (int rc = finish_back(p, par)) return bail(p, par, sp, rc);
     p->run_idx++;
     p->inject_bounds = false;
     p->last_msc = have_rows ? msc_bits : nullptr;
@@ -947,7 +929,7 @@ int dabgpu_pipe_timing(dabgpu_pipe *p, float *ms, int32_t *launches) {
     for (auto &r : p->ev_rec) {
         if (r.first < 0) continue;              // discarded (a missed speculation)
         float t = 0.0f;
-        HIPCHK(hipEventElapsedTime(&t, p->ev_pool[r.second], p->ev_pool[r.second + 1]));
+        HIPCHK(hipEventElapsedTime(&t, p->ev_pool[r.second].e, p->ev_pool[r.second + 1].e));
         ms[r.first] += t;
         if (launches) launches[r.first] += 1;
     }
@@ -994,15 +976,12 @@ int dabgpu_pipe_dabplus(dabgpu_pipe *p, uint8_t *sf_bytes, int32_t sf_stride, da
     if (p->dp.compact) {
         if (p->F > 512) return fail(DABGPU_E_UNSUP, "compact DAB+ output: at most 512 frames per run");
         const size_t need = (size_t)p->S * 4 * p->F * p->NDP * (size_t)sf_stride;
-        if (need > p->dp.sf_sparse_bytes) {
+        if (need > p->dp.sf_sparse_d.n) {
             // the layers that wrote the old scratch ran on this pipeline's back-end streams:
             // wait for those (not the whole device: other pipelines, the null search)
-            for (BackSlot &b : p->back) HIPCHK(hipStreamSynchronize(b.stream));
-            if (p->dp.sf_sparse_d) HIPCHK(hipFree(p->dp.sf_sparse_d));
-            p->dp.sf_sparse_d = nullptr;
-            p->dp.sf_sparse_bytes = 0;
-            HIPCHK(hipMalloc((void **)&p->dp.sf_sparse_d, need));
-            p->dp.sf_sparse_bytes = need;
+            for (BackSlot &b : p->back) HIPCHK(b.stream.sync());
+            p->dp.sf_sparse_d.reset();
+            HIPCHK(p->dp.sf_sparse_d.alloc(need));
         }
         J.sf_out = p->dp.sf_sparse_d;
         J.sf_compact = sf_bytes;
@@ -1013,12 +992,11 @@ int dabgpu_pipe_dabplus(dabgpu_pipe *p, uint8_t *sf_bytes, int32_t sf_stride, da
     // on the last run's back-end stream (after its MSC), after the previous
     // superframe pass (the 5-CIF rings carry state from run to run)
     hipStream_t bs = p->back[p->cur].stream;
-    if (p->dp.rec) HIPCHK(hipStreamWaitEvent(bs, p->dp.ev, 0));
+    HIPCHK(p->dp.ev.wait_on(bs));
     HIPCHK(prof_mark(p, DABGPU_STAGE_DABPLUS, true));
     HIPCHK(launch_dabplus(bs, J));
     HIPCHK(prof_mark(p, DABGPU_STAGE_DABPLUS, false));
-    HIPCHK(hipEventRecord(p->dp.ev, bs));
-    p->dp.rec = true;
+    HIPCHK(p->dp.ev.record(bs));
     // (the run after next does not wait for this: the layer reads this run's MSC output
     // and CIF counters, which that run's back end overwrites behind it on this stream)
     p->last_msc = nullptr;                     // each run's CIFs enter the superframe layer once
@@ -1075,8 +1053,7 @@ static int inject_table(dabgpu_pipe *p) {
                     first = false;
                 }
         }
-        HIPCHK(hipMalloc((void **)&p->substart_bad_d, sizeof(int32_t) * bad.size()));
-        HIPCHK(hipMemcpy(p->substart_bad_d, bad.data(), sizeof(int32_t) * bad.size(), hipMemcpyHostToDevice));
+        HIPCHK(p->substart_bad_d.put(bad));
     }
     return 0;
 }
@@ -1107,7 +1084,7 @@ int dabgpu_pipe_control(dabgpu_pipe *p, int stream, int op) {
     // completes and is applied first, so the control below is the last word (the reference
     // runs these methods between its own sequential steps)
     if (int rc = acq_collect(p, true)) return rc;
-    for (int s = (stream < 0 ? 0 : stream); s < (stream < 0 ? p->S : stream + 1); s++) {
+    for (auto [s, end] = stream_range(p, stream); s < end; s++) {
         StreamSt &x = p->st[s];
         switch (op) {
         case DABGPU_CTL_RESET: x.fine = 0; x.coarse = 0; x.f2 = true; break;      // ofdm-processor.cpp:476-479
@@ -1139,7 +1116,7 @@ int dabgpu_pipe_set_subch(dabgpu_pipe *p, int stream, const dabgpu_subch *sub, i
     // double-buffering them
     if (int rc = sync_streams(p)) return rc;
     const size_t RB = 120 * DP_MAX_RS;
-    for (int s = (stream < 0 ? 0 : stream); s < (stream < 0 ? p->S : stream + 1); s++) {
+    for (auto [s, end] = stream_range(p, stream); s < end; s++) {
         const std::vector<dabgpu_subch> old = p->tab[s];
         const std::vector<int64_t> old_since = p->since[s];
         std::vector<int> old_slot(old.size(), -1);      // DAB+ slot of each old entry
@@ -1246,7 +1223,7 @@ int dabgpu_pipe_set_display(dabgpu_pipe *p, int on) {
     if (!p) return fail(DABGPU_E_ARG, "bad args");
     if (on && !p->disp_d) {
         HIPCHK(hipStreamSynchronize(p->c->stream));
-        HIPCHK(hipMalloc((void **)&p->disp_d, sizeof(float2) * (size_t)p->S * p->R * K));
+        HIPCHK(p->disp_d.alloc((size_t)p->S * p->R * K));
         HIPCHK(hipMemset(p->disp_d, 0, sizeof(float2) * (size_t)p->S * p->R * K));
     }
     p->display = on != 0;

@@ -1003,3 +1003,65 @@ def test_dabplus_run_past_2048_cifs_equals_short_runs(ctx):
         assert ia["status"][c] == o["status"], c
         if o["status"] == 3:
             assert ia["n_corrected"][c] == o["n_corrected"] and np.array_equal(ba[c], o["out"][:110]), c
+
+
+def test_pipeline_lifetime_returns_device_memory(ctx):
+    """a pipeline gives back the device memory it took: seven create / use / close cycles
+    over every allocation the host layer makes lazily (the compact DAB+ scratch, the display
+    feed, the profiling events, the per-entry descriptor tables of a non-uniform set_subch,
+    the DABGPU_CTL_INJECT_BOUNDS table) on top of create's own.  Cycle 1 absorbs the
+    runtime's lazy allocations; free device memory (hipMemGetInfo) after cycle 7 against
+    after cycle 1 must stay under half of one pipeline's footprint -- six cycles that each
+    leaked a pipeline would lose six of them.  The runs must not fault, ctx.check() is clean"""
+    import ctypes as C
+    import dabamd
+    sub = [(0, 48, 64, 0o103, 0, 1), (48, 36, 48, 0o103, 0, 1), (84, 96, 128, 3, 1, 0)]
+    F = 2
+    iqs = _gen(sub, 2 * F + 1, [91, 92], 20.0)
+    S = len(iqs)
+    lens = [len(x) // 2 for x in iqs]
+    stride = max(lens)
+    buf = np.zeros((S, 2 * stride), np.float32)
+    for s, x in enumerate(iqs):
+        buf[s, :len(x)] = x
+    diq = ctx.put(buf)
+    subs = [dabamd.Subch(sc[0], sc[1], sc[2], sc[3], 0 if sc[4] else 1, dabamd.SUBCH_DABPLUS if sc[5] else 0)
+            for sc in sub]
+    hip = C.CDLL("libamdhip64.so")                  # the runtime the library already loaded
+
+    def free_bytes():
+        free, total = C.c_size_t(), C.c_size_t()
+        assert hip.hipMemGetInfo(C.byref(free), C.byref(total)) == 0
+        return free.value
+
+    def cycle():
+        """free device memory just before close()"""
+        pipe = dabamd.Pipeline(ctx, S, F, subs, max_subch=4, max_bitrate=128, max_dabplus=2)
+        try:
+            pipe.set_packed(True)
+            pipe.set_dabplus_compact(True)
+            pipe.set_display(True)
+            pipe.set_profiling(2)
+            for _ in range(2):
+                pipe.run(diq, stride, lens, download=False, partial=True)
+                pipe.dabplus(download=False)
+            pipe.set_subch(0, subs[:2])             # stream 0 differs: the non-uniform tables
+            pipe.sync()                             # raises on a fault or a refused kernel
+            pipe.control(dabamd.CTL_INJECT_BOUNDS)  # no run follows: only its table is allocated
+            ctx.check()
+            return free_bytes()
+        finally:
+            pipe.close()
+
+    try:
+        cycle()
+        f1 = free_bytes()
+        footprint = f1 - cycle()
+        for _ in range(5):
+            cycle()
+        f7 = free_bytes()
+    finally:
+        diq.free()
+    print("footprint", footprint, "bytes; drift f1 - f7", f1 - f7, "bytes")
+    assert footprint > 0
+    assert f1 - f7 < footprint / 2

@@ -2,9 +2,9 @@
 workload once, then times K steps of a fresh pipeline per configuration, configs
 interleaved over several repetitions (box-to-box variance is ~5 %, so A/B across
 gpurun calls is not reliable).  A configuration is a set of environment variables read
-at dabgpu_pipe_create (e.g. DABGPU_TB_DEFER, DABGPU_NO_SPECULATE).
+at dabgpu_pipe_create (e.g. DABGPU_NO_SPECULATE).
 
-  python tools/ab_pipe.py --configs "base:" "nodefer:DABGPU_TB_DEFER=0" [--reps 3 --steps 8]
+  python tools/ab_pipe.py --configs "base:" "nospec:DABGPU_NO_SPECULATE=1" [--reps 3 --steps 8]
 """
 import argparse
 import json
