@@ -63,11 +63,25 @@ typedef struct {
     int16_t bitRate;
     int16_t protLevel;
     int16_t uepFlag;
-    int16_t flags;          /* DABGPU_SUBCH_DABPLUS: feed the DAB+ superframe layer */
+    int16_t flags;          /* DABGPU_SUBCH_DABPLUS: feed the DAB+ superframe layer;
+                               DABGPU_SUBCH_MP2: feed the MPEG layer II layer */
 } dabgpu_subch;
 #define DABGPU_SUBCH_DABPLUS 1
 #define DABGPU_SUBCH_RAW     2   /* dabgpu_msc_deconvolve: no energy dispersal (the bare
                                     uep_/eep_deconvolve::deconvolve output) */
+#define DABGPU_SUBCH_MP2     4   /* feed the MPEG layer II layer (dabgpu_pipe_mp2); not together
+                                    with DABGPU_SUBCH_DABPLUS on one entry (DABGPU_E_ARG) */
+
+/* One CIF of one classic-audio subchannel through mp2Processor::addtoFrame
+ * (mp2processor.cpp:572-617) and, when a frame completed in it, mp2decodeFrame (:365-568). */
+typedef struct {
+    int32_t status;         /* -1 CIF not delivered or inside the entry's warm-up, 0 no frame completed
+                               in this CIF, 1 a frame completed and its header was rejected, 2 decoded */
+    int32_t sample_rate;    /* status >= 1: baudRate when the frame was handed over (48000 or 24000) */
+    int32_t frame_bytes;    /* status 2: mp2decodeFrame's return value */
+} dabgpu_mp2_info;
+/* a decoder's carried state (the last 15 V vectors of both channels), opaque */
+#define DABGPU_MP2_STATE_BYTES 3840
 
 /* One CIF of one DAB+ subchannel through mp4Processor::addtoFrame
  * (mp4processor.cpp:107-145) and, when five blocks are buffered and the fire
@@ -260,6 +274,30 @@ int dabgpu_rs_decode(dabgpu_ctx *ctx, const uint8_t *in_d, int n, uint8_t *out_d
 int dabgpu_msc_deconvolve(dabgpu_ctx *ctx, const int16_t *frag_d, int64_t frag_stride,
                           const dabgpu_subch *subch_h, int n_cw, uint8_t *bits_d, int64_t out_stride);
 
+/* mp2Processor::mp2decodeFrame batched (mp2processor.cpp:365-568; the counterpart of
+ * dabgpu_rs_decode): n_chains independent decoders, each taking chain_len frames in order.
+ *   frames_d  frame j of chain i at frames_d + (i*chain_len + j)*frame_stride; frame_stride
+ *             (>= 4) bytes are readable and the frame reads as zeros beyond them
+ *   state_d   DABGPU_MP2_STATE_BYTES per chain, opaque, all-zero for a new mp2Processor,
+ *             updated in place
+ *   pcm_d     int16 [n_chains][chain_len][1152][2] (left, right), pcm[(idx<<6)|(j<<1)|ch] per
+ *             block of 96 samples as the reference writes it; rows of frames that returned
+ *             0 are left untouched
+ *   ret_d     int32 [n_chains][chain_len]: mp2decodeFrame's return value, the frame size in
+ *             bytes, or 0 for a rejected header (such a frame writes no PCM and leaves the
+ *             state as it was: the frame after it continues from the one before it)
+ * The arithmetic is the reference's, integer from the first bit to the sample.  Three things
+ * the reference leaves to its compiler or to the contents of memory are fixed by rule:
+ *   1. V is int16: (sum + 8192) >> 14 is stored modulo 2^16 (what the reference's int16_t V
+ *      does with gcc; loud frames do wrap);
+ *   2. bits past the end of a frame read as 0 (the reference reads on into its frame buffer,
+ *      2*24*bitRate bytes it never initialises; the host mp2Processor zero-fills it);
+ *   3. products and sums are int32, two's complement (signed overflow is undefined in the
+ *      reference; for frames whose intermediates stay inside int32 nothing rests on this).
+ * Asynchronous on the context stream. */
+int dabgpu_mp2_decode(dabgpu_ctx *ctx, const uint8_t *frames_d, int64_t frame_stride, int n_chains, int chain_len,
+                      void *state_d, int16_t *pcm_d, int32_t *ret_d);
+
 /* ---- streaming pipeline (ofdmProcessor::run + ficHandler + mscHandler) ---
  * n_streams independent ensembles; each call decodes n_frames frames per
  * stream.  Sync, AFC, DQPSK references and the 16-CIF time de-interleaver
@@ -321,12 +359,14 @@ typedef struct {
     int32_t max_subch;     /* table entries per stream; the MSC output's row count */
     int32_t max_bitrate;   /* largest bitRate any entry may have (sizes decisions, msc_stride check) */
     int32_t max_dabplus;   /* DAB+ entries per stream; the DAB+ outputs' slot count */
-    int32_t reserved;
+    int32_t max_mp2;       /* layer II entries per stream; the dabgpu_pipe_mp2 outputs' slot count
+                              (0: no layer II state is allocated) */
 } dabgpu_pipe_caps;
 /* dabgpu_pipe_create with buffers sized by caps: cfg->subch[0..n_subch) is every stream's
  * initial table (n_subch = 0: a FIC-only pipeline until dabgpu_pipe_set_subch).
  * dabgpu_pipe_create is this call with the caps of its table (n_subch, its largest bitRate,
- * its number of DAB+ entries).  Output layouts with caps:
+ * its numbers of DAB+ and of layer II entries).  A pipeline with max_mp2 == 0 allocates and
+ * launches nothing for the layer II layer.  Output layouts with caps:
  *   msc_bits_d [n_streams][4*n_frames][max_subch][msc_stride]: entry k of a stream is row k;
  *              rows of absent or not-yet-valid entries are left untouched
  *   sf_bytes_d / info_d (and the compact form): max_dabplus in place of n_dabplus; DAB+
@@ -337,12 +377,14 @@ int dabgpu_pipe_create_caps(dabgpu_ctx *ctx, const dabgpu_pipe_cfg *cfg, const d
 /* Replace the table of one stream (stream = -1: of every stream) for the runs that follow.
  * Validates as create does: DABGPU_E_UNSUP for an undefined protection or a bad DAB+
  * bitRate, DABGPU_E_ARG for an entry outside its CUs, for n > max_subch, a bitRate above
- * max_bitrate or more DAB+ entries than max_dabplus; on any error the table is unchanged.
+ * max_bitrate, more DAB+ entries than max_dabplus, more layer II entries than max_mp2 or an
+ * entry flagged for both layers; on any error the table is unchanged.
  * Waits for everything the pipeline has enqueued (as dabgpu_pipe_set_profiling): call
- * dabgpu_pipe_dabplus for the last run before it.
- * An entry whose index and all six fields are unchanged keeps its since_cif and DAB+ state
- * and decodes without interruption.  Every other entry gets since_cif = the stream's
- * cif_count at the call, its DAB+ ring and state zeroed (a new mp4Processor), and delivers
+ * dabgpu_pipe_dabplus / dabgpu_pipe_mp2 for the last run before it.
+ * An entry whose index and all six fields are unchanged keeps its since_cif and its DAB+ or
+ * layer II state and decodes without interruption.  Every other entry gets since_cif = the
+ * stream's cif_count at the call, its DAB+ ring and state zeroed (a new mp4Processor) or its
+ * synchroniser and decoder zeroed (a new mp2Processor), and delivers
  * CIF c only when the stream delivered c and c >= since_cif + 16: all 16 source CIFs of
  * such a codeword lie at or after the switch, so the result equals a reference decoder
  * started at the switch.  Initial entries have since_cif 0. */
@@ -390,6 +432,21 @@ int dabgpu_pipe_run(dabgpu_pipe *p, const void *iq_d, int64_t stream_stride, con
  *              corrected superframe bytes where info.status == 3
  *   info_d     [n_streams][4*n_frames][n_dabplus] */
 int dabgpu_pipe_dabplus(dabgpu_pipe *p, uint8_t *sf_bytes_d, int32_t sf_stride, dabgpu_superframe *info_d);
+/* MPEG layer II layer for the CIFs of the last dabgpu_pipe_run (call once per run, after it,
+ * before or after dabgpu_pipe_dabplus: each layer takes a run's CIFs once): for every entry
+ * flagged DABGPU_SUBCH_MP2, mp2Processor::addtoFrame over the CIFs dabgpu_pipe_msc_entry_valid
+ * reports as 1, in order (what dabConcurrent feeds it after its 16-CIF warm-up), and
+ * mp2decodeFrame for every frame that completes (see dabgpu_mp2_decode for the arithmetic).
+ * Synchroniser and decoder state are carried across runs; dabgpu_pipe_set_subch keeps them
+ * for an unchanged entry and gives every other one a new mp2Processor.  At most one frame
+ * completes per CIF and entry.  Outputs (device), MP2 slot j of a stream being its j-th
+ * entry flagged DABGPU_SUBCH_MP2:
+ *   pcm_d  int16 [n_streams][4*n_frames][max_mp2][1152][2], written where info.status == 2
+ *   info_d [n_streams][4*n_frames][max_mp2]
+ * Runs on the run's back-end stream behind its MSC (dabgpu_pipe_sync to wait).  Like the
+ * DAB+ layer it reads msc_bits_d back: not for a run whose msc_bits_d is host memory.
+ * DABGPU_E_STATE for a pipeline with max_mp2 == 0 or without a run to consume. */
+int dabgpu_pipe_mp2(dabgpu_pipe *p, int16_t *pcm_d, dabgpu_mp2_info *info_d);
 /* Compact superframe bytes for the following dabgpu_pipe_dabplus calls (on = 1): only the
  * superframes that complete in the run are stored, per (stream, DAB+ subchannel) in CIF
  * order -- sf_bytes_d [n_streams][n_dabplus][DABGPU_SF_SLOTS(n_frames)][sf_stride], the

@@ -189,6 +189,52 @@ struct DpJob {
     int32_t kmax;
 };
 
+// MPEG layer II layer (k_mp2.hip)
+constexpr int MP2_STATE_I16 = 2 * 15 * 64;  // a decoder's carried state: the last 15 V vectors per channel
+struct Mp2Tabs {
+    int32_t D[512];                 // the synthesis window (mp2processor.cpp:68-133)
+    int16_t N[64 * 32];             // the matrixing coefficients (:229-233)
+    uint8_t band[3][32];            // per quantisation table and subband: allocation bits << 4 | allocation row
+    uint8_t rowq[6][16];            // per allocation row and allocation value: quantiser 1..17, 0 none
+};
+// n_chains decoders, chain_len frame slots each; frame j of chain i at frames + (i * chain_len
+// + j) * stride (stride bytes readable, zeros beyond).  Its outputs lie at index
+// (i / cdiv) * idx_a + (i % cdiv) * idx_b + j * idx_c of pcm ([1152][2] int16 each), ret and info.
+struct Mp2Job {
+    const uint8_t *frames;
+    int64_t stride;
+    int32_t n_chains, chain_len;
+    const uint8_t *present;         // optional [n_chains][chain_len]: 0 = the slot holds no frame
+    const int16_t *state_in;        // [n_chains][MP2_STATE_I16]; not the memory of state_out
+    int16_t *state_out;
+    int16_t *pcm;
+    int32_t *ret;                   // optional: mp2decodeFrame's return value (0 for an empty slot)
+    dabgpu_mp2_info *info;          // optional: status 1 / 2 and frame_bytes of the slots that hold a frame
+    int32_t cdiv;
+    int64_t idx_a, idx_b, idx_c;
+    const Mp2Tabs *tabs;
+};
+struct Mp2SyncState {               // mp2Processor's synchroniser, zero for a new one
+    int32_t ok, hc, bc;             // MP2Header_OK, MP2headerCount, MP2bitCount
+    int32_t half_rate;              // baudRate: 0 48000, 1 24000
+};
+struct Mp2SyncJob {
+    const uint8_t *msc;             // MSC bits of the run: [S][ncif][nsub][msc_stride]
+    int32_t msc_stride, ncif, nsub, nmp, nstreams;
+    int32_t packed;                 // msc holds bytes (8 bits msb first), else one bit per byte
+    const int64_t *cif0s;           // [stream] CIF index of the run's first CIF slot
+    const int32_t *ncifs;           // [stream] CIFs the stream delivered in the run
+    const int32_t *mp_sub;          // [S][nmp] table entry of each MP2 slot of the stream, -1: absent
+    const int16_t *mp_br;           // [S][nmp] its bitRate
+    const int64_t *mp_since;        // [S][nmp] its entry's since_cif
+    Mp2SyncState *state;            // [S][nmp]
+    uint8_t *part;                  // [S][nmp][fstride] the frame being collected, packed
+    uint8_t *frames;                // [S * nmp][ncif][fstride] the frame that completed in each CIF
+    int32_t fstride;                // >= 6 * the largest bitRate
+    uint8_t *present;               // [S * nmp][ncif]
+    dabgpu_mp2_info *info;          // [S][ncif][nmp]
+};
+
 // iq: samples in format fmt (DABGPU_IQ_*); frame descriptors count samples
 hipError_t launch_prs_sync(hipStream_t st, const void *iq, int fmt, const dabgpu_frame *fr, int n, const OfdmTables &T,
                            int level, int32_t *si, float *mx, float *sm, bool general);
@@ -221,5 +267,7 @@ hipError_t launch_iq_convert(hipStream_t st, int format, const void *src, int64_
 // device -> mapped pinned host memory by `wgs` workgroups; src, dst, bytes 16-byte aligned
 hipError_t launch_to_host(hipStream_t st, const void *src, void *dst, size_t bytes, int wgs);
 hipError_t launch_rs(hipStream_t st, const uint8_t *in, int n, const uint8_t *tabs, uint8_t *out, int16_t *ret);
+hipError_t launch_mp2_decode(hipStream_t st, const Mp2Job &job);
+hipError_t launch_mp2_sync(hipStream_t st, const Mp2SyncJob &job);
 
 }  // namespace dab

@@ -314,6 +314,14 @@ int dab::scratch(dabgpu_ctx *c, int slot, size_t bytes, void **p) {
     return 0;
 }
 
+// The layer II tables of the context, uploaded at their first use: a context that never
+// decodes layer II allocates nothing for it.
+int dab::mp2_tables(dabgpu_ctx *c, const Mp2Tabs **out) {
+    if (!c->mp2tab) HIPCHK(c->mp2tab.put(mp2_host_tables()));
+    *out = (const Mp2Tabs *)c->mp2tab.ptr;
+    return 0;
+}
+
 // read (and clear) the device error word; call after a stream synchronisation
 int dab::kernel_errors(dabgpu_ctx *c) {
     HIPCHK(hipMemcpyAsync(c->h_err, c->err, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -710,6 +718,34 @@ int dabgpu_fic_decode_frames(dabgpu_ctx *c, const int16_t *soft, const int32_t *
 int dabgpu_rs_decode(dabgpu_ctx *c, const uint8_t *in, int n, uint8_t *out, int16_t *ret) {
     if (!c || !in || !out || !ret || n < 0) return fail(DABGPU_E_ARG, "bad args");
     HIPCHK(launch_rs(c->stream, in, n, c->dptab, out, ret));
+    return 0;
+}
+
+int dabgpu_mp2_decode(dabgpu_ctx *c, const uint8_t *frames, int64_t frame_stride, int n_chains, int chain_len,
+                      void *state, int16_t *pcm, int32_t *ret) {
+    if (!c || !frames || !state || !pcm || !ret || n_chains < 0 || chain_len < 0) return fail(DABGPU_E_ARG, "bad args");
+    if (frame_stride < 4 || frame_stride > 0x7FFFFFFF) return fail(DABGPU_E_ARG, "frame_stride %lld", (long long)frame_stride);
+    if (!n_chains || !chain_len) return 0;
+    // the chain's first workgroup reads the state its last one writes: it reads a copy
+    const size_t sb = (size_t)n_chains * DABGPU_MP2_STATE_BYTES;
+    void *copy = nullptr;
+    if (int rc = scratch(c, SC_MP2, sb, &copy)) return rc;
+    HIPCHK(hipMemcpyAsync(copy, state, sb, hipMemcpyDeviceToDevice, c->stream));
+    Mp2Job J;
+    memset(&J, 0, sizeof J);
+    J.frames = frames;
+    J.stride = frame_stride;
+    J.n_chains = n_chains;
+    J.chain_len = chain_len;
+    J.state_in = (const int16_t *)copy;
+    J.state_out = (int16_t *)state;
+    J.pcm = pcm;
+    J.ret = ret;
+    J.cdiv = 1;
+    J.idx_a = chain_len;
+    J.idx_c = 1;
+    if (int rc = mp2_tables(c, &J.tabs)) return rc;
+    HIPCHK(launch_mp2_decode(c->stream, J));
     return 0;
 }
 

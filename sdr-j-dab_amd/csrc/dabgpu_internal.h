@@ -114,6 +114,7 @@ struct dabgpu_ctx {
     dab::DevBuf<float> refarg;
     dab::DevBuf<uint8_t> dptab;    // DAB+ tables (HostTables::dptab)
     dab::DevBuf<uint8_t> fic_inv;  // the FIC profile's inverse depuncturing table (make_inv)
+    dab::DevBuf<uint8_t> mp2tab;   // layer II tables (Mp2Tabs, mp2_host_tables)
     dab::DevBuf<int32_t> err;      // device error word (KERR_* bits)
     dab::PinBuf<int32_t> h_err;    // its pinned host copy (read after every synchronising pass)
     dab::OfdmTables T{};
@@ -138,7 +139,7 @@ int fail(int code, const char *fmt, ...);
                         hipGetErrorString(e_), __FILE__, __LINE__);                                \
     } while (0)
 
-enum { SC_DEC = 0, SC_PROF = 1, SC_I32 = 2, SC_FRAMES = 3, SC_FC = 4, SC_MISC = 5, SC_ACQ = 6 };
+enum { SC_DEC = 0, SC_PROF = 1, SC_I32 = 2, SC_FRAMES = 3, SC_FC = 4, SC_MISC = 5, SC_ACQ = 6, SC_MP2 = 7 };
 int scratch(dabgpu_ctx *c, int slot, size_t bytes, void **p);
 // read (and clear) the device error word; call after a stream synchronisation
 int kernel_errors(dabgpu_ctx *c);
@@ -152,5 +153,7 @@ int demod_chunks(int n, int extra = 0);
 int make_profile(const dabgpu_subch &s, Profile &p);     // deconvolve.cpp:142-366; nonzero: undefined
 Profile fic_profile();                                   // fic-handler.cpp:254-288
 std::vector<uint8_t> make_inv(const Profile &P);         // inverse depuncturing table
+std::vector<uint8_t> mp2_host_tables();                  // an Mp2Tabs (k_mp2.hip)
+int mp2_tables(dabgpu_ctx *c, const Mp2Tabs **out);      // the context's device copy, made at first use
 
 }  // namespace dab

@@ -57,10 +57,25 @@ struct DabPlus {
     DevBuf<uint8_t> code_d;       // [S][NDP][4F] superframe verdict per candidate CIF
     Event ev;                     // the last superframe pass
 };
+// MPEG layer II layer (mp2Processor per classic-audio subchannel and stream): allocated only
+// for a pipeline with caps.max_mp2 > 0
+struct Mp2Layer {
+    int fstride = 0;              // bytes per frame slot: 2 * 24 * max_bitrate bits
+    DevBuf<int32_t> sub_d;
+    DevBuf<int16_t> br_d;
+    DevBuf<int64_t> since_d;      // [S][NMP]
+    DevBuf<Mp2SyncState> sync_d;  // [S][NMP] the synchronisers
+    DevBuf<uint8_t> part_d;       // [S][NMP][fstride] their frames in progress
+    DevBuf<int16_t> vstate_d[2];  // [S][NMP][MP2_STATE_I16] the decoders: a pass reads [cur], writes [cur ^ 1]
+    int cur = 0;
+    DevBuf<uint8_t> frames_d;     // [S * NMP][4F][fstride] the frames that completed in the run
+    DevBuf<uint8_t> present_d;    // [S * NMP][4F]
+    Event ev;                     // the last pass
+};
 
 struct dabgpu_pipe {
     dabgpu_ctx *c = nullptr;
-    int S = 0, F = 0, NSUB = 0, R = 0, NDP = 0;
+    int S = 0, F = 0, NSUB = 0, R = 0, NDP = 0, NMP = 0;
     int16_t threshold = 3;
     int16_t method = 1;              // freqSyncMethod
     bool scan = false;               // scanMode (No_Signal_Found after > 5 attempts)
@@ -124,7 +139,9 @@ struct dabgpu_pipe {
     std::vector<dabgpu_frame> last_frames;   // [S][F]
     std::vector<dabgpu_frame_info> last_info;   // [S][F] observables of the last run
     DabPlus dp;
+    Mp2Layer mp2;
     const uint8_t *last_msc = nullptr; // MSC bits of the last run
+    bool dp_pending = false, mp2_pending = false;   // the last run's CIFs have not entered the layer yet
     int32_t last_msc_stride = 0;
     bool last_msc_packed = false;
     // the iqBuffer feed (dabgpu_pipe_set_display): symbol 2's display carriers per ring slot
@@ -228,10 +245,10 @@ static int acq_async_setup(dabgpu_pipe *p) {
 
 // A subchannel table against the reference's definitions and the pipeline's caps
 // (dabgpu_pipe_create_caps and dabgpu_pipe_set_subch validate alike)
-static int check_table(const dabgpu_subch *sub, int n, int max_subch, int max_bitrate, int max_dabplus) {
+static int check_table(const dabgpu_subch *sub, int n, int max_subch, int max_bitrate, int max_dabplus, int max_mp2) {
     if (n < 0 || (n > 0 && !sub)) return fail(DABGPU_E_ARG, "bad subchannel table");
     if (n > max_subch) return fail(DABGPU_E_ARG, "%d subchannels, the pipeline holds %d per stream", n, max_subch);
-    int ndp = 0;
+    int ndp = 0, nmp = 0;
     for (int i = 0; i < n; i++) {
         Profile P;
         if (make_profile(sub[i], P)) return fail(DABGPU_E_UNSUP, "subchannel %d protection undefined", i);
@@ -239,6 +256,9 @@ static int check_table(const dabgpu_subch *sub, int n, int max_subch, int max_bi
             return fail(DABGPU_E_ARG, "subchannel %d does not fit its CUs", i);
         if (sub[i].bitRate > max_bitrate)
             return fail(DABGPU_E_ARG, "subchannel %d: bitRate %d above the pipeline's %d", i, sub[i].bitRate, max_bitrate);
+        if ((sub[i].flags & DABGPU_SUBCH_MP2) && (sub[i].flags & DABGPU_SUBCH_DABPLUS))
+            return fail(DABGPU_E_ARG, "subchannel %d is flagged both DAB+ and layer II", i);
+        if (sub[i].flags & DABGPU_SUBCH_MP2) nmp++;
         if (!(sub[i].flags & DABGPU_SUBCH_DABPLUS)) continue;
         // DAB+ subchannels (mp4Processor: RSDims = bitRate / 8, mp4processor.cpp:83-84)
         const int br = sub[i].bitRate;
@@ -247,6 +267,7 @@ static int check_table(const dabgpu_subch *sub, int n, int max_subch, int max_bi
         ndp++;
     }
     if (ndp > max_dabplus) return fail(DABGPU_E_ARG, "%d DAB+ subchannels, the pipeline holds %d per stream", ndp, max_dabplus);
+    if (nmp > max_mp2) return fail(DABGPU_E_ARG, "%d layer II subchannels, the pipeline holds %d per stream", nmp, max_mp2);
     return 0;
 }
 
@@ -339,6 +360,23 @@ static int rebuild_tables(dabgpu_pipe *p) {
         HIPCHK(p->ent_since_d.put(esince));
         HIPCHK(p->act_d.put(act));
     }
+    if (p->NMP) {                 // layer II slots: slot j of a stream is its j-th entry flagged DABGPU_SUBCH_MP2
+        const size_t nm = (size_t)S * p->NMP;
+        std::vector<int32_t> ms(nm, -1);
+        std::vector<int16_t> mb(nm, 0);
+        std::vector<int64_t> mc(nm, 0);
+        for (int s = 0; s < S; s++)
+            for (int k = 0, j = 0; k < (int)p->tab[s].size(); k++) {
+                if (!(p->tab[s][k].flags & DABGPU_SUBCH_MP2)) continue;
+                const size_t i = (size_t)s * p->NMP + j++;
+                ms[i] = k;
+                mb[i] = p->tab[s][k].bitRate;
+                mc[i] = p->since[s][k];
+            }
+        HIPCHK(hipMemcpy(p->mp2.sub_d, ms.data(), sizeof(int32_t) * nm, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(p->mp2.br_d, mb.data(), sizeof(int16_t) * nm, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(p->mp2.since_d, mc.data(), sizeof(int64_t) * nm, hipMemcpyHostToDevice));
+    }
     if (p->NDP) {
         HIPCHK(hipMemcpy(p->dp.sub_d, dps.data(), sizeof(int32_t) * nd, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(p->dp.br_d, dpb.data(), sizeof(int16_t) * nd, hipMemcpyHostToDevice));
@@ -356,6 +394,7 @@ int dabgpu_pipe_create(dabgpu_ctx *c, const dabgpu_pipe_cfg *cfg, dabgpu_pipe **
     for (int i = 0; i < cfg->n_subch; i++) {
         caps.max_bitrate = std::max<int32_t>(caps.max_bitrate, cfg->subch[i].bitRate);
         if (cfg->subch[i].flags & DABGPU_SUBCH_DABPLUS) caps.max_dabplus++;
+        if (cfg->subch[i].flags & DABGPU_SUBCH_MP2) caps.max_mp2++;
     }
     return dabgpu_pipe_create_caps(c, cfg, &caps, out);
 }
@@ -365,17 +404,19 @@ int dabgpu_pipe_create_caps(dabgpu_ctx *c, const dabgpu_pipe_cfg *cfg, const dab
     *out = nullptr;
     if (cfg->n_streams <= 0 || cfg->n_frames <= 0 || cfg->n_subch < 0) return fail(DABGPU_E_ARG, "bad sizes");
     if (caps->max_subch < 0 || caps->max_bitrate < 0 || caps->max_dabplus < 0 || caps->max_dabplus > caps->max_subch ||
-        caps->max_subch > 64 || caps->max_bitrate > 8 * DP_MAX_RS)
+        caps->max_mp2 < 0 || caps->max_mp2 > caps->max_subch || caps->max_subch > 64 || caps->max_bitrate > 8 * DP_MAX_RS)
         return fail(DABGPU_E_ARG, "bad caps (at most 64 subchannels of at most 384 kbit/s)");
     if (cfg->freq_sync_method < 0 || cfg->freq_sync_method > 2)
         return fail(DABGPU_E_UNSUP, "freqSyncMethod %d (0, 1 or 2: ofdm-decoder.cpp:103-161)", cfg->freq_sync_method);
-    if (int rc = check_table(cfg->subch, cfg->n_subch, caps->max_subch, caps->max_bitrate, caps->max_dabplus)) return rc;
+    if (int rc = check_table(cfg->subch, cfg->n_subch, caps->max_subch, caps->max_bitrate, caps->max_dabplus, caps->max_mp2))
+        return rc;
     auto p = std::make_unique<dabgpu_pipe>();
     p->c = c;
     p->S = cfg->n_streams;
     p->F = cfg->n_frames;
     p->NSUB = caps->max_subch;
     p->NDP = caps->max_dabplus;
+    p->NMP = caps->max_mp2;
     p->max_bitrate = caps->max_bitrate;
     p->R = 2 * cfg->n_frames + 4;
     p->threshold = cfg->threshold;
@@ -430,6 +471,25 @@ int dabgpu_pipe_create_caps(dabgpu_ctx *c, const dabgpu_pipe_cfg *cfg, const dab
         HIPCHK(p->dp.code_d.alloc(nd * 4 * p->F));
         HIPCHK(hipMemset(p->dp.ring_d, 0, nd * 120 * DP_MAX_RS));
         HIPCHK(hipMemset(p->dp.state_d, 0, sizeof(DpState) * nd));
+    }
+    if (p->NMP) {
+        Mp2Layer &m = p->mp2;
+        const size_t nm = (size_t)p->S * p->NMP;
+        m.fstride = 6 * std::max(p->max_bitrate, 1);
+        HIPCHK(m.ev.create(hipEventDisableTiming));
+        HIPCHK(m.sub_d.alloc(nm));
+        HIPCHK(m.br_d.alloc(nm));
+        HIPCHK(m.since_d.alloc(nm));
+        HIPCHK(m.sync_d.alloc(nm));
+        HIPCHK(m.part_d.alloc(nm * m.fstride));
+        HIPCHK(m.frames_d.alloc(nm * 4 * p->F * m.fstride));
+        HIPCHK(m.present_d.alloc(nm * 4 * p->F));
+        HIPCHK(hipMemset(m.sync_d, 0, sizeof(Mp2SyncState) * nm));
+        HIPCHK(hipMemset(m.part_d, 0, nm * m.fstride));
+        for (auto &v : m.vstate_d) {
+            HIPCHK(v.alloc(nm * MP2_STATE_I16));
+            HIPCHK(hipMemset(v, 0, sizeof(int16_t) * nm * MP2_STATE_I16));
+        }
     }
     if (int rc = rebuild_tables(p.get())) return rc;
     // the default re-acquisition mode: a stream that loses sync is searched in the
@@ -904,6 +964,7 @@ int dabgpu_pipe_run(dabgpu_pipe *p, const void *iq, int64_t stride, const int64_
     p->run_idx++;
     p->inject_bounds = false;
     p->last_msc = have_rows ? msc_bits : nullptr;
+    p->dp_pending = p->mp2_pending = have_rows;
     p->last_msc_stride = msc_stride;
     p->last_msc_packed = p->packed;
     publish_validity(p, done, have_rows, msc_valid);
@@ -951,7 +1012,7 @@ int dabgpu_pipe_sync(dabgpu_pipe *p) {
 int dabgpu_pipe_dabplus(dabgpu_pipe *p, uint8_t *sf_bytes, int32_t sf_stride, dabgpu_superframe *info) {
     if (!p || !sf_bytes || !info) return fail(DABGPU_E_ARG, "null arg");
     if (p->NDP == 0) return fail(DABGPU_E_STATE, "no DAB+ subchannel in this pipeline");
-    if (!p->last_msc) return fail(DABGPU_E_STATE, "no dabgpu_pipe_run with MSC output to consume");
+    if (!p->last_msc || !p->dp_pending) return fail(DABGPU_E_STATE, "no dabgpu_pipe_run with MSC output to consume");
     if (sf_stride < 110 * p->dp.max_rs) return fail(DABGPU_E_ARG, "sf_stride %d < %d", sf_stride, 110 * p->dp.max_rs);
     dabgpu_ctx *c = p->c;
     DpJob J;
@@ -999,7 +1060,60 @@ int dabgpu_pipe_dabplus(dabgpu_pipe *p, uint8_t *sf_bytes, int32_t sf_stride, da
     HIPCHK(p->dp.ev.record(bs));
     // (the run after next does not wait for this: the layer reads this run's MSC output
     // and CIF counters, which that run's back end overwrites behind it on this stream)
-    p->last_msc = nullptr;                     // each run's CIFs enter the superframe layer once
+    p->dp_pending = false;                     // each run's CIFs enter the superframe layer once
+    return 0;
+}
+
+int dabgpu_pipe_mp2(dabgpu_pipe *p, int16_t *pcm, dabgpu_mp2_info *info) {
+    if (!p || !pcm || !info) return fail(DABGPU_E_ARG, "null arg");
+    if (p->NMP == 0) return fail(DABGPU_E_STATE, "no layer II subchannel in this pipeline");
+    if (!p->last_msc || !p->mp2_pending) return fail(DABGPU_E_STATE, "no dabgpu_pipe_run with MSC output to consume");
+    Mp2Layer &m = p->mp2;
+    Mp2SyncJob Y;
+    memset(&Y, 0, sizeof Y);
+    Y.msc = p->last_msc;
+    Y.msc_stride = p->last_msc_stride;
+    Y.packed = p->last_msc_packed ? 1 : 0;
+    Y.ncif = 4 * p->F;
+    Y.nsub = p->NSUB;
+    Y.nmp = p->NMP;
+    Y.nstreams = p->S;
+    Y.cif0s = p->cif0_dev(p->cur);
+    Y.ncifs = p->ncif_dev(p->cur);
+    Y.mp_sub = m.sub_d;
+    Y.mp_br = m.br_d;
+    Y.mp_since = m.since_d;
+    Y.state = m.sync_d;
+    Y.part = m.part_d;
+    Y.frames = m.frames_d;
+    Y.fstride = m.fstride;
+    Y.present = m.present_d;
+    Y.info = info;
+    Mp2Job J;
+    memset(&J, 0, sizeof J);
+    J.frames = m.frames_d;
+    J.stride = m.fstride;
+    J.n_chains = p->S * p->NMP;
+    J.chain_len = 4 * p->F;
+    J.present = m.present_d;
+    J.state_in = m.vstate_d[m.cur];
+    J.state_out = m.vstate_d[m.cur ^ 1];
+    J.pcm = pcm;
+    J.info = info;
+    J.cdiv = p->NMP;
+    J.idx_a = (int64_t)4 * p->F * p->NMP;
+    J.idx_b = 1;
+    J.idx_c = p->NMP;
+    if (int rc = mp2_tables(p->c, &J.tabs)) return rc;
+    // on the last run's back-end stream (after its MSC), after the previous pass (the
+    // synchronisers, the decoders and the frame slots carry over or are reused)
+    hipStream_t bs = p->back[p->cur].stream;
+    HIPCHK(m.ev.wait_on(bs));
+    HIPCHK(launch_mp2_sync(bs, Y));
+    HIPCHK(launch_mp2_decode(bs, J));
+    HIPCHK(m.ev.record(bs));
+    m.cur ^= 1;
+    p->mp2_pending = false;                    // each run's CIFs enter the layer once
     return 0;
 }
 
@@ -1110,7 +1224,7 @@ int dabgpu_pipe_frame_slot(dabgpu_pipe *p, int frame, int32_t *slot) {
 }
 int dabgpu_pipe_set_subch(dabgpu_pipe *p, int stream, const dabgpu_subch *sub, int32_t n) {
     if (!p || stream < -1 || stream >= p->S) return fail(DABGPU_E_ARG, "bad args");
-    if (int rc = check_table(sub, n, p->NSUB, p->max_bitrate, p->NDP)) return rc;   // the table stays on error
+    if (int rc = check_table(sub, n, p->NSUB, p->max_bitrate, p->NDP, p->NMP)) return rc;   // the table stays on error
     // in-flight kernels read the device tables: a rare control call, so it waits for
     // everything the pipeline has enqueued (as dabgpu_pipe_set_profiling) instead of
     // double-buffering them
@@ -1134,6 +1248,34 @@ int dabgpu_pipe_set_subch(dabgpu_pipe *p, int stream, const dabgpu_subch *sub, i
             HIPCHK(hipMemcpy(sts.data(), p->dp.state_d + (size_t)s * p->NDP, sizeof(DpState) * p->NDP, hipMemcpyDeviceToHost));
             nrings.assign(rings.size(), 0);
             nsts.assign(p->NDP, DpState{0, 0});
+        }
+        // the layer II slots likewise: synchroniser, frame in progress and decoder of an
+        // unchanged entry move to its new slot, every other slot is a new mp2Processor
+        if (p->NMP) {
+            Mp2Layer &m = p->mp2;
+            const size_t NM = p->NMP, FS = m.fstride, o = (size_t)s * NM;
+            std::vector<Mp2SyncState> sy(NM), nsy(NM, Mp2SyncState{0, 0, 0, 0});
+            std::vector<uint8_t> pt(NM * FS), npt(NM * FS, 0);
+            std::vector<int16_t> vs(NM * MP2_STATE_I16), nvs(NM * MP2_STATE_I16, 0);
+            HIPCHK(hipMemcpy(sy.data(), m.sync_d + o, sizeof(Mp2SyncState) * NM, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(pt.data(), m.part_d + o * FS, NM * FS, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(vs.data(), m.vstate_d[m.cur] + o * MP2_STATE_I16, sizeof(int16_t) * vs.size(), hipMemcpyDeviceToHost));
+            std::vector<int> oslot(old.size(), -1);
+            for (int k = 0, j = 0; k < (int)old.size(); k++)
+                if (old[k].flags & DABGPU_SUBCH_MP2) oslot[k] = j++;
+            for (int k = 0, j = 0; k < n; k++) {
+                if (!(sub[k].flags & DABGPU_SUBCH_MP2)) continue;
+                if (k < (int)old.size() && same_subch(old[k], sub[k])) {
+                    nsy[j] = sy[oslot[k]];
+                    memcpy(npt.data() + j * FS, pt.data() + oslot[k] * FS, FS);
+                    memcpy(nvs.data() + (size_t)j * MP2_STATE_I16, vs.data() + (size_t)oslot[k] * MP2_STATE_I16,
+                           sizeof(int16_t) * MP2_STATE_I16);
+                }
+                j++;
+            }
+            HIPCHK(hipMemcpy(m.sync_d + o, nsy.data(), sizeof(Mp2SyncState) * NM, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(m.part_d + o * FS, npt.data(), NM * FS, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(m.vstate_d[m.cur] + o * MP2_STATE_I16, nvs.data(), sizeof(int16_t) * nvs.size(), hipMemcpyHostToDevice));
         }
         p->tab[s].assign(sub, sub + n);
         p->since[s].assign(n, p->st[s].cif_count);

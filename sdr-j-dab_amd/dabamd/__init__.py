@@ -35,6 +35,9 @@ class Subch(C.Structure):
 
 
 SUBCH_DABPLUS = 1   # Subch.flags: feed the DAB+ superframe layer
+SUBCH_MP2 = 4       # Subch.flags: feed the MPEG layer II layer (Pipeline.mp2)
+MP2_STATE_BYTES = 3840   # DABGPU_MP2_STATE_BYTES: a layer II decoder's carried state
+MP2_INFO_DTYPE = np.dtype([("status", "<i4"), ("sample_rate", "<i4"), ("frame_bytes", "<i4")])   # dabgpu_mp2_info
 SUPERFRAME_DTYPE = np.dtype([("status", "i1"), ("num_aus", "i1"), ("n_corrected", "<i2"), ("au_start", "<i2", (7,)),
                              ("au_crc_ok", "u1"), ("reserved", "u1")])
 
@@ -53,7 +56,7 @@ class Frame(C.Structure):
 
 class PipeCaps(C.Structure):
     _fields_ = [("max_subch", C.c_int32), ("max_bitrate", C.c_int32), ("max_dabplus", C.c_int32),
-                ("reserved", C.c_int32)]
+                ("max_mp2", C.c_int32)]
 
 
 class PipeCfg(C.Structure):
@@ -123,6 +126,8 @@ def lib() -> C.CDLL:
             "dabgpu_msc_deconvolve": ([vp, vp, i64, vp, i32, vp, i64], i32),
             "dabgpu_rs_decode": ([vp, vp, i32, vp, vp], i32),
             "dabgpu_pipe_dabplus": ([vp, vp, C.c_int32, vp], i32),
+            "dabgpu_mp2_decode": ([vp, vp, i64, i32, i32, vp, vp, vp], i32),
+            "dabgpu_pipe_mp2": ([vp, vp, vp], i32),
             "dabgpu_pipe_sync": ([vp], i32),
             "dabgpu_pipe_create": ([vp, vp, C.POINTER(vp)], i32), "dabgpu_pipe_destroy": ([vp], i32),
             "dabgpu_pipe_acquire": ([vp, vp, i64, vp, vp], i32),
@@ -446,6 +451,30 @@ class Context:
         finally:
             din.free(); dout.free(); dr.free()
 
+    def mp2_decode(self, frames: np.ndarray, chain_len: int, state: Optional[np.ndarray] = None):
+        """mp2Processor::mp2decodeFrame per row (mp2processor.cpp:365-568): frames
+        [n_chains * chain_len, stride] bytes, chain_len consecutive rows to each decoder in
+        order; state [n_chains, MP2_STATE_BYTES] bytes carried from an earlier call (None:
+        new decoders).  Returns (pcm [n_chains, chain_len, 1152, 2] int16 -- zeros where the
+        frame was rejected --, ret [n_chains, chain_len] int32, state)."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        n, stride = frames.shape
+        if chain_len <= 0 or n % chain_len:
+            raise DabError("mp2_decode: rows are not a multiple of chain_len")
+        nc = n // chain_len
+        st = np.zeros((nc, MP2_STATE_BYTES), np.uint8) if state is None else \
+            np.ascontiguousarray(state, dtype=np.uint8).reshape(nc, MP2_STATE_BYTES)
+        din, ds = self.put(frames), self.put(st)
+        dp, dr = self.buf(max(1, n * 1152 * 4)).zero(), self.buf(max(4, 4 * n))
+        try:
+            _chk(lib().dabgpu_mp2_decode(self.h, din.ptr, stride, nc, chain_len, ds.ptr, dp.ptr, dr.ptr),
+                 "dabgpu_mp2_decode")
+            self.sync()
+            return (dp.download(np.int16, (nc, chain_len, 1152, 2)), dr.download(np.int32, (nc, chain_len)),
+                    ds.download(np.uint8, (nc, MP2_STATE_BYTES)))
+        finally:
+            din.free(); ds.free(); dp.free(); dr.free()
+
     def prs_sync(self, iq: DevBuf, frames: Sequence[Frame], level: int = 3):
         """phaseReference::findIndex (phasereference.cpp:60-88) per frame window."""
         n = len(frames)
@@ -607,7 +636,8 @@ class Pipeline:
 
     def __init__(self, ctx: Context, n_streams: int, n_frames: int, subch: Sequence[Subch],
                  threshold: int = 3, freq_sync_method: int = 1, max_subch: Optional[int] = None,
-                 max_bitrate: Optional[int] = None, max_dabplus: Optional[int] = None):
+                 max_bitrate: Optional[int] = None, max_dabplus: Optional[int] = None,
+                 max_mp2: Optional[int] = None):
         self.ctx, self.S, self.F, self.subch = ctx, n_streams, n_frames, list(subch)
         self._arr = (Subch * max(1, len(self.subch)))(*self.subch)
         cfg = PipeCfg(n_streams, n_frames, len(self.subch), threshold, freq_sync_method,
@@ -617,10 +647,11 @@ class Pipeline:
                sum(1 for s in self.subch if s.flags & SUBCH_DABPLUS))
         given = (max_subch, max_bitrate, max_dabplus)
         self.max_subch, self.max_bitrate, self.max_dabplus = [o if g is None else int(g) for o, g in zip(own, given)]
-        if given == (None, None, None):
+        self.max_mp2 = sum(1 for s in self.subch if s.flags & SUBCH_MP2) if max_mp2 is None else int(max_mp2)
+        if given == (None, None, None) and max_mp2 is None:
             _chk(lib().dabgpu_pipe_create(ctx.h, C.byref(cfg), C.byref(h)), "dabgpu_pipe_create")
         else:
-            caps = PipeCaps(self.max_subch, self.max_bitrate, self.max_dabplus, 0)
+            caps = PipeCaps(self.max_subch, self.max_bitrate, self.max_dabplus, self.max_mp2)
             _chk(lib().dabgpu_pipe_create_caps(ctx.h, C.byref(cfg), C.byref(caps), C.byref(h)),
                  "dabgpu_pipe_create_caps")
         self.h = h
@@ -648,6 +679,10 @@ class Pipeline:
             nrec = n_streams * 4 * n_frames * self.max_dabplus
             self._sf = [(ctx.buf(nrec * self.sf_stride), ctx.buf(nrec * C.sizeof(Superframe))) for _ in range(2)]
             self.sf_d, self.sfi_d = self._sf[0]
+        self._mp2 = []
+        if self.max_mp2:
+            nrec = n_streams * 4 * n_frames * self.max_mp2
+            self._mp2 = [(ctx.buf(nrec * 1152 * 4).zero(), ctx.buf(nrec * MP2_INFO_DTYPE.itemsize)) for _ in range(2)]
 
     def acquire(self, iq: DevBuf, stride: int, start: Sequence[int], n_avail: Sequence[int]) -> None:
         st = np.asarray(start, dtype=np.int64)
@@ -728,6 +763,23 @@ class Pipeline:
         else:
             sf = self.sf_d.download(np.uint8, (self.S, 4 * self.F, nd, self.sf_stride))
         return info, sf
+
+    def mp2(self, download: bool = True):
+        """MPEG layer II layer over the CIFs of the last run() (dabgpu_pipe_mp2; mp2processor.cpp:
+        365-617).  Returns (pcm [S, 4F, max_mp2, 1152, 2] int16, valid where info.status == 2,
+        info [S, 4F, max_mp2] MP2_INFO_DTYPE records)."""
+        if not self._mp2:                # max_mp2 == 0: the library refuses (DABGPU_E_STATE) before it writes
+            _chk(lib().dabgpu_pipe_mp2(self.h, self.fic_d.ptr, self.crc_d.ptr), "dabgpu_pipe_mp2")
+            raise DabError("dabgpu_pipe_mp2 accepted a pipeline without layer II slots")
+        self.pcm_d, self.mp2i_d = self._mp2[(self._run - 1) & 1]
+        _chk(lib().dabgpu_pipe_mp2(self.h, self.pcm_d.ptr, self.mp2i_d.ptr), "dabgpu_pipe_mp2")
+        if not download:
+            return None
+        self.sync()
+        shape = (self.S, 4 * self.F, self.max_mp2)
+        raw = self.mp2i_d.download(np.uint8, int(np.prod(shape)) * MP2_INFO_DTYPE.itemsize)
+        return (self.pcm_d.download(np.int16, shape + (1152, 2)),
+                np.frombuffer(raw.tobytes(), dtype=MP2_INFO_DTYPE).reshape(shape))
 
     STAGES = ("prs_sync", "block0", "demod", "fic", "msc_acs", "msc_traceback", "dabplus")
 
@@ -827,7 +879,7 @@ class Pipeline:
 
     def close(self) -> None:
         if self.h:
-            for o in self._outs + self._sf:
+            for o in self._outs + self._sf + self._mp2:
                 for b in o:
                     b.free()
             lib().dabgpu_pipe_destroy(self.h)

@@ -244,7 +244,9 @@ ensembleDecoder::ensembleDecoder(const config &cfg) : cfg_(cfg) {
     for (const dabgpu_subch &sc : cfg.subch) {
         caps.max_bitrate = std::max<int32_t>(caps.max_bitrate, sc.bitRate);
         if (sc.flags & DABGPU_SUBCH_DABPLUS) caps.max_dabplus++;
+        if (sc.flags & DABGPU_SUBCH_MP2) caps.max_mp2++;
     }
+    if (cfg.max_mp2) caps.max_mp2 = cfg.max_mp2;
     if (cfg.max_subch) caps.max_subch = cfg.max_subch;                    // ... or what the caller allows
     if (cfg.max_bitrate) caps.max_bitrate = cfg.max_bitrate;
     if (cfg.max_dabplus) caps.max_dabplus = cfg.max_dabplus;
@@ -273,6 +275,11 @@ ensembleDecoder::ensembleDecoder(const config &cfg) : cfg_(cfg) {
     if (ndp_) {
         sf_.resize(SF * 4 * ndp_ * sf_stride_);
         sfi_.resize(SF * 4 * ndp_ * sizeof(dabgpu_superframe));
+    }
+    nmp_ = caps.max_mp2;
+    if (nmp_) {
+        pcm_.resize(SF * 4 * nmp_ * 2304 * sizeof(int16_t));
+        mp2i_.resize(SF * 4 * nmp_ * sizeof(dabgpu_mp2_info));
     }
 }
 
@@ -501,6 +508,27 @@ bool ensembleDecoder::step() {
             }
         }
     }
+    if (NS && nmp_) {
+        chk(dabgpu_pipe_mp2(pipe_, (int16_t *)pcm_.get(), (dabgpu_mp2_info *)mp2i_.get()), "dabgpu_pipe_mp2");
+        chk(dabgpu_pipe_sync(pipe_), "dabgpu_pipe_sync");
+        if (pcm_cb_) {
+            std::vector<dabgpu_mp2_info> info((size_t)S * 4 * F * nmp_);
+            std::vector<int16_t> pcm(info.size() * 2304);
+            mp2i_.download(info.data(), info.size() * sizeof(dabgpu_mp2_info));
+            pcm_.download(pcm.data(), pcm.size() * sizeof(int16_t));
+            for (int s = 0; s < S; s++) {
+                std::vector<int> slot;               // MP2 slot j of a stream is its j-th flagged entry
+                for (int k = 0; k < (int)tab_[s].size(); k++)
+                    if (tab_[s][k].flags & DABGPU_SUBCH_MP2) slot.push_back(k);
+                for (int c = 0; c < 4 * F; c++)
+                    for (int j = 0; j < (int)slot.size() && j < nmp_; j++) {
+                        const size_t r = ((size_t)s * 4 * F + c) * nmp_ + j;
+                        if (info[r].status == 2)
+                            pcm_cb_(s, 4 * frames_done_[s] + c, slot[j], pcm.data() + r * 2304, 1152, info[r].sample_rate);
+                    }
+            }
+        }
+    }
     for (int s = 0; s < S; s++) {
         dabgpu_stream_state st;
         chk(dabgpu_pipe_state(pipe_, s, &st), "dabgpu_pipe_state");
@@ -509,7 +537,7 @@ bool ensembleDecoder::step() {
     // FIC first: a table parsed twice alike (two steps) and not yet applied is applied now
     for (int s = 0; s < S && cfg_.auto_layout; s++) {
         std::vector<dabgpu_subch> now;
-        for (const fib_subch &e : fibs_[s].subchannels())
+        for (const fib_subch &e : fibs_[s].subchannels(nullptr, pcm_cb_ != nullptr && nmp_ > 0))
             now.push_back({e.startAddr, e.length, e.bitRate, e.protLevel, e.uepFlag, e.flags});
         auto same = [](const std::vector<dabgpu_subch> &x, const std::vector<dabgpu_subch> &y) {
             return x.size() == y.size() && (x.empty() || !std::memcmp(x.data(), y.data(), x.size() * sizeof(dabgpu_subch)));

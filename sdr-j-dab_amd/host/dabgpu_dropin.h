@@ -476,6 +476,7 @@ public:
         // dabgpu_pipe_caps: table entries, largest bitRate and DAB+ entries a stream's table
         // may hold (0: what subch needs)
         int max_subch = 0, max_bitrate = 0, max_dabplus = 0;
+        int max_mp2 = 0;                     // layer II (DABGPU_SUBCH_MP2) entries likewise
         // FIC first: each stream's table follows its own FIG 0/1 and 0/2 (a fib_processor per
         // stream, fed its CRC-good FIBs).  At the end of a step() a stream's parsed table is
         // applied (set_subch) when it is non-empty, equals the one parsed at the end of the
@@ -492,6 +493,14 @@ public:
     void on_fib(fib_cb f) { fib_cb_ = std::move(f); }
     void on_msc(msc_cb f) { msc_cb_ = std::move(f); }
     void on_superframe(sf_cb f) { sf_cb_ = std::move(f); }
+    // Decoded classic DAB audio, where audioSink::audioOut stands in the reference
+    // (mp2processor.cpp:584-588): one call per MPEG layer II frame of an entry flagged
+    // DABGPU_SUBCH_MP2 that mp2decodeFrame accepted (dabgpu_pipe_mp2), pcm = n_samples
+    // (1152) stereo pairs, rate = the processor's baudRate (48000 or 24000); cif is the CIF
+    // in which the frame completed.  With auto_layout, sub-channels whose audio component
+    // has ASCTy 0 are flagged when this callback is set before the table is applied.
+    using pcm_cb = std::function<void(int stream, int64_t cif, int subch, const int16_t *pcm, int n_samples, int rate)>;
+    void on_pcm(pcm_cb f) { pcm_cb_ = std::move(f); }
     // samples[s] -> n[s] cf32 samples of stream s (copied to HBM)
     void load(const std::vector<const DSPCOMPLEX *> &samples, const std::vector<int64_t> &n);
     // the streams as recorded: format DABGPU_IQ_S16 (.sdr PCM16 I/Q pairs) or DABGPU_IQ_U8
@@ -520,7 +529,9 @@ public:
 private:
     config cfg_;
     dabgpu_pipe *pipe_ = nullptr;
-    devbuf iq_, fic_, crc_, msc_, sf_, sfi_;
+    devbuf iq_, fic_, crc_, msc_, sf_, sfi_, pcm_, mp2i_;
+    int nmp_ = 0;
+    pcm_cb pcm_cb_;
     int64_t stride_ = 0;
     std::vector<int64_t> navail_;
     int msc_stride_ = 0, sf_stride_ = 0, ndp_ = 0, maxbits_ = 0, nsub_ = 0;

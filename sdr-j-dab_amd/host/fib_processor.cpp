@@ -367,7 +367,7 @@ int fib_processor::bind(int8_t tmid, int32_t sid, int16_t compnr) {
     return first_free;
 }
 
-std::vector<fib_subch> fib_processor::subchannels(std::vector<int> *ids) const {
+std::vector<fib_subch> fib_processor::subchannels(std::vector<int> *ids, bool classic_audio) const {
     std::vector<fib_subch> v;
     if (ids) ids->clear();
     for (int id = 0; id < 64; id++) {
@@ -376,7 +376,11 @@ std::vector<fib_subch> fib_processor::subchannels(std::vector<int> *ids) const {
         fib_subch e = {(int16_t)s.StartAddr, (int16_t)s.Length, (int16_t)s.BitRate, (int16_t)s.protLevel,
                           (int16_t)s.uepFlag, 0};
         for (const component &c : components_)
-            if (c.inUse && c.TMid == 0 && c.subchannelId == id && c.ASCTy == 077) e.flags |= 1;   // DABGPU_SUBCH_DABPLUS
+            if (c.inUse && c.TMid == 0 && c.subchannelId == id) {
+                if (c.ASCTy == 077) e.flags |= 1;                       // DABGPU_SUBCH_DABPLUS
+                else if (c.ASCTy == 0 && classic_audio) e.flags |= 4;   // DABGPU_SUBCH_MP2
+            }
+        if (e.flags & 1) e.flags &= ~4;                                 // (one layer per entry)
         v.push_back(e);
         if (ids) ids->push_back(id);
     }

@@ -94,7 +94,9 @@ public:
     // dabgpu_pipe_set_subch takes: startAddr, length, bitRate, protLevel and uepFlag as the
     // parser stores them; flags = DABGPU_SUBCH_DABPLUS where a bound audio component
     // (FIG 0/2) on the sub-channel has ASCTy 63.  ids (optional) receives each entry's SubChId.
-    std::vector<fib_subch> subchannels(std::vector<int> *ids = nullptr) const;
+    // classic_audio: also flag DABGPU_SUBCH_MP2 (4) where such a component has ASCTy 0
+    // (MPEG layer II, what the reference hands to mp2Processor).
+    std::vector<fib_subch> subchannels(std::vector<int> *ids = nullptr, bool classic_audio = false) const;
 
     std::string ensembleName() const { return ensemble_; }
     std::vector<std::string> serviceLabels() const;
