@@ -72,6 +72,60 @@ typedef struct {
 #define DABGPU_SUBCH_MP2     4   /* feed the MPEG layer II layer (dabgpu_pipe_mp2); not together
                                     with DABGPU_SUBCH_DABPLUS on one entry (DABGPU_E_ARG) */
 
+#define DABGPU_SUBCH_PACKET  8   /* feed the packet-mode data layer (dabgpu_pipe_packet); not together
+                                    with DABGPU_SUBCH_DABPLUS or DABGPU_SUBCH_MP2 on one entry
+                                    (DABGPU_E_ARG); bitRate a multiple of 8 in [8, max_bitrate]
+                                    (DABGPU_E_UNSUP otherwise) */
+
+/* One CIF of one packet-mode subchannel through mscDatagroup::handlePackets
+ * (msc-datagroup.cpp:221-319, show_crcErrors on). */
+typedef struct {
+    int16_t status;         /* -1 CIF not delivered or inside the entry's warm-up, 0 fed */
+    int16_t packets;        /* packets handlePackets walked in this CIF */
+    int16_t crc_errors;     /* ... of which check_CRC_bits refused */
+    int16_t groups;         /* data groups completed in this CIF */
+    int16_t quality;        /* what show_mscErrors emits in this CIF (100 - crcErrors / 5 when the
+                               carried count of handled packets reaches 500, :250-254), else -1 */
+    int16_t address;        /* streamAddress after the CIF, -1 before the latch */
+} dabgpu_packet_info;
+/* One (stream, packet slot) after a run */
+typedef struct {
+    int32_t n_groups;       /* groups completed in the run */
+    int32_t n_bytes;        /* their stored bytes, packed back to back from offset 0 */
+    int32_t state;          /* packetState after the run */
+    int32_t pending_bytes;  /* length of the series in flight (0 in state 0) */
+} dabgpu_packet_run;
+/* One completed MSC data group: what my_dataHandler->add_mscDatagroup receives, as bytes, and
+ * the generic header as mot_databuilder::add_mscDatagroup parses it (mot-databuilder.cpp:37-95) */
+typedef struct {
+    int32_t cif;            /* slot in the run of the packet that completed the group */
+    int32_t offset;         /* of its first byte in the (stream, slot)'s arena */
+    int32_t nbytes;         /* its length (stored: min(nbytes, max_group_bytes)) */
+    int32_t data_offset;    /* the reference's next / 8: header bytes before the data field */
+    int32_t data_nbytes;    /* the reference's sizeinBits / 8 (in int32), 0 when it would be negative */
+    uint16_t flags;         /* DABGPU_DG_* */
+    uint16_t segmentNumber;
+    uint16_t transportId;
+    uint8_t groupType;
+    uint8_t CI;
+    uint8_t lengthInd;
+    uint8_t reserved[3];
+} dabgpu_datagroup;
+#define DABGPU_DG_EXTENSION   1
+#define DABGPU_DG_CRC         2     /* the CRC flag */
+#define DABGPU_DG_SEGMENT     4
+#define DABGPU_DG_USER_ACCESS 8
+#define DABGPU_DG_LAST        16    /* last segment */
+#define DABGPU_DG_TRANSPORT   32    /* transport-id flag */
+#define DABGPU_DG_ACCEPTED    64    /* nbytes > 0, not truncated, and no CRC flag or a good CRC:
+                                       the groups add_mscDatagroup goes on with */
+#define DABGPU_DG_TRUNCATED   128
+#define DABGPU_PKT_GROUP_BYTES 8216 /* the default max_group_bytes: 2 + 2 + 2 + 16 header bytes,
+                                       8191 data bytes and 2 CRC bytes, rounded up to 8 */
+#define DABGPU_PKT_GROUP_SLOTS(n_frames, max_bitrate) (4 * (n_frames) * ((max_bitrate) / 8))
+#define DABGPU_PKT_ARENA_BYTES(n_frames, max_bitrate, max_group_bytes) \
+    ((max_group_bytes) + 4 * (n_frames) * ((max_bitrate) / 8) * 127)
+
 /* One CIF of one classic-audio subchannel through mp2Processor::addtoFrame
  * (mp2processor.cpp:572-617) and, when a frame completed in it, mp2decodeFrame (:365-568). */
 typedef struct {
@@ -377,10 +431,13 @@ int dabgpu_pipe_create_caps(dabgpu_ctx *ctx, const dabgpu_pipe_cfg *cfg, const d
 /* Replace the table of one stream (stream = -1: of every stream) for the runs that follow.
  * Validates as create does: DABGPU_E_UNSUP for an undefined protection or a bad DAB+
  * bitRate, DABGPU_E_ARG for an entry outside its CUs, for n > max_subch, a bitRate above
- * max_bitrate, more DAB+ entries than max_dabplus, more layer II entries than max_mp2 or an
- * entry flagged for both layers; on any error the table is unchanged.
+ * max_bitrate, more DAB+ entries than max_dabplus, more layer II entries than max_mp2, more
+ * packet-mode entries than dabgpu_pipe_packet_caps allows or an entry flagged for two layers;
+ * DABGPU_E_UNSUP for a packet-mode bitRate that is no multiple of 8; on any error the table
+ * is unchanged.  (A packet-mode entry that is not unchanged is a new mscDatagroup.)
  * Waits for everything the pipeline has enqueued (as dabgpu_pipe_set_profiling): call
- * dabgpu_pipe_dabplus / dabgpu_pipe_mp2 for the last run before it.
+ * dabgpu_pipe_dabplus / dabgpu_pipe_mp2 / dabgpu_pipe_packet for the last run before it (the
+ * layers refuse a run decoded under the old table: its rows are not the new slots').
  * An entry whose index and all six fields are unchanged keeps its since_cif and its DAB+ or
  * layer II state and decodes without interruption.  Every other entry gets since_cif = the
  * stream's cif_count at the call, its DAB+ ring and state zeroed (a new mp4Processor) or its
@@ -447,6 +504,48 @@ int dabgpu_pipe_dabplus(dabgpu_pipe *p, uint8_t *sf_bytes_d, int32_t sf_stride, 
  * DAB+ layer it reads msc_bits_d back: not for a run whose msc_bits_d is host memory.
  * DABGPU_E_STATE for a pipeline with max_mp2 == 0 or without a run to consume. */
 int dabgpu_pipe_mp2(dabgpu_pipe *p, int16_t *pcm_d, dabgpu_mp2_info *info_d);
+/* Packet-mode data layer for the CIFs of the last dabgpu_pipe_run (call once per run, after
+ * it, in any order with dabgpu_pipe_dabplus / dabgpu_pipe_mp2): for every entry flagged
+ * DABGPU_SUBCH_PACKET, mscDatagroup::handlePackets + handlePacket (msc-datagroup.cpp:221-319,
+ * show_crcErrors on) over the CIFs dabgpu_pipe_msc_entry_valid reports as 1, in order, and for
+ * every completed series the header parse and CRC of mot_databuilder::add_mscDatagroup
+ * (mot-databuilder.cpp:37-95) -- bit for bit what host/msc_consumers' packetAssembler
+ * delivers, its quirks included: the copy takes usefulLength bytes from byte 3 whatever the
+ * packet's length (a CRC-good packet whose useful length exceeds its data field reads its
+ * own CRC bytes complemented, as check_CRC_bits leaves them, then the following packets'
+ * bytes) and stops at the CIF's end.  Where the reference is undefined or unbounded:
+ *   1. header fields past a group's end read as 0 (and a group with the CRC flag and fewer
+ *      than 2 bytes has a bad CRC);
+ *   2. lengths are int32 (the reference's int16_t sizeinBits wraps above 4095 bytes);
+ *   3. a series longer than max_group_bytes keeps its first max_group_bytes bytes, is
+ *      reported with its full nbytes, flagged DABGPU_DG_TRUNCATED and not accepted.
+ * Out of scope: DSCTy 5 with the DG flag (handleTDCAsyncstream delivers nothing: do not
+ * flag such entries) and the FEC scheme (the reference ignores it).
+ * Assembler state (packetState, streamAddress, the 500-packet window, the series in flight)
+ * is carried across runs; dabgpu_pipe_set_subch keeps it for an unchanged entry and gives
+ * every other one a new mscDatagroup.  Outputs (device), packet slot j of a stream being its
+ * j-th entry flagged DABGPU_SUBCH_PACKET:
+ *   info_d   [n_streams][4*n_frames][max_packet]
+ *   run_d    [n_streams][max_packet]
+ *   groups_d [n_streams][max_packet][DABGPU_PKT_GROUP_SLOTS(n_frames, max_bitrate)], in
+ *            completion order, the first run.n_groups written
+ *   bytes_d  [n_streams][max_packet][DABGPU_PKT_ARENA_BYTES(n_frames, max_bitrate,
+ *            max_group_bytes)], the groups' stored bytes back to back (the most a run can
+ *            complete, the over-read included)
+ * Runs on the run's back-end stream behind its MSC (dabgpu_pipe_sync to wait); reads
+ * msc_bits_d (one bit per byte or DABGPU_PACK_MSC bytes) and never writes it: not for a run
+ * whose msc_bits_d is host memory.  DABGPU_E_STATE without a layer (max_packet == 0) or
+ * without a run to consume. */
+int dabgpu_pipe_packet(dabgpu_pipe *p, uint8_t *bytes_d, dabgpu_datagroup *groups_d, dabgpu_packet_run *run_d,
+                       dabgpu_packet_info *info_d);
+/* Size the packet-mode layer: max_packet slots per stream, groups of at most max_group_bytes
+ * (0: DABGPU_PKT_GROUP_BYTES).  Both create calls start with the number of flagged entries
+ * of their table and the default group size; with max_packet == 0 nothing is allocated or
+ * launched.  Between runs; waits for everything enqueued, as dabgpu_pipe_set_subch.  The
+ * state of the existing entries is kept (a series in flight longer than a smaller
+ * max_group_bytes keeps its first bytes).  DABGPU_E_ARG for negative values, max_packet >
+ * max_subch or fewer slots than an applied table flags. */
+int dabgpu_pipe_packet_caps(dabgpu_pipe *p, int max_packet, int max_group_bytes);
 /* Compact superframe bytes for the following dabgpu_pipe_dabplus calls (on = 1): only the
  * superframes that complete in the run are stored, per (stream, DAB+ subchannel) in CIF
  * order -- sf_bytes_d [n_streams][n_dabplus][DABGPU_SF_SLOTS(n_frames)][sf_stride], the

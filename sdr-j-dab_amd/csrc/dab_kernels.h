@@ -235,6 +235,41 @@ struct Mp2SyncJob {
     dabgpu_mp2_info *info;          // [S][ncif][nmp]
 };
 
+// packet-mode data layer (k_packet.hip)
+constexpr int PK_MAX_CELLS = 48;    // 24-byte cells of a CIF at 384 kbit/s
+struct PkState {                    // an mscDatagroup's assembler, {0, -1, 0, 0, 0, 0, 0, 0} for a new one
+    int32_t state, address;         // packetState, streamAddress
+    int32_t handled, crc_errors;    // the 500-packet window (show_crcErrors)
+    int32_t pending;                // bytes of the series in flight (its first `cap` lie in the carry)
+    int32_t prev_state, prev_pending;   // state and pending at the start of the last pass (k_pkt_copy)
+    int32_t reserved;
+};
+struct PkJob {
+    const uint8_t *msc;             // MSC bits of the run: [S][ncif][nsub][msc_stride]
+    int32_t msc_stride, ncif, nsub, npk, nstreams;
+    int32_t packed;                 // msc holds bytes (8 bits msb first), else one bit per byte
+    int32_t ncell;                  // cells per CIF the buffers hold: max_bitrate / 8
+    int32_t cap;                    // max_group_bytes
+    const int64_t *cif0s;           // [stream] CIF index of the run's first CIF slot
+    const int32_t *ncifs;           // [stream] CIFs the stream delivered in the run
+    const int32_t *pk_sub;          // [S][npk] table entry of each packet slot of the stream, -1: absent
+    const int16_t *pk_br;           // [S][npk] its bitRate
+    const int64_t *pk_since;        // [S][npk] its entry's since_cif
+    PkState *state;                 // [S][npk]
+    const uint8_t *carry_in;        // [S][npk][cap] the series in flight before the run
+    uint8_t *carry_out;             // ... and after it (not the memory of carry_in)
+    uint32_t *rec;                  // [S * npk][ncif][ncell] packet records (k_pkt_scan)
+    int2 *take;                     // [S * npk][ncif][ncell] x: bytes taken | series << 7, y: byte offset in the series
+    int32_t *segtab;                // [S * npk][1 + ncif * ncell] per series of the run (0: the one carried in):
+                                    //   its group's arena offset, -1 dropped, -2 still in flight
+    uint8_t *bytes;                 // [S * npk][arena]
+    int64_t arena;
+    dabgpu_datagroup *groups;       // [S * npk][gslots]
+    int32_t gslots;
+    dabgpu_packet_run *run;         // [S * npk]
+    dabgpu_packet_info *info;       // [S][ncif][npk]
+};
+
 // iq: samples in format fmt (DABGPU_IQ_*); frame descriptors count samples
 hipError_t launch_prs_sync(hipStream_t st, const void *iq, int fmt, const dabgpu_frame *fr, int n, const OfdmTables &T,
                            int level, int32_t *si, float *mx, float *sm, bool general);
@@ -269,5 +304,6 @@ hipError_t launch_to_host(hipStream_t st, const void *src, void *dst, size_t byt
 hipError_t launch_rs(hipStream_t st, const uint8_t *in, int n, const uint8_t *tabs, uint8_t *out, int16_t *ret);
 hipError_t launch_mp2_decode(hipStream_t st, const Mp2Job &job);
 hipError_t launch_mp2_sync(hipStream_t st, const Mp2SyncJob &job);
+hipError_t launch_packet(hipStream_t st, const PkJob &job);
 
 }  // namespace dab

@@ -72,10 +72,25 @@ struct Mp2Layer {
     DevBuf<uint8_t> present_d;    // [S * NMP][4F]
     Event ev;                     // the last pass
 };
+// Packet-mode data layer (an mscDatagroup's assembler per packet-mode subchannel and stream):
+// allocated only while dabgpu_pipe_packet_caps' max_packet > 0
+struct PacketLayer {
+    int cap = 0, ncell = 0;       // max_group_bytes; cells per CIF the buffers hold (max_bitrate / 8)
+    DevBuf<int32_t> sub_d;
+    DevBuf<int16_t> br_d;
+    DevBuf<int64_t> since_d;      // [S][NPK]
+    DevBuf<PkState> state_d;      // [S][NPK] the assemblers
+    DevBuf<uint8_t> carry_d[2];   // [S][NPK][cap] their series in flight: a pass reads [cur], writes [cur ^ 1]
+    int cur = 0;
+    DevBuf<uint32_t> rec_d;       // [S * NPK][4F][ncell] packet records of the run
+    DevBuf<int2> take_d;          // [S * NPK][4F][ncell]
+    DevBuf<int32_t> segtab_d;     // [S * NPK][1 + 4F * ncell]
+    Event ev;                     // the last pass
+};
 
 struct dabgpu_pipe {
     dabgpu_ctx *c = nullptr;
-    int S = 0, F = 0, NSUB = 0, R = 0, NDP = 0, NMP = 0;
+    int S = 0, F = 0, NSUB = 0, R = 0, NDP = 0, NMP = 0, NPK = 0;
     int16_t threshold = 3;
     int16_t method = 1;              // freqSyncMethod
     bool scan = false;               // scanMode (No_Signal_Found after > 5 attempts)
@@ -140,8 +155,9 @@ struct dabgpu_pipe {
     std::vector<dabgpu_frame_info> last_info;   // [S][F] observables of the last run
     DabPlus dp;
     Mp2Layer mp2;
+    PacketLayer pk;
     const uint8_t *last_msc = nullptr; // MSC bits of the last run
-    bool dp_pending = false, mp2_pending = false;   // the last run's CIFs have not entered the layer yet
+    bool dp_pending = false, mp2_pending = false, pk_pending = false;   // the last run's CIFs have not entered the layer yet
     int32_t last_msc_stride = 0;
     bool last_msc_packed = false;
     // the iqBuffer feed (dabgpu_pipe_set_display): symbol 2's display carriers per ring slot
@@ -245,20 +261,30 @@ static int acq_async_setup(dabgpu_pipe *p) {
 
 // A subchannel table against the reference's definitions and the pipeline's caps
 // (dabgpu_pipe_create_caps and dabgpu_pipe_set_subch validate alike)
-static int check_table(const dabgpu_subch *sub, int n, int max_subch, int max_bitrate, int max_dabplus, int max_mp2) {
+static int check_table(const dabgpu_subch *sub, int n, int max_subch, int max_bitrate, int max_dabplus, int max_mp2,
+                       int max_packet) {
     if (n < 0 || (n > 0 && !sub)) return fail(DABGPU_E_ARG, "bad subchannel table");
     if (n > max_subch) return fail(DABGPU_E_ARG, "%d subchannels, the pipeline holds %d per stream", n, max_subch);
-    int ndp = 0, nmp = 0;
+    int ndp = 0, nmp = 0, npk = 0;
     for (int i = 0; i < n; i++) {
         Profile P;
         if (make_profile(sub[i], P)) return fail(DABGPU_E_UNSUP, "subchannel %d protection undefined", i);
         if (sub[i].startAddr < 0 || sub[i].startAddr + sub[i].length > 864 || P.frag > sub[i].length * 64)
             return fail(DABGPU_E_ARG, "subchannel %d does not fit its CUs", i);
+        // packets are multiples of 24 bytes: a CIF of 3 * bitRate bytes holds bitRate / 8 cells
+        if ((sub[i].flags & DABGPU_SUBCH_PACKET) && (sub[i].bitRate < 8 || sub[i].bitRate % 8 || sub[i].bitRate > max_bitrate))
+            return fail(DABGPU_E_UNSUP, "packet-mode subchannel %d: bitRate %d is not a multiple of 8 in [8, %d]", i,
+                        sub[i].bitRate, max_bitrate);
         if (sub[i].bitRate > max_bitrate)
             return fail(DABGPU_E_ARG, "subchannel %d: bitRate %d above the pipeline's %d", i, sub[i].bitRate, max_bitrate);
         if ((sub[i].flags & DABGPU_SUBCH_MP2) && (sub[i].flags & DABGPU_SUBCH_DABPLUS))
             return fail(DABGPU_E_ARG, "subchannel %d is flagged both DAB+ and layer II", i);
         if (sub[i].flags & DABGPU_SUBCH_MP2) nmp++;
+        if (sub[i].flags & DABGPU_SUBCH_PACKET) {
+            if (sub[i].flags & (DABGPU_SUBCH_MP2 | DABGPU_SUBCH_DABPLUS))
+                return fail(DABGPU_E_ARG, "subchannel %d is flagged packet mode and an audio layer", i);
+            npk++;
+        }
         if (!(sub[i].flags & DABGPU_SUBCH_DABPLUS)) continue;
         // DAB+ subchannels (mp4Processor: RSDims = bitRate / 8, mp4processor.cpp:83-84)
         const int br = sub[i].bitRate;
@@ -268,12 +294,62 @@ static int check_table(const dabgpu_subch *sub, int n, int max_subch, int max_bi
     }
     if (ndp > max_dabplus) return fail(DABGPU_E_ARG, "%d DAB+ subchannels, the pipeline holds %d per stream", ndp, max_dabplus);
     if (nmp > max_mp2) return fail(DABGPU_E_ARG, "%d layer II subchannels, the pipeline holds %d per stream", nmp, max_mp2);
+    if (npk > max_packet)
+        return fail(DABGPU_E_ARG, "%d packet-mode subchannels, the pipeline holds %d per stream", npk, max_packet);
     return 0;
 }
 
 static bool same_subch(const dabgpu_subch &a, const dabgpu_subch &b) {
     return a.startAddr == b.startAddr && a.length == b.length && a.bitRate == b.bitRate && a.protLevel == b.protLevel &&
            a.uepFlag == b.uepFlag && a.flags == b.flags;
+}
+
+// (Re)size the packet-mode layer to npk slots per stream and groups of cap bytes.  The
+// assemblers of the slots both sizes hold go on (their carried bytes cut or padded to cap),
+// every other slot is a new mscDatagroup.  The caller has waited for the streams.  The new
+// layer is built beside the old one and takes its place only when everything succeeded: on
+// an error the pipeline keeps the layer, and the assemblers, it had.
+static int packet_size(dabgpu_pipe *p, int npk, int cap) {
+    const PacketLayer &old = p->pk;
+    const int S = p->S, old_n = p->NPK, old_cap = old.cap;
+    std::vector<PkState> ost;
+    std::vector<uint8_t> oca;
+    if (old_n) {
+        ost.resize((size_t)S * old_n);
+        oca.resize((size_t)S * old_n * old_cap);
+        HIPCHK(hipMemcpy(ost.data(), old.state_d, sizeof(PkState) * ost.size(), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(oca.data(), old.carry_d[old.cur], oca.size(), hipMemcpyDeviceToHost));
+    }
+    PacketLayer k;
+    if (!npk) {
+        p->pk = std::move(k);
+        p->NPK = 0;
+        return 0;
+    }
+    k.cap = cap;
+    k.ncell = std::max(1, p->max_bitrate / 8);
+    const size_t ne = (size_t)S * npk, cells = (size_t)4 * p->F * k.ncell;
+    HIPCHK(k.ev.create(hipEventDisableTiming));
+    HIPCHK(k.sub_d.alloc(ne));
+    HIPCHK(k.br_d.alloc(ne));
+    HIPCHK(k.since_d.alloc(ne));
+    HIPCHK(k.state_d.alloc(ne));
+    HIPCHK(k.rec_d.alloc(ne * cells));
+    HIPCHK(k.take_d.alloc(ne * cells));
+    HIPCHK(k.segtab_d.alloc(ne * (1 + cells)));
+    for (auto &c : k.carry_d) HIPCHK(c.alloc(ne * cap));
+    std::vector<PkState> st(ne, PkState{0, -1, 0, 0, 0, 0, 0, 0});
+    std::vector<uint8_t> ca(ne * cap, 0);
+    for (int s = 0; s < S; s++)
+        for (int j = 0; j < std::min(old_n, npk); j++) {
+            st[(size_t)s * npk + j] = ost[(size_t)s * old_n + j];
+            memcpy(ca.data() + ((size_t)s * npk + j) * cap, oca.data() + ((size_t)s * old_n + j) * old_cap, std::min(cap, old_cap));
+        }
+    HIPCHK(hipMemcpy(k.state_d, st.data(), sizeof(PkState) * ne, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(k.carry_d[0], ca.data(), ca.size(), hipMemcpyHostToDevice));
+    p->pk = std::move(k);
+    p->NPK = npk;
+    return 0;
 }
 
 // The device's descriptor tables from p->tab / p->since.  The caller has waited for the
@@ -377,6 +453,23 @@ static int rebuild_tables(dabgpu_pipe *p) {
         HIPCHK(hipMemcpy(p->mp2.br_d, mb.data(), sizeof(int16_t) * nm, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(p->mp2.since_d, mc.data(), sizeof(int64_t) * nm, hipMemcpyHostToDevice));
     }
+    if (p->NPK) {                 // packet slots: slot j of a stream is its j-th entry flagged DABGPU_SUBCH_PACKET
+        const size_t nk = (size_t)S * p->NPK;
+        std::vector<int32_t> ks(nk, -1);
+        std::vector<int16_t> kb(nk, 0);
+        std::vector<int64_t> kc(nk, 0);
+        for (int s = 0; s < S; s++)
+            for (int k = 0, j = 0; k < (int)p->tab[s].size(); k++) {
+                if (!(p->tab[s][k].flags & DABGPU_SUBCH_PACKET)) continue;
+                const size_t i = (size_t)s * p->NPK + j++;
+                ks[i] = k;
+                kb[i] = p->tab[s][k].bitRate;
+                kc[i] = p->since[s][k];
+            }
+        HIPCHK(hipMemcpy(p->pk.sub_d, ks.data(), sizeof(int32_t) * nk, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(p->pk.br_d, kb.data(), sizeof(int16_t) * nk, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(p->pk.since_d, kc.data(), sizeof(int64_t) * nk, hipMemcpyHostToDevice));
+    }
     if (p->NDP) {
         HIPCHK(hipMemcpy(p->dp.sub_d, dps.data(), sizeof(int32_t) * nd, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(p->dp.br_d, dpb.data(), sizeof(int16_t) * nd, hipMemcpyHostToDevice));
@@ -408,7 +501,10 @@ int dabgpu_pipe_create_caps(dabgpu_ctx *c, const dabgpu_pipe_cfg *cfg, const dab
         return fail(DABGPU_E_ARG, "bad caps (at most 64 subchannels of at most 384 kbit/s)");
     if (cfg->freq_sync_method < 0 || cfg->freq_sync_method > 2)
         return fail(DABGPU_E_UNSUP, "freqSyncMethod %d (0, 1 or 2: ofdm-decoder.cpp:103-161)", cfg->freq_sync_method);
-    if (int rc = check_table(cfg->subch, cfg->n_subch, caps->max_subch, caps->max_bitrate, caps->max_dabplus, caps->max_mp2))
+    int npk = 0;                  // the packet-mode layer starts with what the table flags (dabgpu_pipe_packet_caps)
+    for (int i = 0; i < cfg->n_subch; i++)
+        if (cfg->subch[i].flags & DABGPU_SUBCH_PACKET) npk++;
+    if (int rc = check_table(cfg->subch, cfg->n_subch, caps->max_subch, caps->max_bitrate, caps->max_dabplus, caps->max_mp2, npk))
         return rc;
     auto p = std::make_unique<dabgpu_pipe>();
     p->c = c;
@@ -491,6 +587,8 @@ int dabgpu_pipe_create_caps(dabgpu_ctx *c, const dabgpu_pipe_cfg *cfg, const dab
             HIPCHK(hipMemset(v, 0, sizeof(int16_t) * nm * MP2_STATE_I16));
         }
     }
+    if (npk)
+        if (int rc = packet_size(p.get(), npk, DABGPU_PKT_GROUP_BYTES)) return rc;
     if (int rc = rebuild_tables(p.get())) return rc;
     // the default re-acquisition mode: a stream that loses sync is searched in the
     // background (DABGPU_CTL_ACQ_ASYNC; DABGPU_CTL_ACQ_SYNC restores the in-run search)
@@ -964,7 +1062,7 @@ int dabgpu_pipe_run(dabgpu_pipe *p, const void *iq, int64_t stride, const int64_
     p->run_idx++;
     p->inject_bounds = false;
     p->last_msc = have_rows ? msc_bits : nullptr;
-    p->dp_pending = p->mp2_pending = have_rows;
+    p->dp_pending = p->mp2_pending = p->pk_pending = have_rows;
     p->last_msc_stride = msc_stride;
     p->last_msc_packed = p->packed;
     publish_validity(p, done, have_rows, msc_valid);
@@ -1117,6 +1215,66 @@ int dabgpu_pipe_mp2(dabgpu_pipe *p, int16_t *pcm, dabgpu_mp2_info *info) {
     return 0;
 }
 
+int dabgpu_pipe_packet(dabgpu_pipe *p, uint8_t *bytes, dabgpu_datagroup *groups, dabgpu_packet_run *run,
+                       dabgpu_packet_info *info) {
+    if (!p || !bytes || !groups || !run || !info) return fail(DABGPU_E_ARG, "null arg");
+    if (p->NPK == 0) return fail(DABGPU_E_STATE, "no packet-mode subchannel in this pipeline");
+    if (!p->last_msc || !p->pk_pending) return fail(DABGPU_E_STATE, "no dabgpu_pipe_run with MSC output to consume");
+    PacketLayer &k = p->pk;
+    PkJob J;
+    memset(&J, 0, sizeof J);
+    J.msc = p->last_msc;
+    J.msc_stride = p->last_msc_stride;
+    J.packed = p->last_msc_packed ? 1 : 0;
+    J.ncif = 4 * p->F;
+    J.nsub = p->NSUB;
+    J.npk = p->NPK;
+    J.nstreams = p->S;
+    J.ncell = k.ncell;
+    J.cap = k.cap;
+    J.cif0s = p->cif0_dev(p->cur);
+    J.ncifs = p->ncif_dev(p->cur);
+    J.pk_sub = k.sub_d;
+    J.pk_br = k.br_d;
+    J.pk_since = k.since_d;
+    J.state = k.state_d;
+    J.carry_in = k.carry_d[k.cur];
+    J.carry_out = k.carry_d[k.cur ^ 1];
+    J.rec = k.rec_d;
+    J.take = k.take_d;
+    J.segtab = k.segtab_d;
+    J.bytes = bytes;
+    J.arena = DABGPU_PKT_ARENA_BYTES((int64_t)p->F, p->max_bitrate, k.cap);
+    J.groups = groups;
+    J.gslots = DABGPU_PKT_GROUP_SLOTS(p->F, p->max_bitrate);
+    J.run = run;
+    J.info = info;
+    // on the last run's back-end stream (after its MSC), after the previous pass (the
+    // assemblers and the work buffers carry over or are reused)
+    hipStream_t bs = p->back[p->cur].stream;
+    HIPCHK(k.ev.wait_on(bs));
+    HIPCHK(launch_packet(bs, J));
+    HIPCHK(k.ev.record(bs));
+    k.cur ^= 1;
+    p->pk_pending = false;                     // each run's CIFs enter the layer once
+    return 0;
+}
+
+int dabgpu_pipe_packet_caps(dabgpu_pipe *p, int max_packet, int max_group_bytes) {
+    if (!p || max_packet < 0 || max_group_bytes < 0 || max_packet > p->NSUB) return fail(DABGPU_E_ARG, "bad args");
+    if (max_packet && p->max_bitrate < 8) return fail(DABGPU_E_ARG, "max_bitrate %d holds no packet-mode entry", p->max_bitrate);
+    const int cap = max_group_bytes ? max_group_bytes : DABGPU_PKT_GROUP_BYTES;
+    for (int s = 0; s < p->S; s++) {
+        int n = 0;
+        for (const dabgpu_subch &e : p->tab[s])
+            if (e.flags & DABGPU_SUBCH_PACKET) n++;
+        if (n > max_packet) return fail(DABGPU_E_ARG, "stream %d's table has %d packet-mode subchannels", s, n);
+    }
+    if (int rc = sync_streams(p)) return rc;
+    if (int rc = packet_size(p, max_packet, cap)) return rc;
+    return rebuild_tables(p);
+}
+
 int dabgpu_pipe_state(dabgpu_pipe *p, int s, dabgpu_stream_state *o) {
     if (!p || !o || s < 0 || s >= p->S) return fail(DABGPU_E_ARG, "bad args");
     // a background null search that has finished is taken now (not at the next run), so
@@ -1224,7 +1382,7 @@ int dabgpu_pipe_frame_slot(dabgpu_pipe *p, int frame, int32_t *slot) {
 }
 int dabgpu_pipe_set_subch(dabgpu_pipe *p, int stream, const dabgpu_subch *sub, int32_t n) {
     if (!p || stream < -1 || stream >= p->S) return fail(DABGPU_E_ARG, "bad args");
-    if (int rc = check_table(sub, n, p->NSUB, p->max_bitrate, p->NDP, p->NMP)) return rc;   // the table stays on error
+    if (int rc = check_table(sub, n, p->NSUB, p->max_bitrate, p->NDP, p->NMP, p->NPK)) return rc;   // the table stays on error
     // in-flight kernels read the device tables: a rare control call, so it waits for
     // everything the pipeline has enqueued (as dabgpu_pipe_set_profiling) instead of
     // double-buffering them
@@ -1276,6 +1434,29 @@ int dabgpu_pipe_set_subch(dabgpu_pipe *p, int stream, const dabgpu_subch *sub, i
             HIPCHK(hipMemcpy(m.sync_d + o, nsy.data(), sizeof(Mp2SyncState) * NM, hipMemcpyHostToDevice));
             HIPCHK(hipMemcpy(m.part_d + o * FS, npt.data(), NM * FS, hipMemcpyHostToDevice));
             HIPCHK(hipMemcpy(m.vstate_d[m.cur] + o * MP2_STATE_I16, nvs.data(), sizeof(int16_t) * nvs.size(), hipMemcpyHostToDevice));
+        }
+        // the packet slots likewise: an unchanged entry's assembler and series in flight move
+        // to its new slot, every other slot is a new mscDatagroup
+        if (p->NPK) {
+            PacketLayer &m = p->pk;
+            const size_t NK = p->NPK, CB = m.cap, o = (size_t)s * NK;
+            std::vector<PkState> ps(NK), nps(NK, PkState{0, -1, 0, 0, 0, 0, 0, 0});
+            std::vector<uint8_t> ca(NK * CB), nca(NK * CB, 0);
+            HIPCHK(hipMemcpy(ps.data(), m.state_d + o, sizeof(PkState) * NK, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(ca.data(), m.carry_d[m.cur] + o * CB, NK * CB, hipMemcpyDeviceToHost));
+            std::vector<int> oslot(old.size(), -1);
+            for (int k = 0, j = 0; k < (int)old.size(); k++)
+                if (old[k].flags & DABGPU_SUBCH_PACKET) oslot[k] = j++;
+            for (int k = 0, j = 0; k < n; k++) {
+                if (!(sub[k].flags & DABGPU_SUBCH_PACKET)) continue;
+                if (k < (int)old.size() && same_subch(old[k], sub[k])) {
+                    nps[j] = ps[oslot[k]];
+                    memcpy(nca.data() + j * CB, ca.data() + oslot[k] * CB, CB);
+                }
+                j++;
+            }
+            HIPCHK(hipMemcpy(m.state_d + o, nps.data(), sizeof(PkState) * NK, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(m.carry_d[m.cur] + o * CB, nca.data(), NK * CB, hipMemcpyHostToDevice));
         }
         p->tab[s].assign(sub, sub + n);
         p->since[s].assign(n, p->st[s].cif_count);

@@ -38,6 +38,28 @@ SUBCH_DABPLUS = 1   # Subch.flags: feed the DAB+ superframe layer
 SUBCH_MP2 = 4       # Subch.flags: feed the MPEG layer II layer (Pipeline.mp2)
 MP2_STATE_BYTES = 3840   # DABGPU_MP2_STATE_BYTES: a layer II decoder's carried state
 MP2_INFO_DTYPE = np.dtype([("status", "<i4"), ("sample_rate", "<i4"), ("frame_bytes", "<i4")])   # dabgpu_mp2_info
+SUBCH_PACKET = 8    # Subch.flags: feed the packet-mode data layer (Pipeline.packet)
+PKT_GROUP_BYTES = 8216   # DABGPU_PKT_GROUP_BYTES: the default max_group_bytes
+PACKET_INFO_DTYPE = np.dtype([("status", "<i2"), ("packets", "<i2"), ("crc_errors", "<i2"), ("groups", "<i2"),
+                              ("quality", "<i2"), ("address", "<i2")])                     # dabgpu_packet_info
+PACKET_RUN_DTYPE = np.dtype([("n_groups", "<i4"), ("n_bytes", "<i4"), ("state", "<i4"), ("pending_bytes", "<i4")])
+DATAGROUP_DTYPE = np.dtype([("cif", "<i4"), ("offset", "<i4"), ("nbytes", "<i4"), ("data_offset", "<i4"),
+                            ("data_nbytes", "<i4"), ("flags", "<u2"), ("segmentNumber", "<u2"), ("transportId", "<u2"),
+                            ("groupType", "u1"), ("CI", "u1"), ("lengthInd", "u1"), ("reserved", "u1", (3,))])
+DG_EXTENSION, DG_CRC, DG_SEGMENT, DG_USER_ACCESS, DG_LAST, DG_TRANSPORT, DG_ACCEPTED, DG_TRUNCATED = (
+    1, 2, 4, 8, 16, 32, 64, 128)
+
+
+def pkt_group_slots(n_frames: int, max_bitrate: int) -> int:
+    """DABGPU_PKT_GROUP_SLOTS"""
+    return 4 * n_frames * (max_bitrate // 8)
+
+
+def pkt_arena_bytes(n_frames: int, max_bitrate: int, max_group_bytes: int) -> int:
+    """DABGPU_PKT_ARENA_BYTES"""
+    return max_group_bytes + 4 * n_frames * (max_bitrate // 8) * 127
+
+
 SUPERFRAME_DTYPE = np.dtype([("status", "i1"), ("num_aus", "i1"), ("n_corrected", "<i2"), ("au_start", "<i2", (7,)),
                              ("au_crc_ok", "u1"), ("reserved", "u1")])
 
@@ -128,6 +150,8 @@ def lib() -> C.CDLL:
             "dabgpu_pipe_dabplus": ([vp, vp, C.c_int32, vp], i32),
             "dabgpu_mp2_decode": ([vp, vp, i64, i32, i32, vp, vp, vp], i32),
             "dabgpu_pipe_mp2": ([vp, vp, vp], i32),
+            "dabgpu_pipe_packet": ([vp, vp, vp, vp, vp], i32),
+            "dabgpu_pipe_packet_caps": ([vp, i32, i32], i32),
             "dabgpu_pipe_sync": ([vp], i32),
             "dabgpu_pipe_create": ([vp, vp, C.POINTER(vp)], i32), "dabgpu_pipe_destroy": ([vp], i32),
             "dabgpu_pipe_acquire": ([vp, vp, i64, vp, vp], i32),
@@ -637,7 +661,8 @@ class Pipeline:
     def __init__(self, ctx: Context, n_streams: int, n_frames: int, subch: Sequence[Subch],
                  threshold: int = 3, freq_sync_method: int = 1, max_subch: Optional[int] = None,
                  max_bitrate: Optional[int] = None, max_dabplus: Optional[int] = None,
-                 max_mp2: Optional[int] = None):
+                 max_mp2: Optional[int] = None, max_packet: Optional[int] = None,
+                 max_group_bytes: Optional[int] = None):
         self.ctx, self.S, self.F, self.subch = ctx, n_streams, n_frames, list(subch)
         self._arr = (Subch * max(1, len(self.subch)))(*self.subch)
         cfg = PipeCfg(n_streams, n_frames, len(self.subch), threshold, freq_sync_method,
@@ -683,6 +708,59 @@ class Pipeline:
         if self.max_mp2:
             nrec = n_streams * 4 * n_frames * self.max_mp2
             self._mp2 = [(ctx.buf(nrec * 1152 * 4).zero(), ctx.buf(nrec * MP2_INFO_DTYPE.itemsize)) for _ in range(2)]
+
+        self._pkt = []
+        self.max_packet = sum(1 for s in self.subch if s.flags & SUBCH_PACKET)
+        self.max_group_bytes = PKT_GROUP_BYTES
+        if max_packet is not None or max_group_bytes is not None:
+            self.packet_caps(self.max_packet if max_packet is None else max_packet, max_group_bytes or 0)
+        else:
+            self._packet_bufs()
+
+    def _packet_bufs(self) -> None:
+        for o in self._pkt:
+            for b in o:
+                b.free()
+        self._pkt = []
+        if self.max_packet:
+            ne = self.S * self.max_packet
+            self._pkt = [(self.ctx.buf(ne * pkt_arena_bytes(self.F, self.max_bitrate, self.max_group_bytes)),
+                          self.ctx.buf(ne * pkt_group_slots(self.F, self.max_bitrate) * DATAGROUP_DTYPE.itemsize),
+                          self.ctx.buf(ne * PACKET_RUN_DTYPE.itemsize),
+                          self.ctx.buf(ne * 4 * self.F * PACKET_INFO_DTYPE.itemsize)) for _ in range(2)]
+
+    def packet_caps(self, max_packet: int, max_group_bytes: int = 0) -> None:
+        """size the packet-mode layer between runs (dabgpu_pipe_packet_caps): max_packet slots
+        per stream, groups of at most max_group_bytes (0: PKT_GROUP_BYTES); the existing
+        entries keep their assembler state"""
+        _chk(lib().dabgpu_pipe_packet_caps(self.h, int(max_packet), int(max_group_bytes)), "dabgpu_pipe_packet_caps")
+        self.max_packet, self.max_group_bytes = int(max_packet), int(max_group_bytes) or PKT_GROUP_BYTES
+        self._packet_bufs()
+
+    def packet(self, download: bool = True):
+        """packet-mode data layer over the CIFs of the last run() (dabgpu_pipe_packet;
+        msc-datagroup.cpp:221-319, mot-databuilder.cpp:37-95).  Returns (bytes [S, max_packet,
+        arena] uint8, groups [S, max_packet, slots] DATAGROUP_DTYPE -- the first run.n_groups of a
+        row are this run's --, run [S, max_packet] PACKET_RUN_DTYPE, info [S, 4F, max_packet]
+        PACKET_INFO_DTYPE)."""
+        if not self._pkt:                # max_packet == 0: the library refuses (DABGPU_E_STATE) before it writes
+            _chk(lib().dabgpu_pipe_packet(self.h, self.fic_d.ptr, self.fic_d.ptr, self.fic_d.ptr, self.fic_d.ptr),
+                 "dabgpu_pipe_packet")
+            raise DabError("dabgpu_pipe_packet accepted a pipeline without packet slots")
+        self.pkb_d, self.pkg_d, self.pkr_d, self.pki_d = self._pkt[(self._run - 1) & 1]
+        _chk(lib().dabgpu_pipe_packet(self.h, self.pkb_d.ptr, self.pkg_d.ptr, self.pkr_d.ptr, self.pki_d.ptr),
+             "dabgpu_pipe_packet")
+        if not download:
+            return None
+        self.sync()
+        S, NP = self.S, self.max_packet
+
+        def rec(buf, dtype, shape):
+            raw = buf.download(np.uint8, int(np.prod(shape)) * dtype.itemsize)
+            return np.frombuffer(raw.tobytes(), dtype=dtype).reshape(shape)
+        return (self.pkb_d.download(np.uint8, (S, NP, pkt_arena_bytes(self.F, self.max_bitrate, self.max_group_bytes))),
+                rec(self.pkg_d, DATAGROUP_DTYPE, (S, NP, pkt_group_slots(self.F, self.max_bitrate))),
+                rec(self.pkr_d, PACKET_RUN_DTYPE, (S, NP)), rec(self.pki_d, PACKET_INFO_DTYPE, (S, 4 * self.F, NP)))
 
     def acquire(self, iq: DevBuf, stride: int, start: Sequence[int], n_avail: Sequence[int]) -> None:
         st = np.asarray(start, dtype=np.int64)
@@ -879,7 +957,7 @@ class Pipeline:
 
     def close(self) -> None:
         if self.h:
-            for o in self._outs + self._sf + self._mp2:
+            for o in self._outs + self._sf + self._mp2 + self._pkt:
                 for b in o:
                     b.free()
             lib().dabgpu_pipe_destroy(self.h)

@@ -281,6 +281,22 @@ ensembleDecoder::ensembleDecoder(const config &cfg) : cfg_(cfg) {
         pcm_.resize(SF * 4 * nmp_ * 2304 * sizeof(int16_t));
         mp2i_.resize(SF * 4 * nmp_ * sizeof(dabgpu_mp2_info));
     }
+    for (const dabgpu_subch &sc : cfg.subch)
+        if (sc.flags & DABGPU_SUBCH_PACKET) npk_++;
+    pk_cap_ = cfg.max_group_bytes ? cfg.max_group_bytes : DABGPU_PKT_GROUP_BYTES;
+    if (cfg.max_packet || cfg.max_group_bytes) {
+        npk_ = cfg.max_packet ? cfg.max_packet : npk_;
+        chk(dabgpu_pipe_packet_caps(pipe_, npk_, cfg.max_group_bytes), "dabgpu_pipe_packet_caps");
+    }
+    if (npk_) {
+        pk_slots_ = DABGPU_PKT_GROUP_SLOTS(cfg.n_frames, (int)caps.max_bitrate);
+        pk_arena_ = DABGPU_PKT_ARENA_BYTES((size_t)cfg.n_frames, (int)caps.max_bitrate, pk_cap_);
+        const size_t ne = (size_t)cfg.n_streams * npk_;
+        pkb_.resize(ne * pk_arena_);
+        pkg_.resize(std::max<size_t>(1, ne * pk_slots_) * sizeof(dabgpu_datagroup));
+        pkr_.resize(ne * sizeof(dabgpu_packet_run));
+        pki_.resize(SF * 4 * npk_ * sizeof(dabgpu_packet_info));
+    }
 }
 
 void ensembleDecoder::set_subch(int stream, const std::vector<dabgpu_subch> &subch) {
@@ -529,6 +545,42 @@ bool ensembleDecoder::step() {
             }
         }
     }
+    if (NS && npk_) {
+        chk(dabgpu_pipe_packet(pipe_, (uint8_t *)pkb_.get(), (dabgpu_datagroup *)pkg_.get(), (dabgpu_packet_run *)pkr_.get(),
+                               (dabgpu_packet_info *)pki_.get()), "dabgpu_pipe_packet");
+        chk(dabgpu_pipe_sync(pipe_), "dabgpu_pipe_sync");
+        if (dg_cb_ || pq_cb_) {
+            // only what the run completed crosses PCIe: the run records, then per (stream,
+            // slot) its group records and its arena's used bytes
+            std::vector<dabgpu_packet_run> run((size_t)S * npk_);
+            std::vector<dabgpu_packet_info> info((size_t)S * 4 * F * npk_);
+            pkr_.download(run.data(), run.size() * sizeof(dabgpu_packet_run));
+            pki_.download(info.data(), info.size() * sizeof(dabgpu_packet_info));
+            std::vector<dabgpu_datagroup> groups;
+            std::vector<uint8_t> bytes;
+            for (int s = 0; s < S; s++) {
+                std::vector<int> slot;               // packet slot j of a stream is its j-th flagged entry
+                for (int k = 0; k < (int)tab_[s].size(); k++)
+                    if (tab_[s][k].flags & DABGPU_SUBCH_PACKET) slot.push_back(k);
+                for (int j = 0; j < (int)slot.size() && j < npk_; j++) {
+                    const size_t e = (size_t)s * npk_ + j;
+                    for (int c = 0; c < 4 * F && pq_cb_; c++) {
+                        const dabgpu_packet_info &i = info[((size_t)s * 4 * F + c) * npk_ + j];
+                        if (i.status == 0 && i.quality >= 0) pq_cb_(s, 4 * frames_done_[s] + c, slot[j], i.quality);
+                    }
+                    if (!dg_cb_ || run[e].n_groups <= 0) continue;
+                    groups.resize(run[e].n_groups);
+                    bytes.resize(std::max(1, run[e].n_bytes));
+                    chk(dabgpu_memcpy_d2h(thread_context(), groups.data(), (const dabgpu_datagroup *)pkg_.get() + e * pk_slots_,
+                                          groups.size() * sizeof(dabgpu_datagroup)), "dabgpu_memcpy_d2h");
+                    chk(dabgpu_memcpy_d2h(thread_context(), bytes.data(), (const uint8_t *)pkb_.get() + e * pk_arena_, run[e].n_bytes),
+                        "dabgpu_memcpy_d2h");
+                    for (const dabgpu_datagroup &g : groups)
+                        dg_cb_(s, 4 * frames_done_[s] + g.cif, slot[j], g, bytes.data() + g.offset, std::min(g.nbytes, pk_cap_));
+                }
+            }
+        }
+    }
     for (int s = 0; s < S; s++) {
         dabgpu_stream_state st;
         chk(dabgpu_pipe_state(pipe_, s, &st), "dabgpu_pipe_state");
@@ -537,7 +589,7 @@ bool ensembleDecoder::step() {
     // FIC first: a table parsed twice alike (two steps) and not yet applied is applied now
     for (int s = 0; s < S && cfg_.auto_layout; s++) {
         std::vector<dabgpu_subch> now;
-        for (const fib_subch &e : fibs_[s].subchannels(nullptr, pcm_cb_ != nullptr && nmp_ > 0))
+        for (const fib_subch &e : fibs_[s].subchannels(nullptr, pcm_cb_ != nullptr && nmp_ > 0, dg_cb_ != nullptr && npk_ > 0))
             now.push_back({e.startAddr, e.length, e.bitRate, e.protLevel, e.uepFlag, e.flags});
         auto same = [](const std::vector<dabgpu_subch> &x, const std::vector<dabgpu_subch> &y) {
             return x.size() == y.size() && (x.empty() || !std::memcmp(x.data(), y.data(), x.size() * sizeof(dabgpu_subch)));

@@ -477,6 +477,9 @@ public:
         // may hold (0: what subch needs)
         int max_subch = 0, max_bitrate = 0, max_dabplus = 0;
         int max_mp2 = 0;                     // layer II (DABGPU_SUBCH_MP2) entries likewise
+        // dabgpu_pipe_packet_caps: packet-mode (DABGPU_SUBCH_PACKET) entries a stream's table may
+        // hold (0: what subch flags) and the largest data group (0: DABGPU_PKT_GROUP_BYTES)
+        int max_packet = 0, max_group_bytes = 0;
         // FIC first: each stream's table follows its own FIG 0/1 and 0/2 (a fib_processor per
         // stream, fed its CRC-good FIBs).  At the end of a step() a stream's parsed table is
         // applied (set_subch) when it is non-empty, equals the one parsed at the end of the
@@ -501,6 +504,19 @@ public:
     // has ASCTy 0 are flagged when this callback is set before the table is applied.
     using pcm_cb = std::function<void(int stream, int64_t cif, int subch, const int16_t *pcm, int n_samples, int rate)>;
     void on_pcm(pcm_cb f) { pcm_cb_ = std::move(f); }
+    // MSC data groups of the packet-mode entries (DABGPU_SUBCH_PACKET, dabgpu_pipe_packet), where
+    // my_dataHandler->add_mscDatagroup stands in the reference (msc-datagroup.cpp:285, :304):
+    // one call per completed group, accepted or not, as bytes (the reference passes one bit per
+    // byte) with its parsed header; nbytes is what is stored, min(g.nbytes, max_group_bytes);
+    // cif is the CIF of the packet that completed it.  With auto_layout, sub-channels with a
+    // packet-mode component (not DSCTy 5 with the DG flag) are flagged when this callback is
+    // set before the table is applied.
+    using datagroup_cb = std::function<void(int stream, int64_t cif, int subch, const dabgpu_datagroup &g,
+                                            const uint8_t *bytes, int nbytes)>;
+    void on_datagroup(datagroup_cb f) { dg_cb_ = std::move(f); }
+    // show_mscErrors (msc-datagroup.cpp:250-254): 100 - crcErrors / 5 per 500 handled packets
+    using packet_quality_cb = std::function<void(int stream, int64_t cif, int subch, int value)>;
+    void on_packet_quality(packet_quality_cb f) { pq_cb_ = std::move(f); }
     // samples[s] -> n[s] cf32 samples of stream s (copied to HBM)
     void load(const std::vector<const DSPCOMPLEX *> &samples, const std::vector<int64_t> &n);
     // the streams as recorded: format DABGPU_IQ_S16 (.sdr PCM16 I/Q pairs) or DABGPU_IQ_U8
@@ -529,9 +545,12 @@ public:
 private:
     config cfg_;
     dabgpu_pipe *pipe_ = nullptr;
-    devbuf iq_, fic_, crc_, msc_, sf_, sfi_, pcm_, mp2i_;
-    int nmp_ = 0;
+    devbuf iq_, fic_, crc_, msc_, sf_, sfi_, pcm_, mp2i_, pkb_, pkg_, pkr_, pki_;
+    int nmp_ = 0, npk_ = 0, pk_cap_ = 0;
+    size_t pk_slots_ = 0, pk_arena_ = 0;
     pcm_cb pcm_cb_;
+    datagroup_cb dg_cb_;
+    packet_quality_cb pq_cb_;
     int64_t stride_ = 0;
     std::vector<int64_t> navail_;
     int msc_stride_ = 0, sf_stride_ = 0, ndp_ = 0, maxbits_ = 0, nsub_ = 0;

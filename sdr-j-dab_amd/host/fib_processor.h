@@ -96,7 +96,14 @@ public:
     // (FIG 0/2) on the sub-channel has ASCTy 63.  ids (optional) receives each entry's SubChId.
     // classic_audio: also flag DABGPU_SUBCH_MP2 (4) where such a component has ASCTy 0
     // (MPEG layer II, what the reference hands to mp2Processor).
-    std::vector<fib_subch> subchannels(std::vector<int> *ids = nullptr, bool classic_audio = false) const;
+    // packet_data: also flag DABGPU_SUBCH_PACKET (8) where a packet-mode component (TMid 3, FIG
+    // 0/2 + FIG 0/3) lies on the sub-channel, unless it has DSCTy 5 with the DG flag set
+    // (handleTDCAsyncstream: nothing to deliver).  A component counts once its FIG 0/3 has
+    // arrived, which is taken from DSCTy != 0: until then its sub-channel field still holds 0
+    // and would flag sub-channel 0; a component announced with DSCTy 0 (unspecified data) is
+    // therefore not flagged either.  The audio layers win on a conflict.
+    std::vector<fib_subch> subchannels(std::vector<int> *ids = nullptr, bool classic_audio = false,
+                                       bool packet_data = false) const;
 
     std::string ensembleName() const { return ensemble_; }
     std::vector<std::string> serviceLabels() const;
