@@ -318,15 +318,24 @@ int dabgpu_fic_decode_frames(dabgpu_ctx *ctx, const int16_t *softbits_d, const i
 /* uep_/eep_deconvolve::deconvolve + energy dispersal (deconvolve.cpp:172-237,
  * 325-366; dab-concurrent.cpp:183-190; no dispersal with DABGPU_SUBCH_RAW) for n_cw codewords whose
  * fragmentSize = length*64 soft bits are given contiguous (already
- * time-de-interleaved), one subchannel description per codeword.
- * Output bits_d[n_cw][24*max_bitRate] (row stride out_stride bytes). */
+ * time-de-interleaved), one subchannel description per codeword: codeword i reads
+ * frag_d + i*frag_stride (frag_stride >= every fragmentSize, DABGPU_E_ARG otherwise).
+ * Output: codeword i's 24*bitRate bits at bits_d + i*out_stride, one per byte (out_stride
+ * in bytes, >= the longest codeword's 24*bitRate, DABGPU_E_ARG otherwise; any alignment
+ * of bits_d and out_stride).  Only those bytes are written: the rest of a row -- the gap
+ * up to out_stride, and behind a codeword shorter than the longest -- and everything
+ * outside the rows is left as it was.
+ * bitRate: whatever the protection defines, up to 1824 kbit/s (EEP 4-B, 855 CU, the
+ * longest subchannel a CIF's 864 CUs hold; EEP 4-A ends at 1728): the energy-dispersal
+ * sequence runs on for 24*bitRate bits as dab-concurrent.cpp:183-190 builds it.
+ * DABGPU_E_UNSUP above that, and for a protection the reference does not define. */
+int dabgpu_msc_deconvolve(dabgpu_ctx *ctx, const int16_t *frag_d, int64_t frag_stride,
+                          const dabgpu_subch *subch_h, int n_cw, uint8_t *bits_d, int64_t out_stride);
+
 /* reedSolomon::dec(rsIn, rsOut, 135) batched (reed-solomon.cpp:129-141; the
  * RS(255,245) code of mp4processor.cpp:74 shortened to (120,110)): n codewords of
  * 120 bytes -> 110 corrected bytes each; ret_d[i] = symbols corrected or -1. */
 int dabgpu_rs_decode(dabgpu_ctx *ctx, const uint8_t *in_d, int n, uint8_t *out_d, int16_t *ret_d);
-
-int dabgpu_msc_deconvolve(dabgpu_ctx *ctx, const int16_t *frag_d, int64_t frag_stride,
-                          const dabgpu_subch *subch_h, int n_cw, uint8_t *bits_d, int64_t out_stride);
 
 /* mp2Processor::mp2decodeFrame batched (mp2processor.cpp:365-568; the counterpart of
  * dabgpu_rs_decode): n_chains independent decoders, each taking chain_len frames in order.

@@ -89,6 +89,14 @@ inline __host__ __device__ int32_t dec_chunks(int nbits) { return (nbits + 6 + D
 inline __host__ __device__ int64_t dec_bytes(int n_cw, int nbits) {
     return (int64_t)dec_chunks(nbits) * dec_rows(n_cw) * 64 * 4;
 }
+// The energy-dispersal sequence on the device (fic-handler.cpp:100-108; dab-concurrent.cpp:
+// 183-190 builds it for 24 * bitRate bits), 32 bits per word.  It covers the longest
+// subchannel the 864 CUs of a CIF hold: EEP 4-B at 1824 kbit/s (855 CU; EEP 4-A ends at
+// 1728 kbit/s, 864 CU).  A traceback reads the words of its chunks' bits, whole chunks, and
+// one word beyond (tb_body's hi word): dabgpu_msc_deconvolve refuses a bitRate above this.
+constexpr int MSC_MAX_BITRATE = 1824;
+constexpr int PRBS_WORDS =
+    ((24 * MSC_MAX_BITRATE + 6 + DEC_WORD_STEPS - 1) / DEC_WORD_STEPS * DEC_WORD_STEPS + 31) / 32 + 1;
 // first word of (row, chunk 0); chunk c of the row is 4096 words further on
 inline __host__ __device__ int64_t dec_word_index(int64_t row, int32_t nch) {
     return ((row >> 6) * nch * 64 + (row & 63)) * 64;

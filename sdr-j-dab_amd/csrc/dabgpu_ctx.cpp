@@ -120,11 +120,12 @@ struct HostTables {
             float re = ac - bd, im = ad + bc;
             refarg[i] = atan2f(im, re);
         }
-        // energy dispersal (fic-handler.cpp:100-108), 32768 bits
-        prbs_words.assign(1024, 0u);
+        // energy dispersal (fic-handler.cpp:100-108; dab-concurrent.cpp:183-190 runs the same
+        // register for 24 * bitRate bits): PRBS_WORDS words, the longest subchannel's
+        prbs_words.assign(PRBS_WORDS, 0u);
         uint8_t sr[9];
         memset(sr, 1, 9);
-        for (int i = 0; i < 32768; i++) {
+        for (int i = 0; i < 32 * PRBS_WORDS; i++) {
             uint8_t b = sr[8] ^ sr[4];
             for (int j = 8; j > 0; j--) sr[j] = sr[j - 1];
             sr[0] = b;
@@ -759,6 +760,8 @@ int dabgpu_msc_deconvolve(dabgpu_ctx *c, const int16_t *frag, int64_t frag_strid
     for (int i = 0; i < n_cw; i++) {
         if ((sub[i].flags & DABGPU_SUBCH_RAW) != raw)
             return fail(DABGPU_E_ARG, "DABGPU_SUBCH_RAW must be the same for every codeword of a call");
+        if (sub[i].bitRate > MSC_MAX_BITRATE)          // beyond the energy-dispersal table (and any CIF)
+            return fail(DABGPU_E_UNSUP, "subchannel %d: bitRate %d above %d kbit/s", i, sub[i].bitRate, MSC_MAX_BITRATE);
         Profile p;
         int rc = make_profile(sub[i], p);
         if (rc) return fail(DABGPU_E_UNSUP, "subchannel %d: protection (uep=%d, level 0%o, %d kbps) undefined",

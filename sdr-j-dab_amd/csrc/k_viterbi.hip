@@ -747,7 +747,7 @@ constexpr int TB_RING = TB_RING_DEPTH;      // decision chunks in the register r
 constexpr int TB_WORDS = TB_CW * TB_ROW;    // one chunk of a wave's codewords
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr int TB_GROUP = 8;                 // chunks per output flush (240 bits per codeword)
-constexpr int TB_PRBS = 1024;              // PRBS words (fic-handler.cpp:100-108: 32768 bits)
+constexpr int TB_PRBS = PRBS_WORDS;         // PRBS words the context holds (dab_kernels.h)
 __device__ __forceinline__ void tb_load(u32x4 (&r)[TB_LD], const uint32_t *blk, int lane) {
     const u32x4 *q = (const u32x4 *)blk;
 #pragma unroll
@@ -768,6 +768,8 @@ __device__ __forceinline__ void tb_stage(uint32_t *lds, const u32x4 (&r)[TB_LD],
 
 // PRBS words a traceback of nch chunks reads (LDS sized by the launch)
 __host__ __device__ inline int tb_prbs_words(int nch) { return min(TB_PRBS, (nch * WS + WS) / 32 + 2); }
+// the last chunk of the longest codeword reads words t0 >> 5 and (t0 >> 5) + 1
+static_assert(((((24 * MSC_MAX_BITRATE + 6 + WS - 1) / WS - 1) * WS) >> 5) + 1 < TB_PRBS, "PRBS table too short");
 
 template <int KIND>
 __device__ __forceinline__ void tb_body(const VitJob &J, int blk, uint32_t *stage, uint32_t *prbs_l) {

@@ -35,6 +35,7 @@ class Subch(C.Structure):
 
 
 SUBCH_DABPLUS = 1   # Subch.flags: feed the DAB+ superframe layer
+SUBCH_RAW = 2       # Subch.flags (msc_deconvolve): no energy dispersal
 SUBCH_MP2 = 4       # Subch.flags: feed the MPEG layer II layer (Pipeline.mp2)
 MP2_STATE_BYTES = 3840   # DABGPU_MP2_STATE_BYTES: a layer II decoder's carried state
 MP2_INFO_DTYPE = np.dtype([("status", "<i4"), ("sample_rate", "<i4"), ("frame_bytes", "<i4")])   # dabgpu_mp2_info
@@ -309,7 +310,11 @@ class DevBuf:
         return out
 
     def zero(self) -> "DevBuf":
-        _chk(lib().dabgpu_memset_d(self.ctx.h, self.ptr, 0, self.nbytes), "memset")
+        return self.fill(0)
+
+    def fill(self, value: int) -> "DevBuf":
+        """every byte := value (on the context's stream, ahead of the operators that follow)"""
+        _chk(lib().dabgpu_memset_d(self.ctx.h, self.ptr, int(value) & 0xFF, self.nbytes), "memset")
         return self
 
     def free(self) -> None:
@@ -422,46 +427,108 @@ class Context:
         self.close()
 
     # ---- operators mirroring the reference interfaces -------------------------
-    def viterbi(self, soft: np.ndarray, nbits: int) -> np.ndarray:
-        """viterbi::deconvolve (viterbi.cpp:225-242) for each row of soft [n, 4*(nbits+6)]."""
+    @staticmethod
+    def _out_at(out: Optional[DevBuf], out_offset: int, extent: int) -> C.c_void_p:
+        """the device address of byte out_offset of a caller's output buffer, of which the
+        operator may write [out_offset, out_offset + extent)"""
+        if out_offset < 0 or out_offset + extent > out.nbytes:
+            raise DabError(f"output of {extent} bytes at offset {out_offset} does not fit the {out.nbytes}-byte buffer")
+        return C.c_void_p(out.ptr.value + out_offset)
+
+    def viterbi(self, soft: np.ndarray, nbits: int, out: Optional[DevBuf] = None, out_offset: int = 0) -> np.ndarray:
+        """viterbi::deconvolve (viterbi.cpp:225-242) for each row of soft [n, 4*(nbits+6)].
+        out: the caller's buffer, which receives the rows from byte out_offset on (and stays
+        the caller's: download all of it to see what else was written); else a fresh one."""
         soft = np.ascontiguousarray(soft, dtype=np.int16).reshape(-1, 4 * (nbits + 6))
         n = soft.shape[0]
-        din, dout = self.put(soft), self.buf(n * nbits)
+        din = self.put(soft) if n else self.buf(16)
+        dout = self.buf(n * nbits) if out is None else None
         try:
-            _chk(lib().dabgpu_viterbi(self.h, din.ptr, n, nbits, dout.ptr), "dabgpu_viterbi")
-            r = dout.download(np.uint8, (n, nbits))
+            po = dout.ptr if out is None else self._out_at(out, out_offset, n * nbits)
+            _chk(lib().dabgpu_viterbi(self.h, din.ptr, n, nbits, po), "dabgpu_viterbi")
+            if n == 0:
+                self.sync()
+                r = np.zeros((0, nbits), np.uint8)
+            elif out is None:
+                r = dout.download(np.uint8, (n, nbits))
+            else:
+                r = out.download(np.uint8, out.nbytes)[out_offset:out_offset + n * nbits].reshape(n, nbits)
             self.check()
             return r
         finally:
-            din.free(); dout.free()
+            din.free()
+            if dout is not None:
+                dout.free()
 
-    def fic_process(self, blocks: np.ndarray):
+    def fic_process(self, blocks: np.ndarray, out: Optional[DevBuf] = None, out_offset: int = 0):
         """ficHandler::process_ficInput (fic-handler.cpp:241-321) for [n, 2304] soft bits.
-        Returns (bits [n,768] after energy dispersal and the CRC check's inversion, crc_ok [n,3])."""
+        Returns (bits [n,768] after energy dispersal and the CRC check's inversion, crc_ok [n,3]).
+        out: the caller's buffer for the bits, from byte out_offset on (a multiple of 4: the
+        CRC check reads them as words); else a fresh one."""
         blocks = np.ascontiguousarray(blocks, dtype=np.int16).reshape(-1, 2304)
         n = blocks.shape[0]
-        din, db, dc = self.put(blocks), self.buf(n * 768), self.buf(n * 3)
+        if out is not None and out_offset % 4:
+            raise DabError("fic_process: out_offset must be a multiple of 4")
+        din, dc = self.put(blocks), self.buf(n * 3)
+        db = self.buf(n * 768) if out is None else None
         try:
-            _chk(lib().dabgpu_fic_decode(self.h, din.ptr, n, db.ptr, dc.ptr), "dabgpu_fic_decode")
-            return db.download(np.uint8, (n, 768)), dc.download(np.uint8, (n, 3))
+            pb = db.ptr if out is None else self._out_at(out, out_offset, n * 768)
+            _chk(lib().dabgpu_fic_decode(self.h, din.ptr, n, pb, dc.ptr), "dabgpu_fic_decode")
+            if out is None:
+                bits = db.download(np.uint8, (n, 768))
+            else:
+                bits = out.download(np.uint8, out.nbytes)[out_offset:out_offset + n * 768].reshape(n, 768)
+            return bits, dc.download(np.uint8, (n, 3))
         finally:
-            din.free(); db.free(); dc.free()
+            din.free(); dc.free()
+            if db is not None:
+                db.free()
 
-    def msc_deconvolve(self, frags: np.ndarray, subch: Sequence[Subch]) -> list:
+    def fic_decode_frames(self, soft: DevBuf, slots: Sequence[int]):
+        """dabgpu_fic_decode_frames: the four FIC blocks of each frame slots[i] of a demod
+        soft-bit buffer (int16 [slot][75][3072] on the device; the first 9216 values of a slot
+        are read).  Returns (bits [n, 4, 768], crc_ok [n, 12]) as fic_process does per block."""
+        sl = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        n = len(sl)
+        if n and (sl.min() < 0 or 2 * (int(sl.max()) + 1) * NSYM * SYMBITS > soft.nbytes):
+            raise DabError("fic_decode_frames: a slot outside the soft-bit buffer")
+        db, dc = self.buf(max(1, n * 4 * 768)), self.buf(max(1, n * 12))
+        try:
+            _chk(lib().dabgpu_fic_decode_frames(self.h, soft.ptr, _p(sl), n, db.ptr, dc.ptr), "dabgpu_fic_decode_frames")
+            if n == 0:
+                return np.zeros((0, 4, 768), np.uint8), np.zeros((0, 12), np.uint8)
+            return db.download(np.uint8, (n, 4, 768)), dc.download(np.uint8, (n, 12))
+        finally:
+            db.free(); dc.free()
+
+    def msc_deconvolve(self, frags: np.ndarray, subch: Sequence[Subch], out: Optional[DevBuf] = None,
+                       out_offset: int = 0, out_stride: Optional[int] = None) -> list:
         """uep_/eep_deconvolve::deconvolve + energy dispersal (deconvolve.cpp:172,325;
-        dab-concurrent.cpp:183-190): one already de-interleaved fragment per row."""
+        dab-concurrent.cpp:183-190): one already de-interleaved fragment per row.
+        out_stride: bytes from one codeword's bits to the next's (default: the longest
+        codeword's 24*bitRate); out: the caller's buffer, row i at byte out_offset +
+        i*out_stride (it stays the caller's); else a fresh one."""
         frags = np.ascontiguousarray(frags, dtype=np.int16)
         n, stride = frags.shape
         arr = (Subch * n)(*subch)
-        maxbits = max(24 * s.bitRate for s in subch)
-        din, dout = self.put(frags), self.buf(n * maxbits)
+        nb = [24 * s.bitRate for s in subch]
+        ostride = max(nb) if out_stride is None else int(out_stride)
+        extent = max(i * ostride + max(nb[i], 0) for i in range(n))     # the last byte any row may take
+        din = self.put(frags)
+        dout = self.buf(max(extent, n * max(nb))) if out is None else None
         try:
-            _chk(lib().dabgpu_msc_deconvolve(self.h, din.ptr, stride, C.cast(arr, C.c_void_p), n, dout.ptr, maxbits),
+            po = dout.ptr if out is None else self._out_at(out, out_offset, extent)
+            _chk(lib().dabgpu_msc_deconvolve(self.h, din.ptr, stride, C.cast(arr, C.c_void_p), n, po, ostride),
                  "dabgpu_msc_deconvolve")
-            out = dout.download(np.uint8, (n, maxbits))
-            return [out[i, :24 * subch[i].bitRate] for i in range(n)]
+            if out is None:
+                flat = dout.download(np.uint8, dout.nbytes)
+            else:
+                flat = out.download(np.uint8, out.nbytes)[out_offset:]
+            return [flat[i * ostride:i * ostride + nb[i]] for i in range(n)]
         finally:
-            din.free(); dout.free()
+            din.free()
+            if dout is not None:
+                dout.free()
 
     def rs_decode(self, cw: np.ndarray):
         """reedSolomon::dec(rsIn, rsOut, 135) per row (reed-solomon.cpp:129-141):
