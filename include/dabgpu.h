@@ -126,6 +126,74 @@ typedef struct {
 #define DABGPU_PKT_ARENA_BYTES(n_frames, max_bitrate, max_group_bytes) \
     ((max_group_bytes) + 4 * (n_frames) * ((max_bitrate) / 8) * 127)
 
+#define DABGPU_SUBCH_MOT     16  /* feed the packet entry's data groups to the MOT layer (dabgpu_pipe_mot);
+                                    only together with DABGPU_SUBCH_PACKET (DABGPU_E_ARG otherwise) */
+/* One object motHandler delivered (mot-data.cpp:315-346): a slide where show_slide emits
+ * the_picture, a file where handleComplete fopens, or an EPG object (contentType 7:
+ * handle_epgTopElement returns at once, :355 -- recorded, no bytes). */
+#define DABGPU_MOT_NAME_BYTES 128
+typedef struct {
+    int32_t group;          /* index, in the run's groups, of the group that completed the object */
+    int32_t cif;            /* that group's cif */
+    int32_t offset;         /* of the body in the (stream, slot)'s output arena, a multiple of 16 */
+    int32_t nbytes;         /* bodySize; 0 for DABGPU_MOT_EPG and with DABGPU_MOT_OVERFLOW */
+    uint16_t transportId;
+    uint8_t contentType;
+    uint8_t kind;           /* DABGPU_MOT_SLIDE, DABGPU_MOT_EPG or DABGPU_MOT_FILE */
+    uint16_t contentsubType;
+    uint16_t flags;         /* DABGPU_MOT_OVERFLOW */
+    int32_t name_len;       /* the name's full length; name holds its first DABGPU_MOT_NAME_BYTES bytes */
+    uint8_t name[DABGPU_MOT_NAME_BYTES];
+} dabgpu_mot_object;
+#define DABGPU_MOT_SLIDE 1
+#define DABGPU_MOT_EPG   2
+#define DABGPU_MOT_FILE  3
+#define DABGPU_MOT_TOO_LARGE 1      /* dabgpu_mot_entry.flags: bodySize above max_body_bytes */
+#define DABGPU_MOT_OVERFLOW  2      /* dabgpu_mot_object.flags: the body did not fit the output arena */
+/* One (stream, MOT slot) after a run */
+typedef struct {
+    int32_t n_objects;      /* objects delivered in the run */
+    int32_t n_bytes;        /* output arena bytes used */
+    int32_t malformed;      /* groups dropped by rule 1 (or whose record points outside its arena) */
+    int32_t bad_segment;    /* groups dropped by rule 2 */
+    int32_t other_types;    /* groups that are neither a header (type 3, segment 0) nor type 4 (rule 6) */
+    int32_t entries;        /* table entries in use after the run */
+    int32_t reserved[2];
+} dabgpu_mot_run;
+/* A motHandler's carried state: this head, DABGPU_MOT_ENTRIES entries, then the entries'
+ * bodies, each in (max_body_bytes rounded up to 16) bytes.  All zero is a new motHandler. */
+#define DABGPU_MOT_ENTRIES 16
+typedef struct {
+    int32_t created;        /* entries made so far: the reference's ordernumber - 1 */
+    int32_t old_slide;      /* 1 once a slide has been shown (old_slide != NULL) */
+    int32_t reserved[2];
+} dabgpu_mot_head;
+typedef struct {            /* a motElement (mot-data.h:33-44) */
+    int32_t order;          /* ordernumber; 0: free (the reference's -1) */
+    int32_t transportId;
+    int32_t bodySize;
+    int32_t segmentSize;    /* -1 until a segment that is not the last latched it */
+    int32_t numofSegments;  /* -1 until the last segment set it */
+    int32_t contentType, contentsubType;
+    int32_t flags;          /* DABGPU_MOT_TOO_LARGE */
+    uint32_t marked[4];     /* bit n: segment n is in (as in the reference, newEntry leaves them) */
+    int32_t name_len;
+    int32_t reserved;
+    uint8_t name[DABGPU_MOT_NAME_BYTES];
+} dabgpu_mot_entry;
+#define DABGPU_MOT_BODY_BYTES 65536 /* the default max_body_bytes */
+/* Object slots and output arena bytes per (stream, MOT slot): a run completes at most one
+ * object per group; the arena holds one carried body plus what a run's payload can complete,
+ * each body at a multiple of 16 (127 payload bytes a packet and up to 15 bytes of alignment a
+ * group; the size stays a multiple of 16).  A run can complete more only when several entries were
+ * each left one segment short on purpose -- a hostile stream: such an object is recorded with
+ * DABGPU_MOT_OVERFLOW and no bytes. */
+#define DABGPU_MOT_OBJECT_SLOTS(n_frames, max_bitrate) DABGPU_PKT_GROUP_SLOTS(n_frames, max_bitrate)
+#define DABGPU_MOT_ARENA_FOR(group_slots, max_body_bytes) \
+    ((((max_body_bytes) + 15) / 16) * 16 + (group_slots) * 144)
+#define DABGPU_MOT_ARENA_BYTES(n_frames, max_bitrate, max_body_bytes) \
+    DABGPU_MOT_ARENA_FOR(DABGPU_PKT_GROUP_SLOTS(n_frames, max_bitrate), max_body_bytes)
+
 /* One CIF of one classic-audio subchannel through mp2Processor::addtoFrame
  * (mp2processor.cpp:572-617) and, when a frame completed in it, mp2decodeFrame (:365-568). */
 typedef struct {
@@ -361,6 +429,61 @@ int dabgpu_rs_decode(dabgpu_ctx *ctx, const uint8_t *in_d, int n, uint8_t *out_d
 int dabgpu_mp2_decode(dabgpu_ctx *ctx, const uint8_t *frames_d, int64_t frame_stride, int n_chains, int chain_len,
                       void *state_d, int16_t *pcm_d, int32_t *ret_d);
 
+/* motHandler::process_mscGroup in header mode (mot-data.cpp:679-728) batched: n_slots
+ * independent motHandlers, each taking the groups of one (stream, packet slot) of a
+ * dabgpu_pipe_packet call, or buffers in that layout, in completion order.  Fed are the groups
+ * mot_databuilder::add_mscDatagroup passes on (mot-databuilder.cpp:84-95): DABGPU_DG_ACCEPTED
+ * and DABGPU_DG_TRANSPORT; data is the group's bytes from data_offset, data_nbytes of them.
+ *   state_d    [n_slots][dabgpu_mot_state_bytes(max_body_bytes)], all zero for a new
+ *              motHandler, updated in place (head, entries, bodies: see dabgpu_mot_head)
+ *   groups_d   [n_slots][group_slots], run_d [n_slots] (n_groups is read), bytes_d
+ *              [n_slots][arena_bytes]
+ *   objects_d  [n_slots][group_slots], the first mot_run.n_objects written
+ *   out_d      [n_slots][out_arena_bytes]: the bodies, each as it was when its object completed
+ *              (later groups of the run may rewrite the entry)
+ *   mot_run_d  [n_slots]
+ * Kept bit for bit from the reference:
+ *   - segmentSize = (d[0] & 0x1F) << 8 | d[1]; the header size exactly as process_mscGroup
+ *     computes it, (d[5] & 0x0F) << 9 | d[6] | d[7] >> 7 (:687-689 -- d[6] is not shifted,
+ *     unlike get_dirEntry :216-218): it ends the parameter walk and is where the body bytes of
+ *     a header segment that is not the last begin (:128-132);
+ *   - contentType, contentsubType from segment[5..6], the PLI walk (:62-111); the name is the
+ *     bytes of every parameter 12 after its first, appended (:104-108);
+ *   - a header whose transport id has an entry is ignored (:113-114); a new entry takes the
+ *     first free one, else the one with the lowest ordernumber (:621-655), and inherits its
+ *     marks (newEntry does not clear them);
+ *   - processSegment (:278-312): unknown transport id and marked segment ignored, segmentSize
+ *     latched by the first segment that is not the last, a last segment while it is -1
+ *     dropped, n * segmentSize + size > bodySize dropped, numofSegments set by the last one;
+ *   - completion (:315-346): contentType 2 is a slide, and every slide completion after the
+ *     first ever shown clears the completing entry's marks (the first keeps them, so its
+ *     repeat shows nothing); contentType 7 completes and delivers nothing; anything else is a
+ *     file, name and body.
+ * Where the reference is undefined or unbounded:
+ *   1. bytes past a group's data field read 0; a group with data_nbytes < 2 or segmentSize + 2
+ *      > data_nbytes is dropped and counted (malformed);
+ *   2. a segment number >= 100 is dropped and counted (the reference writes past marked[100]);
+ *   3. sizes are int32 (newEntry's int16_t size wraps from 32768 bytes on: the reference never
+ *      completes such an object); a body above max_body_bytes gets an entry flagged
+ *      DABGPU_MOT_TOO_LARGE whose segments are ignored;
+ *   4. body bytes no segment wrote read 0 (newEntry clears the body); no write leaves
+ *      [0, bodySize): a segment whose size is negative (segmentSize - headerSize < 0) is dropped;
+ *   5. names keep their first DABGPU_MOT_NAME_BYTES bytes, name_len the full length;
+ *      ordernumber is int32 and the entry replaced is the one with the least;
+ *   6. directory mode is out of scope: group type 6, and every group that is neither a header
+ *      (type 3, segment 0) nor type 4, is counted (other_types) and otherwise ignored, so
+ *      theDirectory stays NULL.  (The reference analyses a directory before it is complete,
+ *      :182-189 with num_dirSegments == -1, and getHandle :602-607 then reads ordernumbers
+ *      nothing initialised: there is no defined behaviour to equal.)
+ * max_body_bytes 0 means DABGPU_MOT_BODY_BYTES; at most 1 << 24.  DABGPU_E_ARG for a bad
+ * size: group_slots < 0, arena sizes outside [0, 2^31), out_arena_bytes below
+ * DABGPU_MOT_ARENA_FOR(0, max_body_bytes).  Asynchronous on the context stream. */
+size_t dabgpu_mot_state_bytes(int max_body_bytes);
+int dabgpu_mot_groups(dabgpu_ctx *ctx, void *state_d, int n_slots, int max_body_bytes,
+                      const dabgpu_datagroup *groups_d, int group_slots, const uint8_t *bytes_d, int64_t arena_bytes,
+                      const dabgpu_packet_run *run_d, dabgpu_mot_object *objects_d, uint8_t *out_d,
+                      int64_t out_arena_bytes, dabgpu_mot_run *mot_run_d);
+
 /* ---- streaming pipeline (ofdmProcessor::run + ficHandler + mscHandler) ---
  * n_streams independent ensembles; each call decodes n_frames frames per
  * stream.  Sync, AFC, DQPSK references and the 16-CIF time de-interleaver
@@ -441,9 +564,12 @@ int dabgpu_pipe_create_caps(dabgpu_ctx *ctx, const dabgpu_pipe_cfg *cfg, const d
  * Validates as create does: DABGPU_E_UNSUP for an undefined protection or a bad DAB+
  * bitRate, DABGPU_E_ARG for an entry outside its CUs, for n > max_subch, a bitRate above
  * max_bitrate, more DAB+ entries than max_dabplus, more layer II entries than max_mp2, more
- * packet-mode entries than dabgpu_pipe_packet_caps allows or an entry flagged for two layers;
+ * packet-mode entries than dabgpu_pipe_packet_caps allows, more MOT entries than
+ * dabgpu_pipe_mot_caps allows, an entry flagged DABGPU_SUBCH_MOT without DABGPU_SUBCH_PACKET or
+ * an entry flagged for two layers;
  * DABGPU_E_UNSUP for a packet-mode bitRate that is no multiple of 8; on any error the table
- * is unchanged.  (A packet-mode entry that is not unchanged is a new mscDatagroup.)
+ * is unchanged.  (A packet-mode entry that is not unchanged is a new mscDatagroup, and a new
+ * motHandler when it is flagged DABGPU_SUBCH_MOT; an unchanged one keeps both.)
  * Waits for everything the pipeline has enqueued (as dabgpu_pipe_set_profiling): call
  * dabgpu_pipe_dabplus / dabgpu_pipe_mp2 / dabgpu_pipe_packet for the last run before it (the
  * layers refuse a run decoded under the old table: its rows are not the new slots').
@@ -553,8 +679,29 @@ int dabgpu_pipe_packet(dabgpu_pipe *p, uint8_t *bytes_d, dabgpu_datagroup *group
  * launched.  Between runs; waits for everything enqueued, as dabgpu_pipe_set_subch.  The
  * state of the existing entries is kept (a series in flight longer than a smaller
  * max_group_bytes keeps its first bytes).  DABGPU_E_ARG for negative values, max_packet >
- * max_subch or fewer slots than an applied table flags. */
+ * max_subch, fewer slots than an applied table flags, fewer than the MOT layer holds
+ * (dabgpu_pipe_mot_caps first) or, with a MOT layer, a packet arena of 2 GiB and more. */
 int dabgpu_pipe_packet_caps(dabgpu_pipe *p, int max_packet, int max_group_bytes);
+/* MOT layer for the groups of the run's dabgpu_pipe_packet call (call once per run, after
+ * it): dabgpu_mot_groups for every entry flagged DABGPU_SUBCH_PACKET | DABGPU_SUBCH_MOT, MOT
+ * slot j of a stream being its j-th such entry.  bytes_d, groups_d and run_d of that packet
+ * call are read (keep them alive until the run's work is done) and never written.  The
+ * motHandlers are carried across runs; dabgpu_pipe_set_subch keeps the one of an unchanged
+ * entry and gives every other entry a new one.  Outputs (device):
+ *   bytes_d   [n_streams][max_mot][DABGPU_MOT_ARENA_BYTES(n_frames, max_bitrate, max_body_bytes)]
+ *   objects_d [n_streams][max_mot][DABGPU_MOT_OBJECT_SLOTS(n_frames, max_bitrate)]
+ *   run_d     [n_streams][max_mot]
+ * Runs on the run's back-end stream behind the packet layer.  DABGPU_E_STATE without a layer
+ * (max_mot == 0), without a dabgpu_pipe_packet call for the run, or on a second call. */
+int dabgpu_pipe_mot(dabgpu_pipe *p, uint8_t *bytes_d, dabgpu_mot_object *objects_d, dabgpu_mot_run *run_d);
+/* Size the MOT layer: max_mot slots per stream (<= max_packet), bodies of at most
+ * max_body_bytes (0: DABGPU_MOT_BODY_BYTES).  Both create calls start with the number of
+ * flagged entries of their table and the default body size; with max_mot == 0 nothing is
+ * allocated or launched.  Between runs; waits for everything enqueued.  The state of the
+ * slots both sizes hold is kept (an entry whose body no longer fits becomes
+ * DABGPU_MOT_TOO_LARGE).  DABGPU_E_ARG for negative values, max_mot > max_packet,
+ * max_body_bytes > 1 << 24 or fewer slots than an applied table flags. */
+int dabgpu_pipe_mot_caps(dabgpu_pipe *p, int max_mot, int max_body_bytes);
 /* Compact superframe bytes for the following dabgpu_pipe_dabplus calls (on = 1): only the
  * superframes that complete in the run are stored, per (stream, DAB+ subchannel) in CIF
  * order -- sf_bytes_d [n_streams][n_dabplus][DABGPU_SF_SLOTS(n_frames)][sf_stride], the

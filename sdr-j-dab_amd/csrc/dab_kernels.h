@@ -278,6 +278,32 @@ struct PkJob {
     dabgpu_packet_info *info;       // [S][ncif][npk]
 };
 
+// MOT layer (k_mot.hip): n_slots motHandlers over the groups of a packet-layer pass
+constexpr int MOT_TABLE_BYTES = (int)(sizeof(dabgpu_mot_head) + DABGPU_MOT_ENTRIES * sizeof(dabgpu_mot_entry));
+static_assert(sizeof(dabgpu_mot_head) == 16 && sizeof(dabgpu_mot_entry) == 184 && sizeof(dabgpu_mot_object) == 156 &&
+                  sizeof(dabgpu_mot_run) == 32 && MOT_TABLE_BYTES % 16 == 0,
+              "the MOT records are read as bytes by the bindings");
+struct MotJob {
+    int32_t n_slots;
+    int32_t max_body;               // max_body_bytes
+    int32_t body_cap;               // max_body rounded up to 16: an entry's body bytes in the state
+    int64_t state_bytes;            // MOT_TABLE_BYTES + DABGPU_MOT_ENTRIES * body_cap
+    uint8_t *state;                 // [n_slots][state_bytes]
+    const int32_t *src;             // optional [n_slots]: the packet slot (row of groups / bytes / run) a MOT
+                                    //   slot reads, -1: absent; NULL: slot i reads row i
+    const dabgpu_datagroup *groups; // [rows][gslots]
+    int32_t gslots;
+    const uint8_t *bytes;           // [rows][arena]
+    int64_t arena;                  // < 2^31
+    const dabgpu_packet_run *run;   // [rows]
+    dabgpu_mot_object *objects;     // [n_slots][gslots]
+    uint8_t *out;                   // [n_slots][out_arena]
+    int64_t out_arena;              // < 2^31
+    dabgpu_mot_run *mot_run;        // [n_slots]
+    int4 *ops;                      // [n_slots][2 * gslots] the pass's copy list: x kind, y source, z destination, w bytes
+    int32_t *nops;                  // [n_slots]
+};
+
 // iq: samples in format fmt (DABGPU_IQ_*); frame descriptors count samples
 hipError_t launch_prs_sync(hipStream_t st, const void *iq, int fmt, const dabgpu_frame *fr, int n, const OfdmTables &T,
                            int level, int32_t *si, float *mx, float *sm, bool general);
@@ -313,5 +339,6 @@ hipError_t launch_rs(hipStream_t st, const uint8_t *in, int n, const uint8_t *ta
 hipError_t launch_mp2_decode(hipStream_t st, const Mp2Job &job);
 hipError_t launch_mp2_sync(hipStream_t st, const Mp2SyncJob &job);
 hipError_t launch_packet(hipStream_t st, const PkJob &job);
+hipError_t launch_mot(hipStream_t st, const MotJob &job);
 
 }  // namespace dab

@@ -750,6 +750,49 @@ int dabgpu_mp2_decode(dabgpu_ctx *c, const uint8_t *frames, int64_t frame_stride
     return 0;
 }
 
+size_t dabgpu_mot_state_bytes(int max_body_bytes) {
+    if (max_body_bytes < 0 || max_body_bytes > (1 << 24)) return 0;
+    const size_t cap = ((size_t)(max_body_bytes ? max_body_bytes : DABGPU_MOT_BODY_BYTES) + 15) / 16 * 16;
+    return MOT_TABLE_BYTES + DABGPU_MOT_ENTRIES * cap;
+}
+
+int dabgpu_mot_groups(dabgpu_ctx *c, void *state, int n_slots, int max_body_bytes, const dabgpu_datagroup *groups,
+                      int group_slots, const uint8_t *bytes, int64_t arena_bytes, const dabgpu_packet_run *run,
+                      dabgpu_mot_object *objects, uint8_t *out, int64_t out_arena_bytes, dabgpu_mot_run *mot_run) {
+    if (!c || !state || !groups || !bytes || !run || !objects || !out || !mot_run || n_slots < 0 || group_slots < 0)
+        return fail(DABGPU_E_ARG, "bad args");
+    if (max_body_bytes < 0 || max_body_bytes > (1 << 24)) return fail(DABGPU_E_ARG, "max_body_bytes %d", max_body_bytes);
+    const int body = max_body_bytes ? max_body_bytes : DABGPU_MOT_BODY_BYTES;
+    if (arena_bytes < 0 || arena_bytes > 0x7FFFFFFF || out_arena_bytes > 0x7FFFFFFF || (out_arena_bytes & 15) ||
+        out_arena_bytes < DABGPU_MOT_ARENA_FOR(0, body))
+        return fail(DABGPU_E_ARG, "arena sizes %lld / %lld", (long long)arena_bytes, (long long)out_arena_bytes);
+    if (((uintptr_t)state | (uintptr_t)out) & 15) return fail(DABGPU_E_ARG, "state_d and out_d must be 16-byte aligned");
+    if (!n_slots) return 0;
+    MotJob J;
+    memset(&J, 0, sizeof J);
+    J.n_slots = n_slots;
+    J.max_body = body;
+    J.body_cap = (body + 15) / 16 * 16;
+    J.state_bytes = (int64_t)dabgpu_mot_state_bytes(body);
+    J.state = (uint8_t *)state;
+    J.groups = groups;
+    J.gslots = group_slots;
+    J.bytes = bytes;
+    J.arena = arena_bytes;
+    J.run = run;
+    J.objects = objects;
+    J.out = out;
+    J.out_arena = out_arena_bytes;
+    J.mot_run = mot_run;
+    void *w = nullptr;
+    const size_t ob = ((size_t)n_slots * 2 * group_slots * sizeof(int4) + 15) / 16 * 16;
+    if (int rc = scratch(c, SC_MOT, ob + sizeof(int32_t) * n_slots, &w)) return rc;
+    J.ops = (int4 *)w;
+    J.nops = (int32_t *)((uint8_t *)w + ob);
+    HIPCHK(launch_mot(c->stream, J));
+    return 0;
+}
+
 int dabgpu_msc_deconvolve(dabgpu_ctx *c, const int16_t *frag, int64_t frag_stride, const dabgpu_subch *sub,
                           int n_cw, uint8_t *bits, int64_t out_stride) {
     if (!c || !frag || !sub || !bits || n_cw < 0) return fail(DABGPU_E_ARG, "bad args");

@@ -118,7 +118,7 @@ struct dabgpu_ctx {
     dab::DevBuf<int32_t> err;      // device error word (KERR_* bits)
     dab::PinBuf<int32_t> h_err;    // its pinned host copy (read after every synchronising pass)
     dab::OfdmTables T{};
-    dab::DevBuf<uint8_t> scratch[8];   // growable scratch (dab::scratch)
+    dab::DevBuf<uint8_t> scratch[9];   // growable scratch (dab::scratch)
     dab::Stream stream;
     ~dabgpu_ctx() {
         (void)hipSetDevice(device);
@@ -139,7 +139,7 @@ int fail(int code, const char *fmt, ...);
                         hipGetErrorString(e_), __FILE__, __LINE__);                                \
     } while (0)
 
-enum { SC_DEC = 0, SC_PROF = 1, SC_I32 = 2, SC_FRAMES = 3, SC_FC = 4, SC_MISC = 5, SC_ACQ = 6, SC_MP2 = 7 };
+enum { SC_DEC = 0, SC_PROF = 1, SC_I32 = 2, SC_FRAMES = 3, SC_FC = 4, SC_MISC = 5, SC_ACQ = 6, SC_MP2 = 7, SC_MOT = 8 };
 int scratch(dabgpu_ctx *c, int slot, size_t bytes, void **p);
 // read (and clear) the device error word; call after a stream synchronisation
 int kernel_errors(dabgpu_ctx *c);

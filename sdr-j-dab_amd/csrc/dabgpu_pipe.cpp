@@ -88,9 +88,22 @@ struct PacketLayer {
     Event ev;                     // the last pass
 };
 
+// MOT layer (a motHandler per packet entry flagged DABGPU_SUBCH_MOT and stream): allocated
+// only while dabgpu_pipe_mot_caps' max_mot > 0
+struct MotLayer {
+    int body = 0, body_cap = 0;   // max_body_bytes, and rounded up to 16
+    size_t state_bytes = 0;       // dabgpu_mot_state_bytes(body)
+    int gslots = 0;               // DABGPU_PKT_GROUP_SLOTS(F, max_bitrate)
+    DevBuf<uint8_t> state_d;      // [S][NMOT][state_bytes] the motHandlers, updated in place
+    DevBuf<int32_t> src_d;        // [S][NMOT] the packet slot (s * NPK + j) each reads, -1: absent
+    DevBuf<int4> ops_d;           // [S * NMOT][2 * gslots] the pass's copy list
+    DevBuf<int32_t> nops_d;       // [S * NMOT]
+    Event ev;                     // the last pass
+};
+
 struct dabgpu_pipe {
     dabgpu_ctx *c = nullptr;
-    int S = 0, F = 0, NSUB = 0, R = 0, NDP = 0, NMP = 0, NPK = 0;
+    int S = 0, F = 0, NSUB = 0, R = 0, NDP = 0, NMP = 0, NPK = 0, NMOT = 0;
     int16_t threshold = 3;
     int16_t method = 1;              // freqSyncMethod
     bool scan = false;               // scanMode (No_Signal_Found after > 5 attempts)
@@ -156,6 +169,12 @@ struct dabgpu_pipe {
     DabPlus dp;
     Mp2Layer mp2;
     PacketLayer pk;
+    MotLayer mot;
+    // the outputs of the run's dabgpu_pipe_packet call, which dabgpu_pipe_mot reads
+    const uint8_t *pk_bytes = nullptr;
+    const dabgpu_datagroup *pk_groups = nullptr;
+    const dabgpu_packet_run *pk_run = nullptr;
+    bool mot_pending = false;        // ... have not entered the MOT layer yet
     const uint8_t *last_msc = nullptr; // MSC bits of the last run
     bool dp_pending = false, mp2_pending = false, pk_pending = false;   // the last run's CIFs have not entered the layer yet
     int32_t last_msc_stride = 0;
@@ -262,12 +281,17 @@ static int acq_async_setup(dabgpu_pipe *p) {
 // A subchannel table against the reference's definitions and the pipeline's caps
 // (dabgpu_pipe_create_caps and dabgpu_pipe_set_subch validate alike)
 static int check_table(const dabgpu_subch *sub, int n, int max_subch, int max_bitrate, int max_dabplus, int max_mp2,
-                       int max_packet) {
+                       int max_packet, int max_mot) {
     if (n < 0 || (n > 0 && !sub)) return fail(DABGPU_E_ARG, "bad subchannel table");
     if (n > max_subch) return fail(DABGPU_E_ARG, "%d subchannels, the pipeline holds %d per stream", n, max_subch);
-    int ndp = 0, nmp = 0, npk = 0;
+    int ndp = 0, nmp = 0, npk = 0, nmot = 0;
     for (int i = 0; i < n; i++) {
         Profile P;
+        if (sub[i].flags & DABGPU_SUBCH_MOT) {
+            if (!(sub[i].flags & DABGPU_SUBCH_PACKET))
+                return fail(DABGPU_E_ARG, "subchannel %d is flagged MOT and not packet mode", i);
+            nmot++;
+        }
         if (make_profile(sub[i], P)) return fail(DABGPU_E_UNSUP, "subchannel %d protection undefined", i);
         if (sub[i].startAddr < 0 || sub[i].startAddr + sub[i].length > 864 || P.frag > sub[i].length * 64)
             return fail(DABGPU_E_ARG, "subchannel %d does not fit its CUs", i);
@@ -296,6 +320,7 @@ static int check_table(const dabgpu_subch *sub, int n, int max_subch, int max_bi
     if (nmp > max_mp2) return fail(DABGPU_E_ARG, "%d layer II subchannels, the pipeline holds %d per stream", nmp, max_mp2);
     if (npk > max_packet)
         return fail(DABGPU_E_ARG, "%d packet-mode subchannels, the pipeline holds %d per stream", npk, max_packet);
+    if (nmot > max_mot) return fail(DABGPU_E_ARG, "%d MOT subchannels, the pipeline holds %d per stream", nmot, max_mot);
     return 0;
 }
 
@@ -349,6 +374,57 @@ static int packet_size(dabgpu_pipe *p, int npk, int cap) {
     HIPCHK(hipMemcpy(k.carry_d[0], ca.data(), ca.size(), hipMemcpyHostToDevice));
     p->pk = std::move(k);
     p->NPK = npk;
+    return 0;
+}
+
+// (Re)size the MOT layer to nmot slots per stream and bodies of at most body bytes, as
+// packet_size does: the motHandlers of the slots both sizes hold go on (an entry whose body no
+// longer fits is flagged DABGPU_MOT_TOO_LARGE), every other slot is a new one; the new layer
+// takes the old one's place only when everything succeeded.
+static int mot_size(dabgpu_pipe *p, int nmot, int body) {
+    const MotLayer &old = p->mot;
+    const int S = p->S, old_n = p->NMOT;
+    std::vector<uint8_t> ost;
+    if (old_n) {
+        ost.resize((size_t)S * old_n * old.state_bytes);
+        HIPCHK(hipMemcpy(ost.data(), old.state_d, ost.size(), hipMemcpyDeviceToHost));
+    }
+    MotLayer m;
+    if (!nmot) {
+        p->mot = std::move(m);
+        p->NMOT = 0;
+        return 0;
+    }
+    m.body = body;
+    m.body_cap = (body + 15) / 16 * 16;
+    m.state_bytes = dabgpu_mot_state_bytes(body);
+    m.gslots = DABGPU_PKT_GROUP_SLOTS(p->F, p->max_bitrate);
+    const size_t ne = (size_t)S * nmot;
+    HIPCHK(m.ev.create(hipEventDisableTiming));
+    HIPCHK(m.state_d.alloc(ne * m.state_bytes));
+    HIPCHK(m.src_d.alloc(ne));
+    HIPCHK(m.ops_d.alloc(std::max<size_t>(1, ne * 2 * m.gslots)));
+    HIPCHK(m.nops_d.alloc(ne));
+    std::vector<uint8_t> st(ne * m.state_bytes, 0);
+    for (int s = 0; s < S; s++)
+        for (int j = 0; j < std::min(old_n, nmot); j++) {
+            const uint8_t *o = ost.data() + ((size_t)s * old_n + j) * old.state_bytes;
+            uint8_t *n = st.data() + ((size_t)s * nmot + j) * m.state_bytes;
+            memcpy(n, o, MOT_TABLE_BYTES);
+            auto *e = (dabgpu_mot_entry *)(n + sizeof(dabgpu_mot_head));
+            for (int k = 0; k < DABGPU_MOT_ENTRIES; k++) {
+                if (!e[k].order || (e[k].flags & DABGPU_MOT_TOO_LARGE)) continue;
+                if (e[k].bodySize > body) {
+                    e[k].flags |= DABGPU_MOT_TOO_LARGE;
+                    continue;
+                }
+                memcpy(n + MOT_TABLE_BYTES + (size_t)k * m.body_cap, o + MOT_TABLE_BYTES + (size_t)k * old.body_cap,
+                       (size_t)std::max(0, e[k].bodySize));
+            }
+        }
+    HIPCHK(hipMemcpy(m.state_d, st.data(), st.size(), hipMemcpyHostToDevice));
+    p->mot = std::move(m);
+    p->NMOT = nmot;
     return 0;
 }
 
@@ -470,6 +546,16 @@ static int rebuild_tables(dabgpu_pipe *p) {
         HIPCHK(hipMemcpy(p->pk.br_d, kb.data(), sizeof(int16_t) * nk, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(p->pk.since_d, kc.data(), sizeof(int64_t) * nk, hipMemcpyHostToDevice));
     }
+    if (p->NMOT) {                // MOT slots: slot m of a stream is its m-th entry flagged DABGPU_SUBCH_MOT
+        std::vector<int32_t> src((size_t)S * p->NMOT, -1);
+        for (int s = 0; s < S; s++)
+            for (int k = 0, j = 0, m = 0; k < (int)p->tab[s].size(); k++) {
+                if (!(p->tab[s][k].flags & DABGPU_SUBCH_PACKET)) continue;
+                if (p->tab[s][k].flags & DABGPU_SUBCH_MOT) src[(size_t)s * p->NMOT + m++] = s * p->NPK + j;
+                j++;
+            }
+        HIPCHK(hipMemcpy(p->mot.src_d, src.data(), sizeof(int32_t) * src.size(), hipMemcpyHostToDevice));
+    }
     if (p->NDP) {
         HIPCHK(hipMemcpy(p->dp.sub_d, dps.data(), sizeof(int32_t) * nd, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(p->dp.br_d, dpb.data(), sizeof(int16_t) * nd, hipMemcpyHostToDevice));
@@ -501,10 +587,13 @@ int dabgpu_pipe_create_caps(dabgpu_ctx *c, const dabgpu_pipe_cfg *cfg, const dab
         return fail(DABGPU_E_ARG, "bad caps (at most 64 subchannels of at most 384 kbit/s)");
     if (cfg->freq_sync_method < 0 || cfg->freq_sync_method > 2)
         return fail(DABGPU_E_UNSUP, "freqSyncMethod %d (0, 1 or 2: ofdm-decoder.cpp:103-161)", cfg->freq_sync_method);
-    int npk = 0;                  // the packet-mode layer starts with what the table flags (dabgpu_pipe_packet_caps)
-    for (int i = 0; i < cfg->n_subch; i++)
+    int npk = 0, nmot = 0;        // the packet-mode and MOT layers start with what the table flags (dabgpu_pipe_packet_caps)
+    for (int i = 0; i < cfg->n_subch; i++) {
         if (cfg->subch[i].flags & DABGPU_SUBCH_PACKET) npk++;
-    if (int rc = check_table(cfg->subch, cfg->n_subch, caps->max_subch, caps->max_bitrate, caps->max_dabplus, caps->max_mp2, npk))
+        if (cfg->subch[i].flags & DABGPU_SUBCH_MOT) nmot++;
+    }
+    if (int rc = check_table(cfg->subch, cfg->n_subch, caps->max_subch, caps->max_bitrate, caps->max_dabplus, caps->max_mp2, npk,
+                             nmot))
         return rc;
     auto p = std::make_unique<dabgpu_pipe>();
     p->c = c;
@@ -589,6 +678,8 @@ int dabgpu_pipe_create_caps(dabgpu_ctx *c, const dabgpu_pipe_cfg *cfg, const dab
     }
     if (npk)
         if (int rc = packet_size(p.get(), npk, DABGPU_PKT_GROUP_BYTES)) return rc;
+    if (nmot)
+        if (int rc = mot_size(p.get(), nmot, DABGPU_MOT_BODY_BYTES)) return rc;
     if (int rc = rebuild_tables(p.get())) return rc;
     // the default re-acquisition mode: a stream that loses sync is searched in the
     // background (DABGPU_CTL_ACQ_ASYNC; DABGPU_CTL_ACQ_SYNC restores the in-run search)
@@ -1063,6 +1154,7 @@ int dabgpu_pipe_run(dabgpu_pipe *p, const void *iq, int64_t stride, const int64_
     p->inject_bounds = false;
     p->last_msc = have_rows ? msc_bits : nullptr;
     p->dp_pending = p->mp2_pending = p->pk_pending = have_rows;
+    p->mot_pending = false;                    // until this run's dabgpu_pipe_packet
     p->last_msc_stride = msc_stride;
     p->last_msc_packed = p->packed;
     publish_validity(p, done, have_rows, msc_valid);
@@ -1257,13 +1349,75 @@ int dabgpu_pipe_packet(dabgpu_pipe *p, uint8_t *bytes, dabgpu_datagroup *groups,
     HIPCHK(k.ev.record(bs));
     k.cur ^= 1;
     p->pk_pending = false;                     // each run's CIFs enter the layer once
+    p->pk_bytes = bytes;
+    p->pk_groups = groups;
+    p->pk_run = run;
+    p->mot_pending = p->NMOT > 0;
     return 0;
+}
+
+int dabgpu_pipe_mot(dabgpu_pipe *p, uint8_t *bytes, dabgpu_mot_object *objects, dabgpu_mot_run *run) {
+    if (!p || !bytes || !objects || !run) return fail(DABGPU_E_ARG, "null arg");
+    if (p->NMOT == 0) return fail(DABGPU_E_STATE, "no MOT subchannel in this pipeline");
+    if (!p->mot_pending) return fail(DABGPU_E_STATE, "no dabgpu_pipe_packet call of this run to consume");
+    if ((uintptr_t)bytes & 15) return fail(DABGPU_E_ARG, "bytes_d must be 16-byte aligned");
+    MotLayer &m = p->mot;
+    MotJob J;
+    memset(&J, 0, sizeof J);
+    J.n_slots = p->S * p->NMOT;
+    J.max_body = m.body;
+    J.body_cap = m.body_cap;
+    J.state_bytes = (int64_t)m.state_bytes;
+    J.state = m.state_d;
+    J.src = m.src_d;
+    J.groups = p->pk_groups;
+    J.gslots = m.gslots;
+    J.bytes = p->pk_bytes;
+    J.arena = DABGPU_PKT_ARENA_BYTES((int64_t)p->F, p->max_bitrate, p->pk.cap);
+    J.run = p->pk_run;
+    J.objects = objects;
+    J.out = bytes;
+    J.out_arena = DABGPU_MOT_ARENA_BYTES((int64_t)p->F, p->max_bitrate, m.body);
+    J.mot_run = run;
+    J.ops = m.ops_d;
+    J.nops = m.nops_d;
+    // on the run's back-end stream, behind its packet layer; after the previous pass (the
+    // motHandlers are updated in place, the copy list is reused)
+    hipStream_t bs = p->back[p->cur].stream;
+    HIPCHK(m.ev.wait_on(bs));
+    HIPCHK(launch_mot(bs, J));
+    HIPCHK(m.ev.record(bs));
+    p->mot_pending = false;                    // each run's groups enter the layer once
+    return 0;
+}
+
+int dabgpu_pipe_mot_caps(dabgpu_pipe *p, int max_mot, int max_body_bytes) {
+    if (!p || max_mot < 0 || max_body_bytes < 0 || max_body_bytes > (1 << 24) || max_mot > p->NPK)
+        return fail(DABGPU_E_ARG, "bad args (max_mot <= max_packet, max_body_bytes <= 1 << 24)");
+    const int body = max_body_bytes ? max_body_bytes : DABGPU_MOT_BODY_BYTES;
+    if (max_mot && (DABGPU_PKT_ARENA_BYTES((int64_t)p->F, p->max_bitrate, p->pk.cap) > 0x7FFFFFFF ||
+                    DABGPU_MOT_ARENA_BYTES((int64_t)p->F, p->max_bitrate, body) > 0x7FFFFFFF))
+        return fail(DABGPU_E_ARG, "arenas of 2 GiB and more");
+    for (int s = 0; s < p->S; s++) {
+        int n = 0;
+        for (const dabgpu_subch &e : p->tab[s])
+            if (e.flags & DABGPU_SUBCH_MOT) n++;
+        if (n > max_mot) return fail(DABGPU_E_ARG, "stream %d's table has %d MOT subchannels", s, n);
+    }
+    if (int rc = sync_streams(p)) return rc;
+    if (int rc = mot_size(p, max_mot, body)) return rc;
+    p->mot_pending = false;
+    return rebuild_tables(p);
 }
 
 int dabgpu_pipe_packet_caps(dabgpu_pipe *p, int max_packet, int max_group_bytes) {
     if (!p || max_packet < 0 || max_group_bytes < 0 || max_packet > p->NSUB) return fail(DABGPU_E_ARG, "bad args");
+    if (max_packet < p->NMOT) return fail(DABGPU_E_ARG, "the MOT layer holds %d slots (dabgpu_pipe_mot_caps first)", p->NMOT);
     if (max_packet && p->max_bitrate < 8) return fail(DABGPU_E_ARG, "max_bitrate %d holds no packet-mode entry", p->max_bitrate);
     const int cap = max_group_bytes ? max_group_bytes : DABGPU_PKT_GROUP_BYTES;
+    // the MOT layer indexes the packet arena in int32 (as dabgpu_pipe_mot_caps checks)
+    if (p->NMOT && DABGPU_PKT_ARENA_BYTES((int64_t)p->F, p->max_bitrate, (int64_t)cap) > 0x7FFFFFFF)
+        return fail(DABGPU_E_ARG, "a packet arena of 2 GiB and more under the MOT layer");
     for (int s = 0; s < p->S; s++) {
         int n = 0;
         for (const dabgpu_subch &e : p->tab[s])
@@ -1272,6 +1426,7 @@ int dabgpu_pipe_packet_caps(dabgpu_pipe *p, int max_packet, int max_group_bytes)
     }
     if (int rc = sync_streams(p)) return rc;
     if (int rc = packet_size(p, max_packet, cap)) return rc;
+    p->mot_pending = false;
     return rebuild_tables(p);
 }
 
@@ -1382,7 +1537,7 @@ int dabgpu_pipe_frame_slot(dabgpu_pipe *p, int frame, int32_t *slot) {
 }
 int dabgpu_pipe_set_subch(dabgpu_pipe *p, int stream, const dabgpu_subch *sub, int32_t n) {
     if (!p || stream < -1 || stream >= p->S) return fail(DABGPU_E_ARG, "bad args");
-    if (int rc = check_table(sub, n, p->NSUB, p->max_bitrate, p->NDP, p->NMP, p->NPK)) return rc;   // the table stays on error
+    if (int rc = check_table(sub, n, p->NSUB, p->max_bitrate, p->NDP, p->NMP, p->NPK, p->NMOT)) return rc;   // the table stays on error
     // in-flight kernels read the device tables: a rare control call, so it waits for
     // everything the pipeline has enqueued (as dabgpu_pipe_set_profiling) instead of
     // double-buffering them
@@ -1458,6 +1613,23 @@ int dabgpu_pipe_set_subch(dabgpu_pipe *p, int stream, const dabgpu_subch *sub, i
             HIPCHK(hipMemcpy(m.state_d + o, nps.data(), sizeof(PkState) * NK, hipMemcpyHostToDevice));
             HIPCHK(hipMemcpy(m.carry_d[m.cur] + o * CB, nca.data(), NK * CB, hipMemcpyHostToDevice));
         }
+        // the MOT slots likewise: an unchanged entry's motHandler moves to its new slot, every
+        // other slot is a new one
+        if (p->NMOT) {
+            MotLayer &m = p->mot;
+            const size_t NM = p->NMOT, SB = m.state_bytes, o = (size_t)s * NM * SB;
+            std::vector<uint8_t> ms(NM * SB), nms(NM * SB, 0);
+            HIPCHK(hipMemcpy(ms.data(), m.state_d + o, NM * SB, hipMemcpyDeviceToHost));
+            std::vector<int> oslot(old.size(), -1);
+            for (int k = 0, j = 0; k < (int)old.size(); k++)
+                if (old[k].flags & DABGPU_SUBCH_MOT) oslot[k] = j++;
+            for (int k = 0, j = 0; k < n; k++) {
+                if (!(sub[k].flags & DABGPU_SUBCH_MOT)) continue;
+                if (k < (int)old.size() && same_subch(old[k], sub[k])) memcpy(nms.data() + j * SB, ms.data() + oslot[k] * SB, SB);
+                j++;
+            }
+            HIPCHK(hipMemcpy(m.state_d + o, nms.data(), NM * SB, hipMemcpyHostToDevice));
+        }
         p->tab[s].assign(sub, sub + n);
         p->since[s].assign(n, p->st[s].cif_count);
         for (int k = 0, j = 0; k < n; k++) {
@@ -1476,6 +1648,7 @@ int dabgpu_pipe_set_subch(dabgpu_pipe *p, int stream, const dabgpu_subch *sub, i
         }
     }
     p->last_msc = nullptr;            // the last run's rows follow the old tables: no DAB+ layer over them now
+    p->mot_pending = false;
     if (int rc = rebuild_tables(p)) return rc;
     if (p->inject_bounds) return inject_table(p);
     return 0;

@@ -61,6 +61,66 @@ def pkt_arena_bytes(n_frames: int, max_bitrate: int, max_group_bytes: int) -> in
     return max_group_bytes + 4 * n_frames * (max_bitrate // 8) * 127
 
 
+SUBCH_MOT = 16      # Subch.flags, with SUBCH_PACKET: feed the entry's groups to the MOT layer (Pipeline.mot)
+MOT_BODY_BYTES, MOT_NAME_BYTES, MOT_ENTRIES = 65536, 128, 16
+MOT_SLIDE, MOT_EPG, MOT_FILE = 1, 2, 3      # dabgpu_mot_object.kind
+MOT_TOO_LARGE, MOT_OVERFLOW = 1, 2
+MOT_OBJECT_DTYPE = np.dtype([("group", "<i4"), ("cif", "<i4"), ("offset", "<i4"), ("nbytes", "<i4"),
+                             ("transportId", "<u2"), ("contentType", "u1"), ("kind", "u1"), ("contentsubType", "<u2"),
+                             ("flags", "<u2"), ("name_len", "<i4"), ("name", "u1", (MOT_NAME_BYTES,))])   # dabgpu_mot_object
+MOT_RUN_DTYPE = np.dtype([("n_objects", "<i4"), ("n_bytes", "<i4"), ("malformed", "<i4"), ("bad_segment", "<i4"),
+                          ("other_types", "<i4"), ("entries", "<i4"), ("reserved", "<i4", (2,))])          # dabgpu_mot_run
+
+
+def mot_arena_bytes(group_slots: int, max_body_bytes: int = MOT_BODY_BYTES) -> int:
+    """DABGPU_MOT_ARENA_FOR"""
+    return (max_body_bytes + 15) // 16 * 16 + group_slots * 144
+
+
+def mot_state_bytes(max_body_bytes: int = 0) -> int:
+    """dabgpu_mot_state_bytes: a motHandler's carried state (all zero: a new one)"""
+    return int(lib().dabgpu_mot_state_bytes(int(max_body_bytes)))
+
+
+def _records(buf: "DevBuf", dtype: np.dtype, shape) -> np.ndarray:
+    raw = buf.download(np.uint8, int(np.prod(shape)) * dtype.itemsize)
+    return np.frombuffer(raw.tobytes(), dtype=dtype).reshape(shape)
+
+
+def mot_groups(ctx: "Context", groups: np.ndarray, data: np.ndarray, run: np.ndarray,
+               state: Optional[np.ndarray] = None, max_body_bytes: int = 0, out_arena_bytes: Optional[int] = None):
+    """motHandler::process_mscGroup in header mode per slot (dabgpu_mot_groups; mot-data.cpp:
+    679-728): groups [n_slots, group_slots] DATAGROUP_DTYPE, data [n_slots, arena] uint8 and run
+    [n_slots] PACKET_RUN_DTYPE as Pipeline.packet() returns them for one stream; state
+    [n_slots, mot_state_bytes(max_body_bytes)] bytes carried from an earlier call (None: new
+    motHandlers).  Returns (objects [n_slots, group_slots] MOT_OBJECT_DTYPE -- the first
+    mot_run.n_objects of a row --, bytes [n_slots, out_arena] uint8, mot_run [n_slots]
+    MOT_RUN_DTYPE, state)."""
+    groups = np.ascontiguousarray(groups, dtype=DATAGROUP_DTYPE)
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    run = np.ascontiguousarray(run, dtype=PACKET_RUN_DTYPE)
+    n, gs = groups.shape
+    assert data.shape[0] == n and run.shape == (n,)
+    sb = mot_state_bytes(max_body_bytes)
+    if sb == 0:                          # a max_body_bytes the library refuses (DABGPU_E_ARG, before it reads or
+        sb, state = 16, None             # writes anything): it gets small buffers and says so itself
+        out_arena_bytes = 16 if out_arena_bytes is None else out_arena_bytes
+    st = np.zeros((n, sb), np.uint8) if state is None else np.ascontiguousarray(state, dtype=np.uint8).reshape(n, sb)
+    oa = mot_arena_bytes(gs, max_body_bytes or MOT_BODY_BYTES) if out_arena_bytes is None else int(out_arena_bytes)
+    dg, db, dr, ds = ctx.put(groups.view(np.uint8)), ctx.put(data), ctx.put(run.view(np.uint8)), ctx.put(st)
+    do = ctx.buf(max(16, n * gs * MOT_OBJECT_DTYPE.itemsize)).zero()
+    dby, dmr = ctx.buf(max(16, n * max(oa, 0))).zero(), ctx.buf(max(16, n * MOT_RUN_DTYPE.itemsize))
+    try:
+        _chk(lib().dabgpu_mot_groups(ctx.h, ds.ptr, n, int(max_body_bytes), dg.ptr, gs, db.ptr, data.shape[1], dr.ptr,
+                                     do.ptr, dby.ptr, oa, dmr.ptr), "dabgpu_mot_groups")
+        ctx.sync()
+        return (_records(do, MOT_OBJECT_DTYPE, (n, gs)), dby.download(np.uint8, (n, oa)),
+                _records(dmr, MOT_RUN_DTYPE, (n,)), ds.download(np.uint8, (n, sb)))
+    finally:
+        for b in (dg, db, dr, ds, do, dby, dmr):
+            b.free()
+
+
 SUPERFRAME_DTYPE = np.dtype([("status", "i1"), ("num_aus", "i1"), ("n_corrected", "<i2"), ("au_start", "<i2", (7,)),
                              ("au_crc_ok", "u1"), ("reserved", "u1")])
 
@@ -153,6 +213,10 @@ def lib() -> C.CDLL:
             "dabgpu_pipe_mp2": ([vp, vp, vp], i32),
             "dabgpu_pipe_packet": ([vp, vp, vp, vp, vp], i32),
             "dabgpu_pipe_packet_caps": ([vp, i32, i32], i32),
+            "dabgpu_mot_state_bytes": ([i32], sz),
+            "dabgpu_mot_groups": ([vp, vp, i32, i32, vp, i32, vp, i64, vp, vp, vp, i64, vp], i32),
+            "dabgpu_pipe_mot": ([vp, vp, vp, vp], i32),
+            "dabgpu_pipe_mot_caps": ([vp, i32, i32], i32),
             "dabgpu_pipe_sync": ([vp], i32),
             "dabgpu_pipe_create": ([vp, vp, C.POINTER(vp)], i32), "dabgpu_pipe_destroy": ([vp], i32),
             "dabgpu_pipe_acquire": ([vp, vp, i64, vp, vp], i32),
@@ -729,7 +793,8 @@ class Pipeline:
                  threshold: int = 3, freq_sync_method: int = 1, max_subch: Optional[int] = None,
                  max_bitrate: Optional[int] = None, max_dabplus: Optional[int] = None,
                  max_mp2: Optional[int] = None, max_packet: Optional[int] = None,
-                 max_group_bytes: Optional[int] = None):
+                 max_group_bytes: Optional[int] = None, max_mot: Optional[int] = None,
+                 max_body_bytes: Optional[int] = None):
         self.ctx, self.S, self.F, self.subch = ctx, n_streams, n_frames, list(subch)
         self._arr = (Subch * max(1, len(self.subch)))(*self.subch)
         cfg = PipeCfg(n_streams, n_frames, len(self.subch), threshold, freq_sync_method,
@@ -783,6 +848,50 @@ class Pipeline:
             self.packet_caps(self.max_packet if max_packet is None else max_packet, max_group_bytes or 0)
         else:
             self._packet_bufs()
+        self._mot = []
+        self.max_mot = sum(1 for s in self.subch if s.flags & SUBCH_MOT)
+        self.max_body_bytes = MOT_BODY_BYTES
+        if max_mot is not None or max_body_bytes is not None:
+            self.mot_caps(self.max_mot if max_mot is None else max_mot, max_body_bytes or 0)
+        else:
+            self._mot_bufs()
+
+    def _mot_bufs(self) -> None:
+        for o in self._mot:
+            for b in o:
+                b.free()
+        self._mot = []
+        if self.max_mot:
+            ne, gs = self.S * self.max_mot, pkt_group_slots(self.F, self.max_bitrate)
+            self._mot = [(self.ctx.buf(ne * mot_arena_bytes(gs, self.max_body_bytes)),
+                          self.ctx.buf(ne * gs * MOT_OBJECT_DTYPE.itemsize),
+                          self.ctx.buf(ne * MOT_RUN_DTYPE.itemsize)) for _ in range(2)]
+
+    def mot_caps(self, max_mot: int, max_body_bytes: int = 0) -> None:
+        """size the MOT layer between runs (dabgpu_pipe_mot_caps): max_mot slots per stream
+        (<= max_packet), bodies of at most max_body_bytes (0: MOT_BODY_BYTES); the existing
+        slots keep their motHandlers"""
+        _chk(lib().dabgpu_pipe_mot_caps(self.h, int(max_mot), int(max_body_bytes)), "dabgpu_pipe_mot_caps")
+        self.max_mot, self.max_body_bytes = int(max_mot), int(max_body_bytes) or MOT_BODY_BYTES
+        self._mot_bufs()
+
+    def mot(self, download: bool = True):
+        """MOT layer over the groups of this run's packet() (dabgpu_pipe_mot; mot-data.cpp:
+        679-728 in header mode).  Returns (bytes [S, max_mot, arena] uint8, objects [S, max_mot,
+        slots] MOT_OBJECT_DTYPE -- the first run.n_objects of a row are this run's --, run
+        [S, max_mot] MOT_RUN_DTYPE)."""
+        if not self._mot:                # max_mot == 0: there are no output buffers to hand to the library,
+            e = DabError("dabgpu_pipe_mot: no MOT subchannel in this pipeline")   # which would refuse as well
+            e.code = -6                  # DABGPU_E_STATE
+            raise e
+        self.motb_d, self.moto_d, self.motr_d = self._mot[(self._run - 1) & 1]
+        _chk(lib().dabgpu_pipe_mot(self.h, self.motb_d.ptr, self.moto_d.ptr, self.motr_d.ptr), "dabgpu_pipe_mot")
+        if not download:
+            return None
+        self.sync()
+        S, NM, gs = self.S, self.max_mot, pkt_group_slots(self.F, self.max_bitrate)
+        return (self.motb_d.download(np.uint8, (S, NM, mot_arena_bytes(gs, self.max_body_bytes))),
+                _records(self.moto_d, MOT_OBJECT_DTYPE, (S, NM, gs)), _records(self.motr_d, MOT_RUN_DTYPE, (S, NM)))
 
     def _packet_bufs(self) -> None:
         for o in self._pkt:
@@ -1024,7 +1133,7 @@ class Pipeline:
 
     def close(self) -> None:
         if self.h:
-            for o in self._outs + self._sf + self._mp2 + self._pkt:
+            for o in self._outs + self._sf + self._mp2 + self._pkt + self._mot:
                 for b in o:
                     b.free()
             lib().dabgpu_pipe_destroy(self.h)

@@ -297,6 +297,20 @@ ensembleDecoder::ensembleDecoder(const config &cfg) : cfg_(cfg) {
         pkr_.resize(ne * sizeof(dabgpu_packet_run));
         pki_.resize(SF * 4 * npk_ * sizeof(dabgpu_packet_info));
     }
+    for (const dabgpu_subch &sc : cfg.subch)
+        if (sc.flags & DABGPU_SUBCH_MOT) nmot_++;
+    if (cfg.max_mot || cfg.max_body_bytes) {
+        nmot_ = cfg.max_mot ? cfg.max_mot : nmot_;
+        chk(dabgpu_pipe_mot_caps(pipe_, nmot_, cfg.max_body_bytes), "dabgpu_pipe_mot_caps");
+    }
+    if (nmot_) {
+        mot_arena_ = DABGPU_MOT_ARENA_BYTES((size_t)cfg.n_frames, (int)caps.max_bitrate,
+                                            (size_t)(cfg.max_body_bytes ? cfg.max_body_bytes : DABGPU_MOT_BODY_BYTES));
+        const size_t ne = (size_t)cfg.n_streams * nmot_;
+        mob_.resize(ne * mot_arena_);
+        moo_.resize(std::max<size_t>(1, ne * pk_slots_) * sizeof(dabgpu_mot_object));
+        mor_.resize(ne * sizeof(dabgpu_mot_run));
+    }
 }
 
 void ensembleDecoder::set_subch(int stream, const std::vector<dabgpu_subch> &subch) {
@@ -581,6 +595,35 @@ bool ensembleDecoder::step() {
             }
         }
     }
+    if (NS && nmot_) {
+        chk(dabgpu_pipe_mot(pipe_, (uint8_t *)mob_.get(), (dabgpu_mot_object *)moo_.get(), (dabgpu_mot_run *)mor_.get()),
+            "dabgpu_pipe_mot");
+        chk(dabgpu_pipe_sync(pipe_), "dabgpu_pipe_sync");
+        if (mot_cb_) {
+            // as for the groups: the run records, then per (stream, slot) what the run completed
+            std::vector<dabgpu_mot_run> run((size_t)S * nmot_);
+            mor_.download(run.data(), run.size() * sizeof(dabgpu_mot_run));
+            std::vector<dabgpu_mot_object> objects;
+            std::vector<uint8_t> bytes;
+            for (int s = 0; s < S; s++) {
+                std::vector<int> slot;               // MOT slot j of a stream is its j-th entry flagged for both
+                for (int k = 0; k < (int)tab_[s].size(); k++)
+                    if ((tab_[s][k].flags & DABGPU_SUBCH_PACKET) && (tab_[s][k].flags & DABGPU_SUBCH_MOT)) slot.push_back(k);
+                for (int j = 0; j < (int)slot.size() && j < nmot_; j++) {
+                    const size_t e = (size_t)s * nmot_ + j;
+                    if (run[e].n_objects <= 0) continue;
+                    objects.resize(run[e].n_objects);
+                    bytes.resize(std::max(1, run[e].n_bytes));
+                    chk(dabgpu_memcpy_d2h(thread_context(), objects.data(), (const dabgpu_mot_object *)moo_.get() + e * pk_slots_,
+                                          objects.size() * sizeof(dabgpu_mot_object)), "dabgpu_memcpy_d2h");
+                    chk(dabgpu_memcpy_d2h(thread_context(), bytes.data(), (const uint8_t *)mob_.get() + e * mot_arena_, run[e].n_bytes),
+                        "dabgpu_memcpy_d2h");
+                    for (const dabgpu_mot_object &o : objects)
+                        mot_cb_(s, 4 * frames_done_[s] + o.cif, slot[j], o, bytes.data() + o.offset);
+                }
+            }
+        }
+    }
     for (int s = 0; s < S; s++) {
         dabgpu_stream_state st;
         chk(dabgpu_pipe_state(pipe_, s, &st), "dabgpu_pipe_state");
@@ -589,7 +632,8 @@ bool ensembleDecoder::step() {
     // FIC first: a table parsed twice alike (two steps) and not yet applied is applied now
     for (int s = 0; s < S && cfg_.auto_layout; s++) {
         std::vector<dabgpu_subch> now;
-        for (const fib_subch &e : fibs_[s].subchannels(nullptr, pcm_cb_ != nullptr && nmp_ > 0, dg_cb_ != nullptr && npk_ > 0))
+        for (const fib_subch &e : fibs_[s].subchannels(nullptr, pcm_cb_ != nullptr && nmp_ > 0, dg_cb_ != nullptr && npk_ > 0,
+                                                       mot_cb_ != nullptr && nmot_ > 0))
             now.push_back({e.startAddr, e.length, e.bitRate, e.protLevel, e.uepFlag, e.flags});
         auto same = [](const std::vector<dabgpu_subch> &x, const std::vector<dabgpu_subch> &y) {
             return x.size() == y.size() && (x.empty() || !std::memcmp(x.data(), y.data(), x.size() * sizeof(dabgpu_subch)));

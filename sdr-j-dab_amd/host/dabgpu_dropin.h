@@ -253,10 +253,16 @@ protected:
 class mscDatagroup : public dabConcurrent {
 public:
     mscDatagroup(uint8_t DSCTy, int16_t packetAddress, int16_t fragmentSize, int16_t bitRate, int16_t uepFlag,
-                 int16_t protLevel, uint8_t DGflag, int16_t FEC_scheme, packetAssembler::datagroup_cb cb);
+                 int16_t protLevel, uint8_t DGflag, int16_t FEC_scheme, packetAssembler::datagroup_cb cb,
+                 motAssembler::object_cb mot = nullptr);
     int32_t process(int16_t *v, int16_t cnt) override;
     const packetAssembler &assembler() const { return pa_; }
+    // DSCTy 60 (my_dataHandler = new mot_databuilder, msc-datagroup.cpp:82-84): every data group
+    // also goes through the host motAssembler, whose slides and files go to the mot callback
+    // (nullptr for any other DSCTy)
+    const motAssembler *mot() const { return mot_.get(); }
 private:
+    std::unique_ptr<motAssembler> mot_;        // before pa_, whose callback feeds it
     packetAssembler pa_;
 };
 
@@ -275,6 +281,7 @@ public:
         mp2Processor::frame_cb mp2;            // MPEG-1/2 layer II frames (DAB)
         mp4Processor::au_cb aac;               // AAC access units (DAB+)
         packetAssembler::datagroup_cb datagroup;
+        motAssembler::object_cb mot;           // slides and files of a DSCTy 60 data channel (the_picture, fopen)
     };
     mscHandler(DabParams *p, outputs out, uint8_t concurrent = 1);
     void process_mscBlock(int16_t *fbits, int16_t blkno);
@@ -480,6 +487,9 @@ public:
         // dabgpu_pipe_packet_caps: packet-mode (DABGPU_SUBCH_PACKET) entries a stream's table may
         // hold (0: what subch flags) and the largest data group (0: DABGPU_PKT_GROUP_BYTES)
         int max_packet = 0, max_group_bytes = 0;
+        // dabgpu_pipe_mot_caps: entries also flagged DABGPU_SUBCH_MOT a stream's table may hold
+        // (0: what subch flags; at most max_packet) and the largest MOT body (0: DABGPU_MOT_BODY_BYTES)
+        int max_mot = 0, max_body_bytes = 0;
         // FIC first: each stream's table follows its own FIG 0/1 and 0/2 (a fib_processor per
         // stream, fed its CRC-good FIBs).  At the end of a step() a stream's parsed table is
         // applied (set_subch) when it is non-empty, equals the one parsed at the end of the
@@ -517,6 +527,16 @@ public:
     // show_mscErrors (msc-datagroup.cpp:250-254): 100 - crcErrors / 5 per 500 handled packets
     using packet_quality_cb = std::function<void(int stream, int64_t cif, int subch, int value)>;
     void on_packet_quality(packet_quality_cb f) { pq_cb_ = std::move(f); }
+    // MOT objects of the packet-mode entries also flagged DABGPU_SUBCH_MOT (dabgpu_pipe_mot, after
+    // the step's dabgpu_pipe_packet), where motHandler emits the_picture or fopens (mot-data.cpp:
+    // 315-346): one call per completed object in completion order, after the step's on_datagroup
+    // calls; body holds o.nbytes bytes (none for DABGPU_MOT_EPG or with DABGPU_MOT_OVERFLOW); cif
+    // is the CIF of the group that completed it.  With auto_layout, sub-channels with a DSCTy 60
+    // packet-mode component are flagged DABGPU_SUBCH_PACKET | DABGPU_SUBCH_MOT when this callback
+    // is set before the table is applied (config::max_packet and max_mot say how many).
+    using mot_object_cb = std::function<void(int stream, int64_t cif, int subch, const dabgpu_mot_object &o,
+                                             const uint8_t *body)>;
+    void on_mot_object(mot_object_cb f) { mot_cb_ = std::move(f); }
     // samples[s] -> n[s] cf32 samples of stream s (copied to HBM)
     void load(const std::vector<const DSPCOMPLEX *> &samples, const std::vector<int64_t> &n);
     // the streams as recorded: format DABGPU_IQ_S16 (.sdr PCM16 I/Q pairs) or DABGPU_IQ_U8
@@ -548,6 +568,10 @@ private:
     devbuf iq_, fic_, crc_, msc_, sf_, sfi_, pcm_, mp2i_, pkb_, pkg_, pkr_, pki_;
     int nmp_ = 0, npk_ = 0, pk_cap_ = 0;
     size_t pk_slots_ = 0, pk_arena_ = 0;
+    devbuf mob_, moo_, mor_;                          // the MOT layer's arenas, object records, run records
+    int nmot_ = 0;
+    size_t mot_arena_ = 0;
+    mot_object_cb mot_cb_;
     pcm_cb pcm_cb_;
     datagroup_cb dg_cb_;
     packet_quality_cb pq_cb_;

@@ -367,7 +367,7 @@ int fib_processor::bind(int8_t tmid, int32_t sid, int16_t compnr) {
     return first_free;
 }
 
-std::vector<fib_subch> fib_processor::subchannels(std::vector<int> *ids, bool classic_audio, bool packet_data) const {
+std::vector<fib_subch> fib_processor::subchannels(std::vector<int> *ids, bool classic_audio, bool packet_data, bool mot) const {
     std::vector<fib_subch> v;
     if (ids) ids->clear();
     for (int id = 0; id < 64; id++) {
@@ -383,10 +383,12 @@ std::vector<fib_subch> fib_processor::subchannels(std::vector<int> *ids, bool cl
         // packet data: a TMid 3 component whose FIG 0/3 named this sub-channel; not the one
         // kind mscDatagroup hands to handleTDCAsyncstream, which delivers nothing
         for (const component &c : components_)
-            if (packet_data && c.inUse && c.TMid == 3 && c.DSCTy != 0 && c.subchannelId == id && !(c.DSCTy == 5 && c.DGflag))
-                e.flags |= 8;                                           // DABGPU_SUBCH_PACKET
+            if (c.inUse && c.TMid == 3 && c.DSCTy != 0 && c.subchannelId == id && !(c.DSCTy == 5 && c.DGflag)) {
+                if (packet_data) e.flags |= 8;                          // DABGPU_SUBCH_PACKET
+                if (mot && c.DSCTy == 60) e.flags |= 8 | 16;            // ... | DABGPU_SUBCH_MOT
+            }
         if (e.flags & 1) e.flags &= ~4;                                 // (one layer per entry,
-        if (e.flags & 5) e.flags &= ~8;                                 //  the audio layers first)
+        if (e.flags & 5) e.flags &= ~(8 | 16);                          //  the audio layers first)
         v.push_back(e);
         if (ids) ids->push_back(id);
     }

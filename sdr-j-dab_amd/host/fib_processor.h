@@ -102,8 +102,11 @@ public:
     // arrived, which is taken from DSCTy != 0: until then its sub-channel field still holds 0
     // and would flag sub-channel 0; a component announced with DSCTy 0 (unspecified data) is
     // therefore not flagged either.  The audio layers win on a conflict.
+    // mot: flag DABGPU_SUBCH_PACKET | DABGPU_SUBCH_MOT (8 | 16) where such a component has DSCTy
+    // 60 (MOT: what mscDatagroup hands to mot_databuilder, msc-datagroup.cpp:82-84), whether
+    // packet_data is set or not.
     std::vector<fib_subch> subchannels(std::vector<int> *ids = nullptr, bool classic_audio = false,
-                                       bool packet_data = false) const;
+                                       bool packet_data = false, bool mot = false) const;
 
     std::string ensembleName() const { return ensemble_; }
     std::vector<std::string> serviceLabels() const;

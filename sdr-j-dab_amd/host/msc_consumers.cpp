@@ -152,4 +152,164 @@ void packetAssembler::handlePacket(uint8_t *data, int avail) {          // msc-d
     }
 }
 
+// ---- motAssembler -----------------------------------------------------------------
+motAssembler::motAssembler(object_cb cb, int32_t max_body_bytes) : cb_(std::move(cb)), maxBody_(max_body_bytes) {}
+
+int32_t motAssembler::entries() const {
+    int32_t n = 0;
+    for (const element &e : table_) n += e.ordernumber != 0;
+    return n;
+}
+
+void motAssembler::add_mscDatagroup(const std::vector<uint8_t> &bits) {       // mot-databuilder.cpp:37-95
+    const int32_t nbits = (int32_t)bits.size(), nb = nbits / 8;
+    if (nbits == 0) return;
+    std::vector<uint8_t> g((size_t)nb);
+    for (int32_t i = 0; i < nb; i++) {
+        uint32_t b = 0;
+        for (int k = 0; k < 8; k++) b = (b << 1) | (bits[(size_t)8 * i + k] & 1u);
+        g[(size_t)i] = (uint8_t)b;
+    }
+    auto B = [&](int32_t i) -> uint32_t { return i < nb ? g[(size_t)i] : 0u; };   // fields past the end read 0
+    const bool ext = B(0) & 0x80, crcf = B(0) & 0x40, seg = B(0) & 0x20, ua = B(0) & 0x10;
+    if (crcf) {                                                           // check_CRC_bits, in int32
+        if (nb < 2) return;
+        uint32_t reg = 0xFFFF;
+        for (int32_t i = 0; i < nb; i++) {
+            const uint32_t byte = i >= nb - 2 ? g[(size_t)i] ^ 0xFFu : g[(size_t)i];
+            for (int k = 7; k >= 0; k--) {
+                const uint32_t top = (reg >> 15) & 1u;
+                reg = (reg << 1) & 0xFFFFu;
+                if (top ^ ((byte >> k) & 1u)) reg ^= 0x1021u;
+            }
+        }
+        if (reg != 0) return;
+    }
+    int32_t next = 2 + (ext ? 2 : 0);
+    bool last = false, tidf = false;
+    uint32_t segno = 0, tid = 0;
+    if (seg) {
+        last = B(next) >> 7;
+        segno = ((B(next) & 0x7Fu) << 8) | B(next + 1);
+        next += 2;
+    }
+    if (ua) {
+        tidf = (B(next) >> 4) & 1u;
+        const uint32_t li = B(next) & 0xFu;
+        next += 1;
+        if (tidf) tid = (B(next) << 8) | B(next + 1);
+        next += (int32_t)li;
+    }
+    if (!tidf) return;
+    const int32_t dn = std::max(0, nb - next - (crcf ? 2 : 0));
+    process_mscGroup(dn ? g.data() + next : g.data(), dn, (uint8_t)(B(0) & 0xFu), last, (int32_t)segno, (uint16_t)tid);
+}
+
+motAssembler::element *motAssembler::getHandle(int32_t transportId) {        // mot-data.cpp:590-598
+    for (element &e : table_)
+        if (e.ordernumber != 0 && e.transportId == transportId) return &e;
+    return nullptr;
+}
+
+void motAssembler::process_mscGroup(const uint8_t *d, int32_t dn, uint8_t groupType, bool lastSegment,
+                                    int32_t segmentNumber, uint16_t transportId) {      // mot-data.cpp:679-728
+    const bool hdr = groupType == 3 && segmentNumber == 0;
+    if (!hdr && groupType != 4) {                                         // directory mode and the rest
+        otherTypes_++;
+        return;
+    }
+    auto B = [&](int32_t i) -> uint32_t { return i >= 0 && i < dn ? d[i] : 0u; };
+    const int32_t segmentSize = (int32_t)(((B(0) & 0x1Fu) << 8) | B(1));
+    if (dn < 2 || segmentSize + 2 > dn) {
+        malformed_++;
+        return;
+    }
+    if (!hdr) {
+        if (segmentNumber >= 100) {                                       // the reference writes past marked[100]
+            badSegments_++;
+            return;
+        }
+        processSegment(getHandle(transportId), d + 2, segmentNumber, segmentSize, lastSegment);
+        return;
+    }
+    const int32_t headerSize = (int32_t)(((B(5) & 0x0Fu) << 9) | B(6) | (B(7) >> 7));   // (:687-689, d[6] unshifted)
+    const int32_t bodySize = (int32_t)((B(2) << 20) | (B(3) << 12) | (B(4) << 4) | (B(5) >> 4));
+    if (getHandle(transportId)) return;                                   // processHeader (:56-133)
+    auto S = [&](int32_t i) -> uint32_t { return B(i + 2); };
+    const int32_t contentType = (int32_t)((S(5) >> 1) & 0x3Fu), contentsubType = (int32_t)(((S(5) & 1u) << 8) | S(6));
+    std::string name;
+    for (int32_t p = 7; p < headerSize;) {
+        const uint32_t PLI = S(p) >> 6, paramId = S(p) & 0x3Fu;
+        if (PLI == 0) {
+            p += 1;
+        } else if (PLI == 1) {
+            p += 2;
+        } else if (PLI == 2) {
+            p += 5;
+        } else {
+            int32_t length;
+            if (S(p + 1) & 0x80u) {
+                length = (int32_t)(((S(p + 1) & 0x7Fu) << 8) | S(p + 2));
+                p += 3;
+            } else {
+                length = (int32_t)(S(p + 1) & 0x7Fu);
+                p += 2;
+            }
+            if (paramId == 12)
+                for (int32_t i = 0; i < length - 1; i++) name.push_back((char)S(p + i + 1));
+            p += length;
+        }
+    }
+    // newEntry (:612-656): the first free entry, else the least ordernumber; the marks stay
+    element *e = nullptr;
+    for (element &t : table_)
+        if (t.ordernumber == 0) {
+            e = &t;
+            break;
+        }
+    if (!e) {
+        e = &table_[0];
+        for (element &t : table_)
+            if (t.ordernumber < e->ordernumber) e = &t;
+    }
+    e->ordernumber = ordernumber_++;
+    e->transportId = transportId;
+    e->bodySize = bodySize;
+    e->contentType = contentType;
+    e->contentsubType = contentsubType;
+    e->segmentSize = e->numofSegments = -1;
+    e->name = name;
+    e->tooLarge = bodySize > maxBody_;
+    e->body.assign(e->tooLarge ? 0 : (size_t)bodySize, 0);
+    if (!lastSegment) processSegment(e, d + 2 + headerSize, 0, segmentSize - headerSize, false);
+}
+
+void motAssembler::processSegment(element *h, const uint8_t *segment, int32_t n, int32_t size, bool lastFlag) {   // :278-312
+    if (!h || h->tooLarge || size < 0) return;
+    if (h->marked[n]) return;
+    if (!lastFlag && h->segmentSize == -1) h->segmentSize = size;
+    if (h->segmentSize == -1) return;
+    if ((int64_t)n * h->segmentSize + size > h->bodySize) return;
+    if (size) memcpy(h->body.data() + (size_t)n * h->segmentSize, segment, (size_t)size);
+    h->marked[n] = true;
+    if (lastFlag) h->numofSegments = n + 1;
+    if (h->numofSegments == -1) return;                                   // isComplete (:578-588)
+    for (int i = 0; i < h->numofSegments; i++)
+        if (!h->marked[i]) return;
+    object o;                                                             // handleComplete (:315-336)
+    o.kind = h->contentType == 2 ? SLIDE : h->contentType == 7 ? EPG : FILE_;
+    if (o.kind == SLIDE) {                                                // show_slide (:337-346)
+        if (oldSlide_)
+            for (int i = 0; i < h->numofSegments; i++) h->marked[i] = false;
+        oldSlide_ = true;
+    }
+    o.transportId = (uint16_t)h->transportId;
+    o.contentType = (uint8_t)h->contentType;
+    o.contentsubType = (uint16_t)h->contentsubType;
+    o.name = h->name;
+    if (o.kind != EPG) o.body = h->body;
+    objects_++;
+    if (cb_) cb_(o);
+}
+
 }  // namespace dabgpu

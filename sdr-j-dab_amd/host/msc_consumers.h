@@ -1,15 +1,17 @@
 // msc_consumers.h -- what the reference does with the decoded MSC bits of a
 // subchannel, minus the codecs: the plug-in interfaces (dabVirtual, dabProcessor),
-// the MPEG-1/2 layer II frame synchroniser of mp2Processor (mp2processor.cpp:572-629)
-// and the packet-mode data-group assembly of mscDatagroup (msc-datagroup.cpp:221-339).
+// the MPEG-1/2 layer II frame synchroniser of mp2Processor (mp2processor.cpp:572-629),
+// the packet-mode data-group assembly of mscDatagroup (msc-datagroup.cpp:221-339) and
+// motHandler's header mode (mot-data.cpp:679-728).
 // Host code (a few bit operations per decoded bit, after the GPU's Viterbi): no Qt,
-// no kjmp2 / faad / MOT / IP handlers -- complete frames and data groups go to
+// no kjmp2 / faad / IP handlers -- complete frames, data groups and MOT objects go to
 // callbacks instead.  Same state machines and quirks as the reference.
 #pragma once
 #include <atomic>
 #include <cstdint>
 #include <cstdio>
 #include <functional>
+#include <string>
 #include <vector>
 
 namespace dabgpu {
@@ -91,6 +93,56 @@ private:
     int32_t streamAddress_ = -1;
     std::vector<uint8_t> series_;
     int32_t crcErrors_ = 0, handledPackets_ = 0, datagroups_ = 0;
+};
+
+// motHandler in header mode (mot-data.cpp:679-728: processHeader, processSegment, newEntry,
+// getHandle, isComplete, handleComplete, show_slide) behind mot_databuilder::add_mscDatagroup
+// (mot-databuilder.cpp:37-95): MSC data groups in, slides and files out through a callback
+// where the reference emits the_picture or fopens.  The same function, byte for byte, as the
+// GPU's MOT layer (dabgpu_mot_groups in include/dabgpu.h, whose rules 1-6 for what the
+// reference leaves undefined hold here too: bytes past a group read 0, segment numbers >= 100
+// and malformed groups are dropped and counted, sizes are int32, bodies above max_body_bytes
+// are refused, directory mode -- group type 6 -- is counted and ignored).
+class motAssembler {
+public:
+    enum { SLIDE = 1, EPG = 2, FILE_ = 3 };
+    struct object {
+        int kind;                       // SLIDE, EPG (contentType 7: nothing is delivered, body empty) or FILE_
+        uint16_t transportId;
+        uint8_t contentType;
+        uint16_t contentsubType;
+        std::string name;               // the whole name (the GPU record keeps its first 128 bytes)
+        std::vector<uint8_t> body;
+    };
+    using object_cb = std::function<void(const object &)>;
+    explicit motAssembler(object_cb cb, int32_t max_body_bytes = 65536);
+    // one MSC data group, one bit per byte, as packetAssembler delivers it
+    void add_mscDatagroup(const std::vector<uint8_t> &bits);
+    // motHandler::process_mscGroup on a data field of nbytes bytes
+    void process_mscGroup(const uint8_t *data, int32_t nbytes, uint8_t groupType, bool lastSegment, int32_t segmentNumber,
+                          uint16_t transportId);
+    int32_t objects() const { return objects_; }
+    int32_t malformed() const { return malformed_; }
+    int32_t badSegments() const { return badSegments_; }
+    int32_t otherTypes() const { return otherTypes_; }
+    int32_t entries() const;
+private:
+    struct element {                    // motElement (mot-data.h:33-44); ordernumber 0: free
+        int32_t ordernumber = 0, transportId = 0, bodySize = 0, segmentSize = -1, numofSegments = -1;
+        int32_t contentType = 0, contentsubType = 0;
+        bool tooLarge = false;
+        bool marked[100] = {};
+        std::string name;
+        std::vector<uint8_t> body;
+    };
+    element *getHandle(int32_t transportId);
+    void processSegment(element *h, const uint8_t *segment, int32_t segmentNumber, int32_t segmentSize, bool lastFlag);
+    object_cb cb_;
+    int32_t maxBody_;
+    element table_[16];
+    int32_t ordernumber_ = 1;
+    bool oldSlide_ = false;
+    int32_t objects_ = 0, malformed_ = 0, badSegments_ = 0, otherTypes_ = 0;
 };
 
 }  // namespace dabgpu

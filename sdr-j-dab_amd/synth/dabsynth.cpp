@@ -314,7 +314,59 @@ struct PacketState {
     std::vector<uint8_t> group;    // rest of the data group in flight
     bool started = false;          // its first packet went out
     int cont = 0;
+    std::vector<std::vector<uint8_t>> carousel;   // DABSYNTH_MOT: the groups sent round and round
+    size_t next = 0;
 };
+
+// an MSC data group with segment and user-access fields, transport id and CRC
+std::vector<uint8_t> mot_group(int type, int tid, int segno, bool last, const std::vector<uint8_t> &segment) {
+    std::vector<uint8_t> g = {(uint8_t)(0x70 | type), 0, (uint8_t)((last ? 0x80 : 0) | (segno >> 8)), (uint8_t)(segno & 0xFF),
+                              0x12, (uint8_t)(tid >> 8), (uint8_t)(tid & 0xFF)};
+    g.push_back((uint8_t)(segment.size() >> 8));          // repetition count 0, segment size
+    g.push_back((uint8_t)(segment.size() & 0xFF));
+    g.insert(g.end(), segment.begin(), segment.end());
+    const uint16_t c = (uint16_t)~crc_ccitt(g.data(), (int)g.size());
+    g.push_back((uint8_t)(c >> 8));
+    g.push_back((uint8_t)(c & 0xFF));
+    return g;
+}
+// A small MOT slide carousel in header mode (EN 301 234): objects 0..2 each as a header group
+// (type 3) and body segments of 100 bytes (type 4), everything sent twice in a row; object 3
+// with header and body in one segment that is not flagged last, then its last segment.  The
+// header-size field holds twice the header's length: the receiver this signal is made for
+// reads the field without the shift of its middle byte, and so walks exactly the header.
+void make_mot_carousel(uint64_t seed, int sub, std::vector<std::vector<uint8_t>> &out) {
+    Rng rng(seed ^ (0x4D4F54ull << 20) ^ (uint64_t)sub);
+    for (int o = 0; o < 4; o++) {
+        const int tid = 0x1000 + 16 * sub + o, nbody = o == 3 ? 150 : 230 + 35 * o;
+        std::vector<uint8_t> body(nbody);
+        for (auto &b : body) b = (uint8_t)rng.next();
+        char nm[16];
+        const int nl = std::snprintf(nm, sizeof nm, "s%d_%d.jpg", sub, o);
+        std::vector<uint8_t> h(7);
+        const int hs = 2 * (7 + 3 + nl);
+        h.push_back(0xC0 | 12), h.push_back((uint8_t)(nl + 1)), h.push_back(0x40);
+        h.insert(h.end(), nm, nm + nl);
+        h[0] = (uint8_t)(nbody >> 20), h[1] = (uint8_t)(nbody >> 12), h[2] = (uint8_t)(nbody >> 4);
+        h[3] = (uint8_t)(((nbody & 15) << 4) | ((hs >> 9) & 15));
+        h[4] = (uint8_t)(hs >> 1);
+        h[5] = (uint8_t)(((hs & 1) << 7) | (2 << 1));       // content type 2 (image), subtype 1 (JFIF)
+        h[6] = 1;
+        std::vector<std::vector<uint8_t>> obj;
+        if (o == 3) {
+            std::vector<uint8_t> seg = h;
+            seg.insert(seg.end(), body.begin(), body.begin() + 100);
+            obj.push_back(mot_group(3, tid, 0, false, seg));
+            obj.push_back(mot_group(4, tid, 1, true, std::vector<uint8_t>(body.begin() + 100, body.end())));
+        } else {
+            obj.push_back(mot_group(3, tid, 0, true, h));
+            for (int k = 0; 100 * k < nbody; k++)
+                obj.push_back(mot_group(4, tid, k, 100 * (k + 1) >= nbody,
+                                        std::vector<uint8_t>(body.begin() + 100 * k, body.begin() + std::min(nbody, 100 * (k + 1)))));
+        }
+        for (int r = 0; r < 2; r++) out.insert(out.end(), obj.begin(), obj.end());
+    }
+}
 void make_packet_cif(Rng &rng, PacketState &st, int bitRate, int addr, uint8_t *info) {
     const int nbytes = 3 * bitRate;
     std::vector<uint8_t> out(nbytes, 0);
@@ -328,7 +380,10 @@ void make_packet_cif(Rng &rng, PacketState &st, int bitRate, int addr, uint8_t *
         const bool padding = rng.next() % 8 == 0;
         int fl = 0, useful = 0, a = 0;
         if (!padding) {
-            if (st.group.empty()) {
+            if (st.group.empty() && !st.carousel.empty()) {
+                st.group = st.carousel[st.next++ % st.carousel.size()];
+                st.started = false;
+            } else if (st.group.empty()) {
                 st.group.resize(20 + rng.next() % 300);
                 for (auto &b : st.group) b = (uint8_t)rng.next();
                 st.started = false;
@@ -451,7 +506,7 @@ static void make_fig_fib(const dabsynth_cfg *cfg, int64_t n, uint8_t *fib) {
         }
         w.put(0, 3), w.put(6, 5), w.put(0, 3), w.put(2, 5);
         w.put(0xC000 + i, 16), w.put(0, 1), w.put(0, 3), w.put(1, 4);
-        if (!sc.dabplus && sc.content == DABSYNTH_PACKET) {
+        if (!sc.dabplus && (sc.content == DABSYNTH_PACKET || sc.content == DABSYNTH_MOT)) {
             // packet-mode component (TMid 3, SCId 0x400 + i), then FIG 0/3: SCId -> DG flag 0,
             // DSCTy 60 (MOT), sub-channel i, packet address 0x100 + i
             w.put(3, 2), w.put(0x400 + i, 12), w.put(1, 1), w.put(0, 1);
@@ -509,7 +564,8 @@ static int gen_core(const dabsynth_cfg *cfg, uint64_t seed, int P, float *iq, ui
         const dabsynth_subch &sc = cfg->subch[s];
         int nb = 24 * sc.bitRate;
         if (cyc && sc.dabplus && NC % 5) return -3;      // superframes must tile the period
-        if (cyc && !sc.dabplus && sc.content == DABSYNTH_PACKET) return -4;   // groups do not wrap (dabsynth.h)
+        if (cyc && !sc.dabplus && (sc.content == DABSYNTH_PACKET || sc.content == DABSYNTH_MOT)) return -4;   // groups do not wrap (dabsynth.h)
+        if (!sc.dabplus && sc.content == DABSYNTH_MOT) make_mot_carousel(seed, s, pst[s].carousel);
         frag_len[s] = sc.length * 64;
         enc_frag[s].assign((size_t)NE * frag_len[s], 0);
         std::vector<uint8_t> info(nb), mother(4 * (nb + 6)), punct(std::max<size_t>(frag_len[s], mother.size()));
@@ -572,7 +628,7 @@ static int gen_core(const dabsynth_cfg *cfg, uint64_t seed, int P, float *iq, ui
                 }
             } else if (sc.content == DABSYNTH_MP2) {
                 make_mp2_frame(rng, sc.bitRate, info.data());
-            } else if (sc.content == DABSYNTH_PACKET) {
+            } else if (sc.content == DABSYNTH_PACKET || sc.content == DABSYNTH_MOT) {
                 make_packet_cif(rng, pst[s], sc.bitRate, 0x100 + s, info.data());
             } else {
                 for (int i = 0; i < nb; i++) info[i] = rng.bit();

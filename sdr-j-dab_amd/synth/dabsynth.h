@@ -33,6 +33,10 @@ typedef struct {
                             12 ones in a row); DABSYNTH_PACKET: packet mode, 24..96-byte packets with
                             CRCs carrying MSC data groups (address 0x100 + subchannel index, some
                             padding packets), announced as DSCTy 60 by FIG 0/2 (TMid 3) + FIG 0/3;
+                            DABSYNTH_MOT: the same, the groups being a seeded MOT slide carousel in
+                            header mode (four objects, transport ids 0x1000 + 16 * subchannel + k:
+                            header groups, 100-byte body segments, every object sent twice, the
+                            last with header and body in one segment);
                             with dabplus: 0 every superframe dacRate 0 / SBR 0 (4 AUs),
                             DABSYNTH_AU_MIX the superframes cycle through the four (dacRate, SBR)
                             layouts of mp4processor.cpp:163-195 (4, 2, 6, 3 AUs) */
@@ -40,6 +44,7 @@ typedef struct {
 #define DABSYNTH_MP2 2
 #define DABSYNTH_PACKET 3
 #define DABSYNTH_AU_MIX 4
+#define DABSYNTH_MOT 5
 
 typedef struct {
     int32_t n_frames;    /* frames after the pre-roll */
