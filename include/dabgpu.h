@@ -194,6 +194,51 @@ typedef struct {            /* a motElement (mot-data.h:33-44) */
 #define DABGPU_MOT_ARENA_BYTES(n_frames, max_bitrate, max_body_bytes) \
     DABGPU_MOT_ARENA_FOR(DABGPU_PKT_GROUP_SLOTS(n_frames, max_bitrate), max_body_bytes)
 
+#define DABGPU_SUBCH_PAD     32  /* feed the DAB+ entry's good AUs to the PAD layer (dabgpu_pipe_pad); only together
+                                    with DABGPU_SUBCH_DABPLUS (DABGPU_E_ARG otherwise).  PAD slot j of a stream is
+                                    its j-th entry so flagged. */
+/* One showLabel emission of padHandler::dynamicLabel (pad-handler.cpp:231-267).  text holds the
+ * bytes the reference passed to toQStringUsingCharset, piece after piece, since the last clear,
+ * unconverted; charset is charSet at the emission; piece_len keeps the boundaries of those
+ * calls, so a caller that owns the reference's charsets.cpp reproduces the QString exactly:
+ * clear, then append the conversion of each piece.  (No character table is part of the product.) */
+#define DABGPU_PAD_LABEL_BYTES  256
+#define DABGPU_PAD_LABEL_PIECES 64
+typedef struct {
+    int32_t cif;            /* of the AU that completed the label (dabgpu_pad_aus: see cif_d; dabgpu_pipe_pad: the
+                               CIF slot in the run of the AU's superframe) */
+    int32_t au;             /* that AU's index: in the call (dabgpu_pad_aus), in its superframe (dabgpu_pipe_pad) */
+    int32_t charset;
+    int32_t nbytes;         /* the full length; text holds the first DABGPU_PAD_LABEL_BYTES */
+    int32_t n_pieces;       /* the full count; piece_len holds the first DABGPU_PAD_LABEL_PIECES */
+    int32_t flags;          /* DABGPU_PAD_LABEL_TRUNCATED */
+    uint8_t piece_len[DABGPU_PAD_LABEL_PIECES];     /* each piece's full length (1..48) */
+    uint8_t text[DABGPU_PAD_LABEL_BYTES];
+} dabgpu_pad_label;
+#define DABGPU_PAD_LABEL_TRUNCATED 1
+/* One padHandler after a dabgpu_pad_aus call */
+typedef struct {
+    int32_t n_labels;       /* labels shown in the run (records: the first label_slots of them) */
+    int32_t n_groups;       /* X-PAD data groups completed (records: the first group_slots) */
+    int32_t n_bytes;        /* their stored bytes, packed back to back from offset 0 */
+    int32_t aus;            /* good AUs seen (length >= 0) */
+    int32_t pads;           /* processPAD calls: AUs that open with a data stream element */
+    int32_t unhandled;      /* PADs left at the first application type outside {1, 2, 3, 12, 13} (:141-145) */
+    int32_t undefined[4];   /* PADs that met rule 1, 2, 3, 4 of dabgpu_pad_aus (a PAD counts once per rule) */
+    int32_t crc_failed;     /* completed groups whose pad_crc failed */
+    int32_t guard_dropped;  /* sub-fields add_MSC_element dropped at its 8192 guard (:285-288) */
+    int32_t rejected_sf;    /* dabgpu_pipe_pad: status-2 superframes skipped (their AUs are not stored); else 0 */
+    int32_t reserved[3];
+} dabgpu_pad_run;
+/* Sizes per padHandler for the AUs a run of n_frames frames can complete: a superframe holds at most 6 AUs;
+ * a PAD carries at most four content indicators, and each sub-field shows at most one label or
+ * completes at most one group; a group's bytes never exceed what was appended since its length
+ * indicator: at most 8191 bytes carried, plus 4 x 48 bytes per AU. */
+#define DABGPU_PAD_AU_SLOTS(n_frames)    (DABGPU_SF_SLOTS(n_frames) * 6)
+#define DABGPU_PAD_LABEL_SLOTS(n_frames) (4 * DABGPU_PAD_AU_SLOTS(n_frames))
+#define DABGPU_PAD_GROUP_SLOTS(n_frames) (4 * DABGPU_PAD_AU_SLOTS(n_frames))
+#define DABGPU_PAD_ARENA_BYTES(n_frames) ((8192 + DABGPU_PAD_AU_SLOTS(n_frames) * 192 + 15) / 16 * 16)
+
 /* One CIF of one classic-audio subchannel through mp2Processor::addtoFrame
  * (mp2processor.cpp:572-617) and, when a frame completed in it, mp2decodeFrame (:365-568). */
 typedef struct {
@@ -484,6 +529,83 @@ int dabgpu_mot_groups(dabgpu_ctx *ctx, void *state_d, int n_slots, int max_body_
                       const dabgpu_packet_run *run_d, dabgpu_mot_object *objects_d, uint8_t *out_d,
                       int64_t out_arena_bytes, dabgpu_mot_run *mot_run_d);
 
+/* padHandler::processPAD (pad-handler.cpp) batched: n_slots independent padHandlers, each
+ * taking its n_aus AUs in order, fed as mp4Processor feeds them (mp4processor.cpp:237-265).
+ *   state_d   [n_slots][dabgpu_pad_state_bytes()], opaque, all zero for a new padHandler,
+ *             updated in place (16-byte aligned)
+ *   aus_d     [n_slots][n_aus][au_stride] bytes; len_d int32 [n_slots][n_aus]: the AU's
+ *             aac_frame_length; negative: the AU failed its CRC and is skipped.  Bytes past an
+ *             AU's length (and past au_stride) read 0: the reference copies the AU into a zeroed
+ *             theAU[1920].  An AU whose (byte0 >> 5) & 7 != 4 -- no data stream element first
+ *             -- is counted (aus) and ignored (:264).
+ *   cif_d     int32 [n_slots][n_aus] or NULL: the value records carry as `cif` (NULL: the AU's
+ *             index in the call)
+ *   labels_d  [n_slots][label_slots], groups_d [n_slots][group_slots], bytes_d
+ *             [n_slots][arena_bytes], run_d [n_slots]
+ * Labels are dabgpu_pad_label records.  X-PAD groups are dabgpu_datagroup records plus bytes in
+ * the packet layer's layout, so groups_d / bytes_d feed dabgpu_mot_groups unchanged (with a
+ * dabgpu_packet_run whose n_groups is this run's).  The header is as build_MSC_segment parses it
+ * (:299-357): every completed group is recorded, and DABGPU_DG_ACCEPTED is set exactly for the
+ * groups it hands to process_mscGroup: CRC flag clear or pad_crc good; group type 3 or 4; a
+ * user access field, if present, has the transport-id flag.  A group without the segment flag
+ * has segmentNumber 0xFFFF (the reference's -1), one without a user access field transportId
+ * 0xFFFF (the reference's int16_t -1 through a uint16_t parameter) with DABGPU_DG_TRANSPORT set
+ * -- the reference passes it on -- and DABGPU_DG_USER_ACCESS clear.  nbytes is
+ * msc_dataGroupLength, data_offset the reference's index (for a group it returns from early,
+ * what index would be: the fields are parsed regardless; a user access field without the
+ * transport-id flag leaves index at that field), data_nbytes = max(0, length - index - (CRC flag
+ * ? 2 : 0)), CI the reference's continuityIndex, (b[1] & 0xF) >> 4, which is always 0,
+ * reserved[0] the AU's index in the call (modulo 256; dabgpu_pipe_pad: its index in its superframe).
+ * Kept bit for bit from the reference:
+ *   - processPAD: count = AU[1] (255 is not an escape), the PAD is AU[2 .. 2+count); only
+ *     F-PAD type 0; X-PAD indicator 1 is short, 2 variable, anything else is ignored;
+ *   - short PAD (:73-82): the CI is always read at count-3, the data is the three bytes below
+ *     it, reversed; only application types 2 and 3;
+ *   - variable PAD (:97-173): CI flag 0 ignored; up to four CIs, an end marker costs one byte;
+ *     sub-fields reversed, lengths 4, 6, 8, 12, 16, 24, 32, 48; type 1 always takes 4 bytes,
+ *     sets length and index and does `continue` (without the :168 check); the first type
+ *     outside {1, 2, 3, 12, 13} records itself in last_appType and drops the rest of the PAD;
+ *     type 12 is taken only after type 1, type 13 only after 12 or 13;
+ *   - dynamicLabel (:177-269) entirely: the first / last / C flags, charSet set only by a
+ *     first segment, the clear command, moreXPad / remainDataLength / isLastSegment, and the
+ *     stale moreXPad a clear command leaves behind (type-3 sub-fields after it are appended to
+ *     the cleared text).  Its five function-local statics are per-handler state here: a process
+ *     with one padHandler cannot tell the difference, and a new handler starts them at their
+ *     initialisers;
+ *   - add_MSC_element (:274-297, MOT_BASICS__ defined, as both of the reference's build files
+ *     do): index < 0 returns; a sub-field with index + length >= 8192 is dropped; completion at
+ *     index >= msc_dataGroupLength, with that many bytes; index then goes back to 0, so further
+ *     type-13 sub-fields fill a new group of the same length;
+ *   - pad_crc (:360-381): CRC-16 0x1021 from all ones over length - 2 bytes against the
+ *     complement of the last two.  Its left shifts of a negative int16_t are undefined before
+ *     C++20; what is computed is the two's-complement result C++20 defines (and the pin is
+ *     compiled as C++20 for that reason).
+ * Where the reference is undefined or unbounded; each PAD that meets a rule is counted:
+ *   1. count < 2: the PAD is ignored (the reference reads buffer[-1] or buffer[-2]);
+ *   2. a read below byte 0 of the PAD reads 0, control flow otherwise the reference's, its
+ *      :168-171 check included (a short PAD with count < 6, a sub-field or a length indicator
+ *      longer than what is left, CIs down to byte 0);
+ *   3. a new handler has last_appType 0, no group in progress (index -1: a type-13 sub-field
+ *      that reaches add_MSC_element before any length indicator returns there), length 0,
+ *      charSet 0 and a zeroed 8192-byte buffer.  The buffer is part of the state: header
+ *      fields past a short group's end read its stale bytes, as in the reference (counted only
+ *      where the byte was never written).  A group with the CRC flag and a length below 2 has
+ *      a bad CRC.  For a group's data field rule 1 of dabgpu_mot_groups applies downstream;
+ *   4. the label text is unbounded in the reference while segments without `first` keep
+ *      arriving: past DABGPU_PAD_LABEL_BYTES bytes or DABGPU_PAD_LABEL_PIECES pieces the record
+ *      keeps the first bytes and pieces, reports the full nbytes and n_pieces and sets
+ *      DABGPU_PAD_LABEL_TRUNCATED.
+ * Beyond the slots: labels and groups past label_slots / group_slots are counted and not
+ * recorded; a group that does not fit the arena is recorded without bytes, flagged
+ * DABGPU_DG_TRUNCATED and not accepted (neither happens with the DABGPU_PAD_* sizes).
+ * DABGPU_E_ARG for negative sizes, an arena below DABGPU_PAD_ARENA_BYTES(0) or of 2 GiB and
+ * more.  Asynchronous on the context stream. */
+size_t dabgpu_pad_state_bytes(void);
+int dabgpu_pad_aus(dabgpu_ctx *ctx, void *state_d, int n_slots, const uint8_t *aus_d, int64_t au_stride,
+                   const int32_t *len_d, int n_aus, const int32_t *cif_d, dabgpu_pad_label *labels_d, int label_slots,
+                   dabgpu_datagroup *groups_d, int group_slots, uint8_t *bytes_d, int64_t arena_bytes,
+                   dabgpu_pad_run *run_d);
+
 /* ---- streaming pipeline (ofdmProcessor::run + ficHandler + mscHandler) ---
  * n_streams independent ensembles; each call decodes n_frames frames per
  * stream.  Sync, AFC, DQPSK references and the 16-CIF time de-interleaver
@@ -565,8 +687,9 @@ int dabgpu_pipe_create_caps(dabgpu_ctx *ctx, const dabgpu_pipe_cfg *cfg, const d
  * bitRate, DABGPU_E_ARG for an entry outside its CUs, for n > max_subch, a bitRate above
  * max_bitrate, more DAB+ entries than max_dabplus, more layer II entries than max_mp2, more
  * packet-mode entries than dabgpu_pipe_packet_caps allows, more MOT entries than
- * dabgpu_pipe_mot_caps allows, an entry flagged DABGPU_SUBCH_MOT without DABGPU_SUBCH_PACKET or
- * an entry flagged for two layers;
+ * dabgpu_pipe_mot_caps allows, an entry flagged DABGPU_SUBCH_MOT without DABGPU_SUBCH_PACKET, more
+ * PAD entries than dabgpu_pipe_pad_caps allows, an entry flagged DABGPU_SUBCH_PAD without
+ * DABGPU_SUBCH_DABPLUS or an entry flagged for two layers;
  * DABGPU_E_UNSUP for a packet-mode bitRate that is no multiple of 8; on any error the table
  * is unchanged.  (A packet-mode entry that is not unchanged is a new mscDatagroup, and a new
  * motHandler when it is flagged DABGPU_SUBCH_MOT; an unchanged one keeps both.)
@@ -702,6 +825,33 @@ int dabgpu_pipe_mot(dabgpu_pipe *p, uint8_t *bytes_d, dabgpu_mot_object *objects
  * DABGPU_MOT_TOO_LARGE).  DABGPU_E_ARG for negative values, max_mot > max_packet,
  * max_body_bytes > 1 << 24 or fewer slots than an applied table flags. */
 int dabgpu_pipe_mot_caps(dabgpu_pipe *p, int max_mot, int max_body_bytes);
+/* PAD layer for the AUs of the run's dabgpu_pipe_dabplus call (call once per run, after it):
+ * dabgpu_pad_aus for every entry flagged DABGPU_SUBCH_DABPLUS | DABGPU_SUBCH_PAD, PAD slot j of
+ * a stream being its j-th such entry.  sf_bytes_d, sf_stride and info_d are those of that call
+ * (DABGPU_E_ARG otherwise), sparse or compact as it wrote them; they are read (keep them alive
+ * until the run's work is done) and never written.  Taken are the AUs of status-3 superframes in
+ * CIF and AU order: AU i is aac_frame_length = au_start[i+1] - au_start[i] - 2 bytes from
+ * au_start[i], skipped where au_crc_ok has its bit clear.  One stated limit: k_dp_layer stores
+ * no bytes for a superframe rejected for an impossible AU table (status 2), whose earlier AUs the
+ * reference would already have processed: such superframes are counted in rejected_sf and
+ * skipped.  The padHandlers are carried across runs; dabgpu_pipe_set_subch keeps the one of an
+ * unchanged entry and gives every other entry a new one.  Outputs (device):
+ *   labels_d [n_streams][max_pad][DABGPU_PAD_LABEL_SLOTS(n_frames)]
+ *   groups_d [n_streams][max_pad][DABGPU_PAD_GROUP_SLOTS(n_frames)]
+ *   bytes_d  [n_streams][max_pad][DABGPU_PAD_ARENA_BYTES(n_frames)]
+ *   run_d    [n_streams][max_pad]
+ * Runs on the run's back-end stream behind the DAB+ layer.  DABGPU_E_STATE without a layer
+ * (max_pad == 0), without a dabgpu_pipe_dabplus call for the run, or on a second call.
+ * X-PAD slides inside the pipeline are not part of this: dabgpu_mot_groups on these groups is
+ * the path. */
+int dabgpu_pipe_pad(dabgpu_pipe *p, const uint8_t *sf_bytes_d, int32_t sf_stride, const dabgpu_superframe *info_d,
+                    dabgpu_pad_label *labels_d, dabgpu_datagroup *groups_d, uint8_t *bytes_d, dabgpu_pad_run *run_d);
+/* Size the PAD layer: max_pad slots per stream (<= max_dabplus).  Both create calls start with
+ * the number of flagged entries of their table; with max_pad == 0 nothing is allocated or
+ * launched.  Between runs; waits for everything enqueued.  The state of the slots both sizes
+ * hold is kept.  DABGPU_E_ARG for a negative value, max_pad > max_dabplus or fewer slots than an
+ * applied table flags. */
+int dabgpu_pipe_pad_caps(dabgpu_pipe *p, int max_pad);
 /* Compact superframe bytes for the following dabgpu_pipe_dabplus calls (on = 1): only the
  * superframes that complete in the run are stored, per (stream, DAB+ subchannel) in CIF
  * order -- sf_bytes_d [n_streams][n_dabplus][DABGPU_SF_SLOTS(n_frames)][sf_stride], the

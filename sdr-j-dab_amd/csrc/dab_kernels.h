@@ -304,6 +304,46 @@ struct MotJob {
     int32_t *nops;                  // [n_slots]
 };
 
+// PAD layer (k_pad.hip): n_slots padHandlers, each over its AUs in order
+constexpr int PAD_BUFFER = 8192;    // msc_dataGroupBuffer
+struct PadState {                   // a padHandler's carried state; all zero: a new one
+    int32_t last_appType, last_set; // last_appType, and whether anything has written it (rule 3)
+    int32_t started, index, length; // a length indicator has been seen; msc_dataGroupIndex / msc_dataGroupLength
+    int32_t hiwater;                // bytes of the buffer ever written (rule 3)
+    int32_t charset, cs_set;
+    int32_t remain, is_last, more;  // dynamicLabel's statics remainDataLength, isLastSegment, moreXPad
+    int32_t text_nbytes, text_npieces;  // dynamicLabelText: the full counts
+    int32_t reserved[3];
+    uint8_t piece_len[DABGPU_PAD_LABEL_PIECES];
+    uint8_t text[DABGPU_PAD_LABEL_BYTES];
+    uint8_t buffer[PAD_BUFFER];
+};
+static_assert(sizeof(PadState) == 64 + 64 + 256 + 8192 && sizeof(PadState) % 16 == 0 && sizeof(dabgpu_pad_label) == 344 &&
+                  sizeof(dabgpu_pad_run) == 64 && sizeof(dabgpu_datagroup) == 32,
+              "the PAD records are read as bytes by the bindings");
+struct PadJob {
+    int32_t n_slots, n_aus;
+    uint8_t *state;                 // [n_slots] PadState
+    const uint8_t *aus;             // [n_slots][n_aus][au_stride]
+    int64_t au_stride;
+    const int32_t *len;             // [n_slots][n_aus] aac_frame_length, negative: skipped
+    const int32_t *cif;             // optional [n_slots][n_aus]: the records' cif (NULL: the AU's index)
+    // the pipeline's source instead of aus / len (info != NULL): the outputs of a dabgpu_pipe_dabplus call
+    const dabgpu_superframe *info;  // [S][ncif][ndp]
+    const uint8_t *sf;              // sparse [S][ncif][ndp][sf_stride], or compact [S][ndp][kmax][sf_stride]
+    int32_t sf_stride, kmax;        // kmax 0: sparse
+    int32_t ncif, ndp;
+    const int32_t *src;             // [n_slots]: the DAB+ slot (s * ndp + j) a handler reads, -1: absent
+    dabgpu_pad_label *labels;       // [n_slots][label_slots]
+    int32_t label_slots;
+    dabgpu_datagroup *groups;       // [n_slots][group_slots]
+    int32_t group_slots;
+    uint8_t *bytes;                 // [n_slots][arena]
+    int64_t arena;                  // < 2^31
+    dabgpu_pad_run *run;            // [n_slots]
+};
+
+
 // iq: samples in format fmt (DABGPU_IQ_*); frame descriptors count samples
 hipError_t launch_prs_sync(hipStream_t st, const void *iq, int fmt, const dabgpu_frame *fr, int n, const OfdmTables &T,
                            int level, int32_t *si, float *mx, float *sm, bool general);
@@ -340,5 +380,6 @@ hipError_t launch_mp2_decode(hipStream_t st, const Mp2Job &job);
 hipError_t launch_mp2_sync(hipStream_t st, const Mp2SyncJob &job);
 hipError_t launch_packet(hipStream_t st, const PkJob &job);
 hipError_t launch_mot(hipStream_t st, const MotJob &job);
+hipError_t launch_pad(hipStream_t st, const PadJob &job);
 
 }  // namespace dab

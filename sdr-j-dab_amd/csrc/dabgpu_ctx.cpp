@@ -750,6 +750,38 @@ int dabgpu_mp2_decode(dabgpu_ctx *c, const uint8_t *frames, int64_t frame_stride
     return 0;
 }
 
+size_t dabgpu_pad_state_bytes(void) { return sizeof(PadState); }
+
+int dabgpu_pad_aus(dabgpu_ctx *c, void *state, int n_slots, const uint8_t *aus, int64_t au_stride, const int32_t *len,
+                   int n_aus, const int32_t *cif, dabgpu_pad_label *labels, int label_slots, dabgpu_datagroup *groups,
+                   int group_slots, uint8_t *bytes, int64_t arena_bytes, dabgpu_pad_run *run) {
+    if (!c || !state || !labels || !groups || !bytes || !run || n_slots < 0 || n_aus < 0 || au_stride < 0 || label_slots < 0 ||
+        group_slots < 0 || (n_aus && (!aus || !len)))
+        return fail(DABGPU_E_ARG, "bad args");
+    if (arena_bytes < DABGPU_PAD_ARENA_BYTES(0) || arena_bytes > 0x7FFFFFFF)
+        return fail(DABGPU_E_ARG, "arena_bytes %lld", (long long)arena_bytes);
+    if ((uintptr_t)state & 15) return fail(DABGPU_E_ARG, "state_d must be 16-byte aligned");
+    if (!n_slots) return 0;
+    PadJob J;
+    memset(&J, 0, sizeof J);
+    J.n_slots = n_slots;
+    J.n_aus = n_aus;
+    J.state = (uint8_t *)state;
+    J.aus = aus;
+    J.au_stride = au_stride;
+    J.len = len;
+    J.cif = cif;
+    J.labels = labels;
+    J.label_slots = label_slots;
+    J.groups = groups;
+    J.group_slots = group_slots;
+    J.bytes = bytes;
+    J.arena = arena_bytes;
+    J.run = run;
+    HIPCHK(launch_pad(c->stream, J));
+    return 0;
+}
+
 size_t dabgpu_mot_state_bytes(int max_body_bytes) {
     if (max_body_bytes < 0 || max_body_bytes > (1 << 24)) return 0;
     const size_t cap = ((size_t)(max_body_bytes ? max_body_bytes : DABGPU_MOT_BODY_BYTES) + 15) / 16 * 16;

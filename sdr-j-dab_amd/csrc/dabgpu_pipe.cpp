@@ -101,9 +101,17 @@ struct MotLayer {
     Event ev;                     // the last pass
 };
 
+// PAD layer (a padHandler per DAB+ entry flagged DABGPU_SUBCH_PAD and stream): allocated only
+// while dabgpu_pipe_pad_caps' max_pad > 0
+struct PadLayer {
+    DevBuf<uint8_t> state_d;      // [S][NPAD] PadState, the padHandlers, updated in place
+    DevBuf<int32_t> src_d;        // [S][NPAD] the DAB+ slot (s * NDP + j) each reads, -1: absent
+    Event ev;                     // the last pass
+};
+
 struct dabgpu_pipe {
     dabgpu_ctx *c = nullptr;
-    int S = 0, F = 0, NSUB = 0, R = 0, NDP = 0, NMP = 0, NPK = 0, NMOT = 0;
+    int S = 0, F = 0, NSUB = 0, R = 0, NDP = 0, NMP = 0, NPK = 0, NMOT = 0, NPAD = 0;
     int16_t threshold = 3;
     int16_t method = 1;              // freqSyncMethod
     bool scan = false;               // scanMode (No_Signal_Found after > 5 attempts)
@@ -175,6 +183,13 @@ struct dabgpu_pipe {
     const dabgpu_datagroup *pk_groups = nullptr;
     const dabgpu_packet_run *pk_run = nullptr;
     bool mot_pending = false;        // ... have not entered the MOT layer yet
+    PadLayer pad;
+    // the outputs of the run's dabgpu_pipe_dabplus call, which dabgpu_pipe_pad reads
+    const uint8_t *dp_sf = nullptr;
+    const dabgpu_superframe *dp_info = nullptr;
+    int32_t dp_sf_stride = 0;
+    bool dp_sf_compact = false;
+    bool pad_pending = false;        // ... have not entered the PAD layer yet
     const uint8_t *last_msc = nullptr; // MSC bits of the last run
     bool dp_pending = false, mp2_pending = false, pk_pending = false;   // the last run's CIFs have not entered the layer yet
     int32_t last_msc_stride = 0;
@@ -281,12 +296,16 @@ static int acq_async_setup(dabgpu_pipe *p) {
 // A subchannel table against the reference's definitions and the pipeline's caps
 // (dabgpu_pipe_create_caps and dabgpu_pipe_set_subch validate alike)
 static int check_table(const dabgpu_subch *sub, int n, int max_subch, int max_bitrate, int max_dabplus, int max_mp2,
-                       int max_packet, int max_mot) {
+                       int max_packet, int max_mot, int max_pad) {
     if (n < 0 || (n > 0 && !sub)) return fail(DABGPU_E_ARG, "bad subchannel table");
     if (n > max_subch) return fail(DABGPU_E_ARG, "%d subchannels, the pipeline holds %d per stream", n, max_subch);
-    int ndp = 0, nmp = 0, npk = 0, nmot = 0;
+    int ndp = 0, nmp = 0, npk = 0, nmot = 0, npad = 0;
     for (int i = 0; i < n; i++) {
         Profile P;
+        if (sub[i].flags & DABGPU_SUBCH_PAD) {
+            if (!(sub[i].flags & DABGPU_SUBCH_DABPLUS)) return fail(DABGPU_E_ARG, "subchannel %d is flagged PAD and not DAB+", i);
+            npad++;
+        }
         if (sub[i].flags & DABGPU_SUBCH_MOT) {
             if (!(sub[i].flags & DABGPU_SUBCH_PACKET))
                 return fail(DABGPU_E_ARG, "subchannel %d is flagged MOT and not packet mode", i);
@@ -321,6 +340,7 @@ static int check_table(const dabgpu_subch *sub, int n, int max_subch, int max_bi
     if (npk > max_packet)
         return fail(DABGPU_E_ARG, "%d packet-mode subchannels, the pipeline holds %d per stream", npk, max_packet);
     if (nmot > max_mot) return fail(DABGPU_E_ARG, "%d MOT subchannels, the pipeline holds %d per stream", nmot, max_mot);
+    if (npad > max_pad) return fail(DABGPU_E_ARG, "%d PAD subchannels, the pipeline holds %d per stream", npad, max_pad);
     return 0;
 }
 
@@ -425,6 +445,37 @@ static int mot_size(dabgpu_pipe *p, int nmot, int body) {
     HIPCHK(hipMemcpy(m.state_d, st.data(), st.size(), hipMemcpyHostToDevice));
     p->mot = std::move(m);
     p->NMOT = nmot;
+    return 0;
+}
+
+// (Re)size the PAD layer to npad slots per stream, as mot_size does: the padHandlers of the
+// slots both sizes hold go on, every other slot is a new one.
+static int pad_size(dabgpu_pipe *p, int npad) {
+    const PadLayer &old = p->pad;
+    const int S = p->S, old_n = p->NPAD;
+    std::vector<uint8_t> ost;
+    if (old_n) {
+        ost.resize((size_t)S * old_n * sizeof(PadState));
+        HIPCHK(hipMemcpy(ost.data(), old.state_d, ost.size(), hipMemcpyDeviceToHost));
+    }
+    PadLayer m;
+    if (!npad) {
+        p->pad = std::move(m);
+        p->NPAD = 0;
+        return 0;
+    }
+    const size_t ne = (size_t)S * npad;
+    HIPCHK(m.ev.create(hipEventDisableTiming));
+    HIPCHK(m.state_d.alloc(ne * sizeof(PadState)));
+    HIPCHK(m.src_d.alloc(ne));
+    std::vector<uint8_t> st(ne * sizeof(PadState), 0);
+    for (int s = 0; s < S; s++)
+        for (int j = 0; j < std::min(old_n, npad); j++)
+            memcpy(st.data() + ((size_t)s * npad + j) * sizeof(PadState), ost.data() + ((size_t)s * old_n + j) * sizeof(PadState),
+                   sizeof(PadState));
+    HIPCHK(hipMemcpy(m.state_d, st.data(), st.size(), hipMemcpyHostToDevice));
+    p->pad = std::move(m);
+    p->NPAD = npad;
     return 0;
 }
 
@@ -556,6 +607,16 @@ static int rebuild_tables(dabgpu_pipe *p) {
             }
         HIPCHK(hipMemcpy(p->mot.src_d, src.data(), sizeof(int32_t) * src.size(), hipMemcpyHostToDevice));
     }
+    if (p->NPAD) {                // PAD slots: slot m of a stream is its m-th entry flagged DABGPU_SUBCH_PAD
+        std::vector<int32_t> src((size_t)S * p->NPAD, -1);
+        for (int s = 0; s < S; s++)
+            for (int k = 0, j = 0, m = 0; k < (int)p->tab[s].size(); k++) {
+                if (!(p->tab[s][k].flags & DABGPU_SUBCH_DABPLUS)) continue;
+                if (p->tab[s][k].flags & DABGPU_SUBCH_PAD) src[(size_t)s * p->NPAD + m++] = s * p->NDP + j;
+                j++;
+            }
+        HIPCHK(hipMemcpy(p->pad.src_d, src.data(), sizeof(int32_t) * src.size(), hipMemcpyHostToDevice));
+    }
     if (p->NDP) {
         HIPCHK(hipMemcpy(p->dp.sub_d, dps.data(), sizeof(int32_t) * nd, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(p->dp.br_d, dpb.data(), sizeof(int16_t) * nd, hipMemcpyHostToDevice));
@@ -587,13 +648,14 @@ int dabgpu_pipe_create_caps(dabgpu_ctx *c, const dabgpu_pipe_cfg *cfg, const dab
         return fail(DABGPU_E_ARG, "bad caps (at most 64 subchannels of at most 384 kbit/s)");
     if (cfg->freq_sync_method < 0 || cfg->freq_sync_method > 2)
         return fail(DABGPU_E_UNSUP, "freqSyncMethod %d (0, 1 or 2: ofdm-decoder.cpp:103-161)", cfg->freq_sync_method);
-    int npk = 0, nmot = 0;        // the packet-mode and MOT layers start with what the table flags (dabgpu_pipe_packet_caps)
+    int npk = 0, nmot = 0, npad = 0;   // the packet-mode, MOT and PAD layers start with what the table flags (dabgpu_pipe_packet_caps)
     for (int i = 0; i < cfg->n_subch; i++) {
         if (cfg->subch[i].flags & DABGPU_SUBCH_PACKET) npk++;
         if (cfg->subch[i].flags & DABGPU_SUBCH_MOT) nmot++;
+        if (cfg->subch[i].flags & DABGPU_SUBCH_PAD) npad++;
     }
     if (int rc = check_table(cfg->subch, cfg->n_subch, caps->max_subch, caps->max_bitrate, caps->max_dabplus, caps->max_mp2, npk,
-                             nmot))
+                             nmot, npad))
         return rc;
     auto p = std::make_unique<dabgpu_pipe>();
     p->c = c;
@@ -680,6 +742,8 @@ int dabgpu_pipe_create_caps(dabgpu_ctx *c, const dabgpu_pipe_cfg *cfg, const dab
         if (int rc = packet_size(p.get(), npk, DABGPU_PKT_GROUP_BYTES)) return rc;
     if (nmot)
         if (int rc = mot_size(p.get(), nmot, DABGPU_MOT_BODY_BYTES)) return rc;
+    if (npad)
+        if (int rc = pad_size(p.get(), npad)) return rc;
     if (int rc = rebuild_tables(p.get())) return rc;
     // the default re-acquisition mode: a stream that loses sync is searched in the
     // background (DABGPU_CTL_ACQ_ASYNC; DABGPU_CTL_ACQ_SYNC restores the in-run search)
@@ -1155,6 +1219,7 @@ int dabgpu_pipe_run(dabgpu_pipe *p, const void *iq, int64_t stride, const int64_
     p->last_msc = have_rows ? msc_bits : nullptr;
     p->dp_pending = p->mp2_pending = p->pk_pending = have_rows;
     p->mot_pending = false;                    // until this run's dabgpu_pipe_packet
+    p->pad_pending = false;                    // until this run's dabgpu_pipe_dabplus
     p->last_msc_stride = msc_stride;
     p->last_msc_packed = p->packed;
     publish_validity(p, done, have_rows, msc_valid);
@@ -1251,7 +1316,63 @@ int dabgpu_pipe_dabplus(dabgpu_pipe *p, uint8_t *sf_bytes, int32_t sf_stride, da
     // (the run after next does not wait for this: the layer reads this run's MSC output
     // and CIF counters, which that run's back end overwrites behind it on this stream)
     p->dp_pending = false;                     // each run's CIFs enter the superframe layer once
+    p->dp_sf = sf_bytes;
+    p->dp_info = info;
+    p->dp_sf_stride = sf_stride;
+    p->dp_sf_compact = p->dp.compact;
+    p->pad_pending = p->NPAD > 0;
     return 0;
+}
+
+int dabgpu_pipe_pad(dabgpu_pipe *p, const uint8_t *sf_bytes, int32_t sf_stride, const dabgpu_superframe *info,
+                    dabgpu_pad_label *labels, dabgpu_datagroup *groups, uint8_t *bytes, dabgpu_pad_run *run) {
+    if (!p || !sf_bytes || !info || !labels || !groups || !bytes || !run) return fail(DABGPU_E_ARG, "null arg");
+    if (p->NPAD == 0) return fail(DABGPU_E_STATE, "no PAD subchannel in this pipeline");
+    if (!p->pad_pending) return fail(DABGPU_E_STATE, "no dabgpu_pipe_dabplus call of this run to consume");
+    if (sf_bytes != p->dp_sf || info != p->dp_info || sf_stride != p->dp_sf_stride)
+        return fail(DABGPU_E_ARG, "sf_bytes_d, sf_stride and info_d are not those of this run's dabgpu_pipe_dabplus call");
+    PadLayer &m = p->pad;
+    PadJob J;
+    memset(&J, 0, sizeof J);
+    J.n_slots = p->S * p->NPAD;
+    J.state = m.state_d;
+    J.info = info;
+    J.sf = sf_bytes;
+    J.sf_stride = sf_stride;
+    J.kmax = p->dp_sf_compact ? DABGPU_SF_SLOTS(p->F) : 0;
+    J.ncif = 4 * p->F;
+    J.ndp = p->NDP;
+    J.src = m.src_d;
+    J.labels = labels;
+    J.label_slots = DABGPU_PAD_LABEL_SLOTS(p->F);
+    J.groups = groups;
+    J.group_slots = DABGPU_PAD_GROUP_SLOTS(p->F);
+    J.bytes = bytes;
+    J.arena = DABGPU_PAD_ARENA_BYTES((int64_t)p->F);
+    J.run = run;
+    // on the run's back-end stream, behind its DAB+ layer; after the previous pass (the
+    // padHandlers are updated in place)
+    hipStream_t bs = p->back[p->cur].stream;
+    HIPCHK(m.ev.wait_on(bs));
+    HIPCHK(launch_pad(bs, J));
+    HIPCHK(m.ev.record(bs));
+    p->pad_pending = false;                    // each run's AUs enter the layer once
+    return 0;
+}
+
+int dabgpu_pipe_pad_caps(dabgpu_pipe *p, int max_pad) {
+    if (!p || max_pad < 0 || max_pad > p->NDP) return fail(DABGPU_E_ARG, "bad args (max_pad <= max_dabplus)");
+    if (max_pad && DABGPU_PAD_ARENA_BYTES((int64_t)p->F) > 0x7FFFFFFF) return fail(DABGPU_E_ARG, "an arena of 2 GiB and more");
+    for (int s = 0; s < p->S; s++) {
+        int n = 0;
+        for (const dabgpu_subch &e : p->tab[s])
+            if (e.flags & DABGPU_SUBCH_PAD) n++;
+        if (n > max_pad) return fail(DABGPU_E_ARG, "stream %d's table has %d PAD subchannels", s, n);
+    }
+    if (int rc = sync_streams(p)) return rc;
+    if (int rc = pad_size(p, max_pad)) return rc;
+    p->pad_pending = false;
+    return rebuild_tables(p);
 }
 
 int dabgpu_pipe_mp2(dabgpu_pipe *p, int16_t *pcm, dabgpu_mp2_info *info) {
@@ -1537,7 +1658,7 @@ int dabgpu_pipe_frame_slot(dabgpu_pipe *p, int frame, int32_t *slot) {
 }
 int dabgpu_pipe_set_subch(dabgpu_pipe *p, int stream, const dabgpu_subch *sub, int32_t n) {
     if (!p || stream < -1 || stream >= p->S) return fail(DABGPU_E_ARG, "bad args");
-    if (int rc = check_table(sub, n, p->NSUB, p->max_bitrate, p->NDP, p->NMP, p->NPK, p->NMOT)) return rc;   // the table stays on error
+    if (int rc = check_table(sub, n, p->NSUB, p->max_bitrate, p->NDP, p->NMP, p->NPK, p->NMOT, p->NPAD)) return rc;   // the table stays on error
     // in-flight kernels read the device tables: a rare control call, so it waits for
     // everything the pipeline has enqueued (as dabgpu_pipe_set_profiling) instead of
     // double-buffering them
@@ -1630,6 +1751,22 @@ int dabgpu_pipe_set_subch(dabgpu_pipe *p, int stream, const dabgpu_subch *sub, i
             }
             HIPCHK(hipMemcpy(m.state_d + o, nms.data(), NM * SB, hipMemcpyHostToDevice));
         }
+        // the PAD slots likewise: an unchanged entry's padHandler moves to its new slot, every
+        // other slot is a new one
+        if (p->NPAD) {
+            const size_t NM = p->NPAD, SB = sizeof(PadState), o = (size_t)s * NM * SB;
+            std::vector<uint8_t> ms(NM * SB), nms(NM * SB, 0);
+            HIPCHK(hipMemcpy(ms.data(), p->pad.state_d + o, NM * SB, hipMemcpyDeviceToHost));
+            std::vector<int> oslot(old.size(), -1);
+            for (int k = 0, j = 0; k < (int)old.size(); k++)
+                if (old[k].flags & DABGPU_SUBCH_PAD) oslot[k] = j++;
+            for (int k = 0, j = 0; k < n; k++) {
+                if (!(sub[k].flags & DABGPU_SUBCH_PAD)) continue;
+                if (k < (int)old.size() && same_subch(old[k], sub[k])) memcpy(nms.data() + j * SB, ms.data() + oslot[k] * SB, SB);
+                j++;
+            }
+            HIPCHK(hipMemcpy(p->pad.state_d + o, nms.data(), NM * SB, hipMemcpyHostToDevice));
+        }
         p->tab[s].assign(sub, sub + n);
         p->since[s].assign(n, p->st[s].cif_count);
         for (int k = 0, j = 0; k < n; k++) {
@@ -1649,6 +1786,7 @@ int dabgpu_pipe_set_subch(dabgpu_pipe *p, int stream, const dabgpu_subch *sub, i
     }
     p->last_msc = nullptr;            // the last run's rows follow the old tables: no DAB+ layer over them now
     p->mot_pending = false;
+    p->pad_pending = false;
     if (int rc = rebuild_tables(p)) return rc;
     if (p->inject_bounds) return inject_table(p);
     return 0;

@@ -121,6 +121,73 @@ def mot_groups(ctx: "Context", groups: np.ndarray, data: np.ndarray, run: np.nda
             b.free()
 
 
+SUBCH_PAD = 32      # Subch.flags, with SUBCH_DABPLUS: feed the entry's good AUs to the PAD layer (Pipeline.pad)
+PAD_LABEL_BYTES, PAD_LABEL_PIECES, PAD_LABEL_TRUNCATED = 256, 64, 1
+PAD_LABEL_DTYPE = np.dtype([("cif", "<i4"), ("au", "<i4"), ("charset", "<i4"), ("nbytes", "<i4"), ("n_pieces", "<i4"),
+                            ("flags", "<i4"), ("piece_len", "u1", (PAD_LABEL_PIECES,)),
+                            ("text", "u1", (PAD_LABEL_BYTES,))])                                         # dabgpu_pad_label
+PAD_RUN_DTYPE = np.dtype([("n_labels", "<i4"), ("n_groups", "<i4"), ("n_bytes", "<i4"), ("aus", "<i4"), ("pads", "<i4"),
+                          ("unhandled", "<i4"), ("undefined", "<i4", (4,)), ("crc_failed", "<i4"),
+                          ("guard_dropped", "<i4"), ("rejected_sf", "<i4"), ("reserved", "<i4", (3,))])  # dabgpu_pad_run
+
+
+def pad_au_slots(n_frames: int) -> int:
+    """DABGPU_PAD_AU_SLOTS"""
+    return ((4 * n_frames + 4) // 5 + 1) * 6
+
+
+def pad_arena_bytes(n_frames: int) -> int:
+    """DABGPU_PAD_ARENA_BYTES"""
+    return (8192 + pad_au_slots(n_frames) * 192 + 15) // 16 * 16
+
+
+def pad_state_bytes() -> int:
+    """dabgpu_pad_state_bytes: a padHandler's carried state (all zero: a new one)"""
+    return int(lib().dabgpu_pad_state_bytes())
+
+
+def pad_aus(ctx: "Context", aus: np.ndarray, lengths: np.ndarray, state: Optional[np.ndarray] = None,
+            cif: Optional[np.ndarray] = None, label_slots: Optional[int] = None, group_slots: Optional[int] = None,
+            arena_bytes: Optional[int] = None):
+    """padHandler::processPAD per slot (dabgpu_pad_aus; pad-handler.cpp): aus [n_slots, n_aus,
+    au_stride] uint8, lengths [n_slots, n_aus] int32 (the AU's aac_frame_length; negative: it
+    failed its CRC), state [n_slots, pad_state_bytes()] bytes carried from an earlier call
+    (None: new padHandlers), cif [n_slots, n_aus] int32 or None.  The slots default to four per
+    AU and the arena to 8192 + 192 bytes per AU (at least pad_arena_bytes(0)).  Returns (labels [n_slots, label_slots]
+    PAD_LABEL_DTYPE -- the first run.n_labels of a row --, groups [n_slots, group_slots]
+    DATAGROUP_DTYPE, bytes [n_slots, arena] uint8, run [n_slots] PAD_RUN_DTYPE, state)."""
+    aus = np.ascontiguousarray(aus, dtype=np.uint8)
+    lengths = np.ascontiguousarray(lengths, dtype=np.int32)
+    n, na, stride = aus.shape
+    assert lengths.shape == (n, na)
+    sb = pad_state_bytes()
+    st = np.zeros((n, sb), np.uint8) if state is None else np.ascontiguousarray(state, dtype=np.uint8).reshape(n, sb)
+    ls = 4 * na if label_slots is None else int(label_slots)
+    gs = 4 * na if group_slots is None else int(group_slots)
+    ar = max(pad_arena_bytes(0), (8192 + 192 * na + 15) // 16 * 16) if arena_bytes is None else int(arena_bytes)
+    bufs = [ctx.put(aus) if aus.size else ctx.buf(16), ctx.put(lengths) if na and n else ctx.buf(16), ctx.put(st) if n else ctx.buf(16)]
+    dc = None
+    if cif is not None:
+        cif = np.ascontiguousarray(cif, dtype=np.int32)
+        assert cif.shape == (n, na)
+        dc = ctx.put(cif) if cif.size else ctx.buf(16)
+        bufs.append(dc)
+    da, dl, ds = bufs[:3]
+    dlab = ctx.buf(max(16, n * max(ls, 0) * PAD_LABEL_DTYPE.itemsize)).zero()
+    dgr = ctx.buf(max(16, n * max(gs, 0) * DATAGROUP_DTYPE.itemsize)).zero()
+    dby, drun = ctx.buf(max(16, n * max(ar, 0))).zero(), ctx.buf(max(16, n * PAD_RUN_DTYPE.itemsize)).zero()
+    bufs += [dlab, dgr, dby, drun]
+    try:
+        _chk(lib().dabgpu_pad_aus(ctx.h, ds.ptr, n, da.ptr, stride, dl.ptr, na, dc.ptr if dc else None, dlab.ptr, ls,
+                                  dgr.ptr, gs, dby.ptr, ar, drun.ptr), "dabgpu_pad_aus")
+        ctx.sync()
+        return (_records(dlab, PAD_LABEL_DTYPE, (n, ls)), _records(dgr, DATAGROUP_DTYPE, (n, gs)),
+                dby.download(np.uint8, (n, ar)), _records(drun, PAD_RUN_DTYPE, (n,)), ds.download(np.uint8, (n, sb)))
+    finally:
+        for b in bufs:
+            b.free()
+
+
 SUPERFRAME_DTYPE = np.dtype([("status", "i1"), ("num_aus", "i1"), ("n_corrected", "<i2"), ("au_start", "<i2", (7,)),
                              ("au_crc_ok", "u1"), ("reserved", "u1")])
 
@@ -215,7 +282,11 @@ def lib() -> C.CDLL:
             "dabgpu_pipe_packet_caps": ([vp, i32, i32], i32),
             "dabgpu_mot_state_bytes": ([i32], sz),
             "dabgpu_mot_groups": ([vp, vp, i32, i32, vp, i32, vp, i64, vp, vp, vp, i64, vp], i32),
+            "dabgpu_pad_state_bytes": ([], sz),
+            "dabgpu_pad_aus": ([vp, vp, i32, vp, i64, vp, i32, vp, vp, i32, vp, i32, vp, i64, vp], i32),
             "dabgpu_pipe_mot": ([vp, vp, vp, vp], i32),
+            "dabgpu_pipe_pad": ([vp, vp, i32, vp, vp, vp, vp, vp], i32),
+            "dabgpu_pipe_pad_caps": ([vp, i32], i32),
             "dabgpu_pipe_mot_caps": ([vp, i32, i32], i32),
             "dabgpu_pipe_sync": ([vp], i32),
             "dabgpu_pipe_create": ([vp, vp, C.POINTER(vp)], i32), "dabgpu_pipe_destroy": ([vp], i32),
@@ -855,6 +926,46 @@ class Pipeline:
             self.mot_caps(self.max_mot if max_mot is None else max_mot, max_body_bytes or 0)
         else:
             self._mot_bufs()
+        self._pad = []
+        self.max_pad = sum(1 for s in self.subch if s.flags & SUBCH_PAD)
+        self._pad_bufs()
+
+    def _pad_bufs(self) -> None:
+        for o in self._pad:
+            for b in o:
+                b.free()
+        self._pad = []
+        if self.max_pad:
+            ne, na = self.S * self.max_pad, pad_au_slots(self.F)
+            self._pad = [(self.ctx.buf(ne * 4 * na * PAD_LABEL_DTYPE.itemsize), self.ctx.buf(ne * 4 * na * DATAGROUP_DTYPE.itemsize),
+                          self.ctx.buf(ne * pad_arena_bytes(self.F)), self.ctx.buf(ne * PAD_RUN_DTYPE.itemsize)) for _ in range(2)]
+
+    def pad_caps(self, max_pad: int) -> None:
+        """size the PAD layer between runs (dabgpu_pipe_pad_caps): max_pad slots per stream
+        (<= max_dabplus); the existing slots keep their padHandlers"""
+        _chk(lib().dabgpu_pipe_pad_caps(self.h, int(max_pad)), "dabgpu_pipe_pad_caps")
+        self.max_pad = int(max_pad)
+        self._pad_bufs()
+
+    def pad(self, download: bool = True):
+        """PAD layer over the AUs of this run's dabplus() (dabgpu_pipe_pad; pad-handler.cpp).
+        Returns (labels [S, max_pad, 4 * pad_au_slots(F)] PAD_LABEL_DTYPE -- the first
+        run.n_labels of a row are this run's --, groups [S, max_pad, 4 * pad_au_slots(F)]
+        DATAGROUP_DTYPE, bytes [S, max_pad, pad_arena_bytes(F)] uint8, run [S, max_pad]
+        PAD_RUN_DTYPE)."""
+        if not self._pad:                # max_pad == 0: there are no output buffers to hand to the library,
+            e = DabError("dabgpu_pipe_pad: no PAD subchannel in this pipeline")   # which would refuse as well
+            e.code = -6
+            raise e
+        self.padl_d, self.padg_d, self.padb_d, self.padr_d = self._pad[(self._run - 1) & 1]
+        _chk(lib().dabgpu_pipe_pad(self.h, self.sf_d.ptr, self.sf_stride, self.sfi_d.ptr, self.padl_d.ptr, self.padg_d.ptr,
+                                   self.padb_d.ptr, self.padr_d.ptr), "dabgpu_pipe_pad")
+        if not download:
+            return None
+        self.sync()
+        S, NP, ns = self.S, self.max_pad, 4 * pad_au_slots(self.F)
+        return (_records(self.padl_d, PAD_LABEL_DTYPE, (S, NP, ns)), _records(self.padg_d, DATAGROUP_DTYPE, (S, NP, ns)),
+                self.padb_d.download(np.uint8, (S, NP, pad_arena_bytes(self.F))), _records(self.padr_d, PAD_RUN_DTYPE, (S, NP)))
 
     def _mot_bufs(self) -> None:
         for o in self._mot:
@@ -1133,7 +1244,7 @@ class Pipeline:
 
     def close(self) -> None:
         if self.h:
-            for o in self._outs + self._sf + self._mp2 + self._pkt + self._mot:
+            for o in self._outs + self._sf + self._mp2 + self._pkt + self._mot + self._pad:
                 for b in o:
                     b.free()
             lib().dabgpu_pipe_destroy(self.h)

@@ -16,7 +16,7 @@ class SynthSubch(C.Structure):
                 ("protLevel", C.c_int16), ("uep", C.c_int16), ("dabplus", C.c_int16), ("content", C.c_int16)]
 
 
-MP2, PACKET, AU_MIX, MOT = 2, 3, 4, 5   # SynthSubch.content (dabsynth.h DABSYNTH_MP2 / _PACKET / _AU_MIX / _MOT)
+MP2, PACKET, AU_MIX, MOT, PAD = 2, 3, 4, 5, 6   # SynthSubch.content (dabsynth.h DABSYNTH_MP2 / _PACKET / _AU_MIX / _MOT / _PAD)
 
 
 class SynthCfg(C.Structure):

@@ -143,6 +143,11 @@ bool mp4Processor::processSuperframe(int base) {                 // mp4processor
         const int len = a[i + 1] - a[i] - 2;
         if (len >= 960 || len < 0) return false;
         const bool ok = dabPlus_crc(&outVector_[a[i]], (int16_t)len);
+        if (pad_ && ok && ((outVector_[a[i]] >> 5) & 07) == 4 && len > 0) {      // (mp4processor.cpp:260-265)
+            uint8_t theAU[2 * 960] = {};
+            memcpy(theAU, &outVector_[a[i]], (size_t)len);
+            pad_(theAU, (int16_t)len);
+        }
         if (cb_) cb_(&outVector_[a[i]], (int16_t)len, ok, info);
     }
     superframes_++;

@@ -303,6 +303,21 @@ ensembleDecoder::ensembleDecoder(const config &cfg) : cfg_(cfg) {
         nmot_ = cfg.max_mot ? cfg.max_mot : nmot_;
         chk(dabgpu_pipe_mot_caps(pipe_, nmot_, cfg.max_body_bytes), "dabgpu_pipe_mot_caps");
     }
+    for (const dabgpu_subch &sc : cfg.subch)
+        if (sc.flags & DABGPU_SUBCH_PAD) npad_++;
+    if (cfg.max_pad) {
+        npad_ = cfg.max_pad;
+        chk(dabgpu_pipe_pad_caps(pipe_, npad_), "dabgpu_pipe_pad_caps");
+    }
+    if (npad_) {
+        pad_slots_ = DABGPU_PAD_LABEL_SLOTS(cfg.n_frames);
+        pad_arena_ = DABGPU_PAD_ARENA_BYTES((size_t)cfg.n_frames);
+        const size_t ne = (size_t)cfg.n_streams * npad_;
+        pdl_.resize(ne * pad_slots_ * sizeof(dabgpu_pad_label));
+        pdg_.resize(ne * pad_slots_ * sizeof(dabgpu_datagroup));
+        pdb_.resize(ne * pad_arena_);
+        pdr_.resize(ne * sizeof(dabgpu_pad_run));
+    }
     if (nmot_) {
         mot_arena_ = DABGPU_MOT_ARENA_BYTES((size_t)cfg.n_frames, (int)caps.max_bitrate,
                                             (size_t)(cfg.max_body_bytes ? cfg.max_body_bytes : DABGPU_MOT_BODY_BYTES));
@@ -315,8 +330,22 @@ ensembleDecoder::ensembleDecoder(const config &cfg) : cfg_(cfg) {
 
 void ensembleDecoder::set_subch(int stream, const std::vector<dabgpu_subch> &subch) {
     chk(dabgpu_pipe_set_subch(pipe_, stream, subch.data(), (int32_t)subch.size()), "dabgpu_pipe_set_subch");
-    for (int s = 0; s < cfg_.n_streams; s++)
-        if (stream < 0 || s == stream) tab_[s] = subch;
+    auto pads = [](const std::vector<dabgpu_subch> &t) {
+        std::vector<dabgpu_subch> v;
+        for (const dabgpu_subch &e : t)
+            if (e.flags & DABGPU_SUBCH_PAD) v.push_back(e);
+        return v;
+    };
+    for (int s = 0; s < cfg_.n_streams; s++) {
+        if (stream >= 0 && s != stream) continue;
+        // the PAD slots' MOT states (on_pad_object): new ones unless the stream's PAD entries stay as they are
+        const std::vector<dabgpu_subch> a = pads(tab_[s]), b = pads(subch);
+        if (pms_.size() && (a.size() != b.size() || (!a.empty() && std::memcmp(a.data(), b.data(), a.size() * sizeof(dabgpu_subch))))) {
+            const size_t sb = dabgpu_mot_state_bytes(0);
+            chk(dabgpu_memset_d(thread_context(), (uint8_t *)pms_.get() + (size_t)s * npad_ * sb, 0, (size_t)npad_ * sb), "dabgpu_memset_d");
+        }
+        tab_[s] = subch;
+    }
 }
 
 std::vector<dabgpu_subch> ensembleDecoder::get_subch(int stream, std::vector<int64_t> *since_cif) const {
@@ -538,6 +567,80 @@ bool ensembleDecoder::step() {
             }
         }
     }
+    if (NS && ndp_ && npad_) {
+        chk(dabgpu_pipe_pad(pipe_, (const uint8_t *)sf_.get(), sf_stride_, (const dabgpu_superframe *)sfi_.get(),
+                            (dabgpu_pad_label *)pdl_.get(), (dabgpu_datagroup *)pdg_.get(), (uint8_t *)pdb_.get(),
+                            (dabgpu_pad_run *)pdr_.get()), "dabgpu_pipe_pad");
+        chk(dabgpu_pipe_sync(pipe_), "dabgpu_pipe_sync");
+        if (label_cb_ || pad_dg_cb_ || pad_obj_cb_) {
+            const size_t ne = (size_t)S * npad_;
+            std::vector<dabgpu_pad_run> run(ne);
+            pdr_.download(run.data(), run.size() * sizeof(dabgpu_pad_run));
+            std::vector<dabgpu_mot_run> mrun(ne);
+            if (pad_obj_cb_) {
+                // padHandler::my_motHandler: one MOT state per stream and PAD slot, the layer's groups as they are
+                const size_t sb = dabgpu_mot_state_bytes(0);
+                if (!pms_.size()) {
+                    pad_mot_arena_ = DABGPU_MOT_ARENA_FOR((size_t)pad_slots_, DABGPU_MOT_BODY_BYTES);
+                    pms_.resize(ne * sb);
+                    chk(dabgpu_memset_d(thread_context(), pms_.get(), 0, ne * sb), "dabgpu_memset_d");
+                    pmr_.resize(ne * sizeof(dabgpu_packet_run));
+                    pmo_.resize(ne * pad_slots_ * sizeof(dabgpu_mot_object));
+                    pmb_.resize(ne * pad_mot_arena_);
+                    pmm_.resize(ne * sizeof(dabgpu_mot_run));
+                }
+                std::vector<dabgpu_packet_run> pr(ne);
+                for (size_t e = 0; e < ne; e++) pr[e] = {std::min(run[e].n_groups, pad_slots_), run[e].n_bytes, 0, 0};
+                pmr_.upload(pr.data(), pr.size() * sizeof(dabgpu_packet_run));
+                chk(dabgpu_mot_groups(thread_context(), pms_.get(), (int)ne, 0, (const dabgpu_datagroup *)pdg_.get(), pad_slots_,
+                                      (const uint8_t *)pdb_.get(), (int64_t)pad_arena_, (const dabgpu_packet_run *)pmr_.get(),
+                                      (dabgpu_mot_object *)pmo_.get(), (uint8_t *)pmb_.get(), (int64_t)pad_mot_arena_,
+                                      (dabgpu_mot_run *)pmm_.get()), "dabgpu_mot_groups");
+                chk(dabgpu_sync(thread_context()), "dabgpu_sync");
+                pmm_.download(mrun.data(), mrun.size() * sizeof(dabgpu_mot_run));
+            }
+            std::vector<dabgpu_pad_label> labels;
+            std::vector<dabgpu_datagroup> groups;
+            std::vector<dabgpu_mot_object> objects;
+            std::vector<uint8_t> bytes;
+            for (int s = 0; s < S; s++) {
+                std::vector<int> slot;               // PAD slot j of a stream is its j-th entry flagged for both
+                for (int k = 0; k < (int)tab_[s].size(); k++)
+                    if ((tab_[s][k].flags & DABGPU_SUBCH_DABPLUS) && (tab_[s][k].flags & DABGPU_SUBCH_PAD)) slot.push_back(k);
+                for (int j = 0; j < (int)slot.size() && j < npad_; j++) {
+                    const size_t e = (size_t)s * npad_ + j;
+                    const int nl = std::min(run[e].n_labels, pad_slots_), ng = std::min(run[e].n_groups, pad_slots_);
+                    if (label_cb_ && nl > 0) {
+                        labels.resize(nl);
+                        chk(dabgpu_memcpy_d2h(thread_context(), labels.data(), (const dabgpu_pad_label *)pdl_.get() + e * pad_slots_,
+                                              labels.size() * sizeof(dabgpu_pad_label)), "dabgpu_memcpy_d2h");
+                        for (const dabgpu_pad_label &l : labels) label_cb_(s, 4 * frames_done_[s] + l.cif, slot[j], l);
+                    }
+                    if (pad_dg_cb_ && ng > 0) {
+                        groups.resize(ng);
+                        bytes.resize(std::max(1, run[e].n_bytes));
+                        chk(dabgpu_memcpy_d2h(thread_context(), groups.data(), (const dabgpu_datagroup *)pdg_.get() + e * pad_slots_,
+                                              groups.size() * sizeof(dabgpu_datagroup)), "dabgpu_memcpy_d2h");
+                        chk(dabgpu_memcpy_d2h(thread_context(), bytes.data(), (const uint8_t *)pdb_.get() + e * pad_arena_, run[e].n_bytes),
+                            "dabgpu_memcpy_d2h");
+                        for (const dabgpu_datagroup &g : groups)
+                            pad_dg_cb_(s, 4 * frames_done_[s] + g.cif, slot[j], g, bytes.data() + g.offset,
+                                       (g.flags & DABGPU_DG_TRUNCATED) ? 0 : g.nbytes);
+                    }
+                    if (pad_obj_cb_ && mrun[e].n_objects > 0) {
+                        objects.resize(mrun[e].n_objects);
+                        bytes.resize(std::max(1, mrun[e].n_bytes));
+                        chk(dabgpu_memcpy_d2h(thread_context(), objects.data(), (const dabgpu_mot_object *)pmo_.get() + e * pad_slots_,
+                                              objects.size() * sizeof(dabgpu_mot_object)), "dabgpu_memcpy_d2h");
+                        chk(dabgpu_memcpy_d2h(thread_context(), bytes.data(), (const uint8_t *)pmb_.get() + e * pad_mot_arena_,
+                                              mrun[e].n_bytes), "dabgpu_memcpy_d2h");
+                        for (const dabgpu_mot_object &o : objects)
+                            pad_obj_cb_(s, 4 * frames_done_[s] + o.cif, slot[j], o, bytes.data() + o.offset);
+                    }
+                }
+            }
+        }
+    }
     if (NS && nmp_) {
         chk(dabgpu_pipe_mp2(pipe_, (int16_t *)pcm_.get(), (dabgpu_mp2_info *)mp2i_.get()), "dabgpu_pipe_mp2");
         chk(dabgpu_pipe_sync(pipe_), "dabgpu_pipe_sync");
@@ -633,7 +736,8 @@ bool ensembleDecoder::step() {
     for (int s = 0; s < S && cfg_.auto_layout; s++) {
         std::vector<dabgpu_subch> now;
         for (const fib_subch &e : fibs_[s].subchannels(nullptr, pcm_cb_ != nullptr && nmp_ > 0, dg_cb_ != nullptr && npk_ > 0,
-                                                       mot_cb_ != nullptr && nmot_ > 0))
+                                                       mot_cb_ != nullptr && nmot_ > 0,
+                                                       (label_cb_ || pad_dg_cb_ || pad_obj_cb_) && npad_ > 0))
             now.push_back({e.startAddr, e.length, e.bitRate, e.protLevel, e.uepFlag, e.flags});
         auto same = [](const std::vector<dabgpu_subch> &x, const std::vector<dabgpu_subch> &y) {
             return x.size() == y.size() && (x.empty() || !std::memcmp(x.data(), y.data(), x.size() * sizeof(dabgpu_subch)));

@@ -211,12 +211,20 @@ public:
     using au_cb = std::function<void(const uint8_t *au, int16_t len, bool crc_ok, const au_info &)>;
     mp4Processor(int16_t bitRate, au_cb cb);
     void addtoFrame(uint8_t *v, int16_t nbits) override;
+    // optional PAD hook, fed where the reference calls my_padHandler.processPAD
+    // (mp4processor.cpp:255-265): an AU with a good CRC whose first syntactic element is a data
+    // stream element, as theAU -- 1920 bytes, the AU's len bytes and zeros behind them.  No hook
+    // (the default): nothing changes.  A padAssembler takes it as
+    //   set_pad_hook([&](const uint8_t *theAU, int16_t len) { pad.processAU(theAU, 1920, len); });
+    using pad_cb = std::function<void(const uint8_t *theAU, int16_t len)>;
+    void set_pad_hook(pad_cb f) { pad_ = std::move(f); }
     int32_t superframes() const { return superframes_; }
     int32_t frameErrors() const { return frameErrors_; }
 private:
     bool processSuperframe(int base);
     int16_t bitRate_, RSDims_;
     au_cb cb_;
+    pad_cb pad_;
     std::vector<uint8_t> frameBytes_, outVector_;
     int16_t blockFillIndex_ = 0, blocksInBuffer_ = 0;
     int32_t superframes_ = 0, frameErrors_ = 0;
@@ -490,6 +498,9 @@ public:
         // dabgpu_pipe_mot_caps: entries also flagged DABGPU_SUBCH_MOT a stream's table may hold
         // (0: what subch flags; at most max_packet) and the largest MOT body (0: DABGPU_MOT_BODY_BYTES)
         int max_mot = 0, max_body_bytes = 0;
+        // dabgpu_pipe_pad_caps: DAB+ entries also flagged DABGPU_SUBCH_PAD a stream's table may hold
+        // (0: what subch flags; at most max_dabplus)
+        int max_pad = 0;
         // FIC first: each stream's table follows its own FIG 0/1 and 0/2 (a fib_processor per
         // stream, fed its CRC-good FIBs).  At the end of a step() a stream's parsed table is
         // applied (set_subch) when it is non-empty, equals the one parsed at the end of the
@@ -537,6 +548,25 @@ public:
     using mot_object_cb = std::function<void(int stream, int64_t cif, int subch, const dabgpu_mot_object &o,
                                              const uint8_t *body)>;
     void on_mot_object(mot_object_cb f) { mot_cb_ = std::move(f); }
+    // DAB+ PAD of the entries flagged DABGPU_SUBCH_DABPLUS | DABGPU_SUBCH_PAD (dabgpu_pipe_pad after
+    // the step's dabgpu_pipe_dabplus): the dynamic label where padHandler emits showLabel (the
+    // record holds the bytes, pieces and charSet the reference hands to toQStringUsingCharset:
+    // INTEGRATION section 6), every completed X-PAD data group with its bytes (g.flags &
+    // DABGPU_DG_ACCEPTED: the ones padHandler hands to its motHandler), and, with on_pad_object
+    // set, the slides and files of padHandler::my_motHandler: the decoder then owns one MOT state
+    // per stream and PAD slot and runs dabgpu_mot_groups on the layer's groups.  (A stream's
+    // set_subch that changes its PAD entries gives the stream new MOT states.)  cif is the CIF of
+    // the AU that completed the label or group.  With auto_layout, DAB+ audio components are
+    // flagged DABGPU_SUBCH_DABPLUS | DABGPU_SUBCH_PAD when one of the three is set before the table
+    // is applied (config::max_pad says how many).
+    using dynamic_label_cb = std::function<void(int stream, int64_t cif, int subch, const dabgpu_pad_label &l)>;
+    using pad_datagroup_cb = std::function<void(int stream, int64_t cif, int subch, const dabgpu_datagroup &g,
+                                                const uint8_t *bytes, int nbytes)>;
+    using pad_object_cb = std::function<void(int stream, int64_t cif, int subch, const dabgpu_mot_object &o,
+                                             const uint8_t *body)>;
+    void on_dynamic_label(dynamic_label_cb f) { label_cb_ = std::move(f); }
+    void on_pad_datagroup(pad_datagroup_cb f) { pad_dg_cb_ = std::move(f); }
+    void on_pad_object(pad_object_cb f) { pad_obj_cb_ = std::move(f); }
     // samples[s] -> n[s] cf32 samples of stream s (copied to HBM)
     void load(const std::vector<const DSPCOMPLEX *> &samples, const std::vector<int64_t> &n);
     // the streams as recorded: format DABGPU_IQ_S16 (.sdr PCM16 I/Q pairs) or DABGPU_IQ_U8
@@ -572,6 +602,13 @@ private:
     int nmot_ = 0;
     size_t mot_arena_ = 0;
     mot_object_cb mot_cb_;
+    devbuf pdl_, pdg_, pdb_, pdr_;                    // the PAD layer's label and group records, arenas, run records
+    devbuf pms_, pmr_, pmo_, pmb_, pmm_;              // on_pad_object: MOT states, packet-run and object records, bodies, runs
+    int npad_ = 0, pad_slots_ = 0;
+    size_t pad_arena_ = 0, pad_mot_arena_ = 0;
+    dynamic_label_cb label_cb_;
+    pad_datagroup_cb pad_dg_cb_;
+    pad_object_cb pad_obj_cb_;
     pcm_cb pcm_cb_;
     datagroup_cb dg_cb_;
     packet_quality_cb pq_cb_;

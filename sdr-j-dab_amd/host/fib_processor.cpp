@@ -367,7 +367,8 @@ int fib_processor::bind(int8_t tmid, int32_t sid, int16_t compnr) {
     return first_free;
 }
 
-std::vector<fib_subch> fib_processor::subchannels(std::vector<int> *ids, bool classic_audio, bool packet_data, bool mot) const {
+std::vector<fib_subch> fib_processor::subchannels(std::vector<int> *ids, bool classic_audio, bool packet_data, bool mot,
+                                                  bool pad) const {
     std::vector<fib_subch> v;
     if (ids) ids->clear();
     for (int id = 0; id < 64; id++) {
@@ -387,6 +388,7 @@ std::vector<fib_subch> fib_processor::subchannels(std::vector<int> *ids, bool cl
                 if (packet_data) e.flags |= 8;                          // DABGPU_SUBCH_PACKET
                 if (mot && c.DSCTy == 60) e.flags |= 8 | 16;            // ... | DABGPU_SUBCH_MOT
             }
+        if ((e.flags & 1) && pad) e.flags |= 32;                        // DABGPU_SUBCH_PAD
         if (e.flags & 1) e.flags &= ~4;                                 // (one layer per entry,
         if (e.flags & 5) e.flags &= ~(8 | 16);                          //  the audio layers first)
         v.push_back(e);

@@ -106,7 +106,8 @@ public:
     // 60 (MOT: what mscDatagroup hands to mot_databuilder, msc-datagroup.cpp:82-84), whether
     // packet_data is set or not.
     std::vector<fib_subch> subchannels(std::vector<int> *ids = nullptr, bool classic_audio = false,
-                                       bool packet_data = false, bool mot = false) const;
+                                       bool packet_data = false, bool mot = false,
+                                       bool pad = false) const;   // pad: DAB+ entries also get DABGPU_SUBCH_PAD (32)
 
     std::string ensembleName() const { return ensemble_; }
     std::vector<std::string> serviceLabels() const;

@@ -312,4 +312,222 @@ void motAssembler::processSegment(element *h, const uint8_t *segment, int32_t n,
     if (cb_) cb_(o);
 }
 
+// ---- padAssembler: padHandler (pad-handler.cpp) ------------------------------------------------
+padAssembler::padAssembler(label_cb on_label, datagroup_cb on_group)
+    : onLabel_(std::move(on_label)), onGroup_(std::move(on_group)), buffer_(8192, 0) {}
+
+void padAssembler::processAU(const uint8_t *au, int32_t nbytes, int32_t aac_frame_length) {
+    if (aac_frame_length < 0) return;
+    c_.aus++;
+    const int32_t n = std::min(nbytes, aac_frame_length);
+    auto B = [&](int32_t i) -> uint8_t { return i < n ? au[i] : 0; };     // theAU is zeroed before the copy
+    if (((B(0) >> 5) & 7) != 4) return;                                   // (mp4processor.cpp:264)
+    uint8_t pad[255];
+    const int32_t count = B(1);
+    for (int32_t i = 0; i < count; i++) pad[i] = B(2 + i);
+    processPAD(pad, count);
+}
+
+static const int32_t kPadSubfield[8] = {4, 6, 8, 12, 16, 24, 32, 48};    // mapLength (:86-95)
+
+void padAssembler::processPAD(const uint8_t *b, int32_t count) {
+    c_.pads++;
+    touched_ = 0;
+    auto done = [&]() {
+        for (int k = 0; k < 4; k++) c_.undefined[k] += (touched_ >> k) & 1;
+    };
+    if (count < 2) {                                                      // rule 1
+        touched_ |= 1;
+        return done();
+    }
+    auto rd = [&](int32_t i) -> uint8_t {                                 // rule 2
+        if (i < 0) {
+            touched_ |= 2;
+            return 0;
+        }
+        return b[i];
+    };
+    if (((b[count - 2] >> 6) & 3) != 0) return done();                    // only F-PAD type 0
+    const int x_padInd = (b[count - 2] >> 4) & 3;
+    if (x_padInd == 1) {                                                  // handle_shortPAD (:73-82)
+        const uint8_t CI = rd(count - 3);
+        uint8_t data[4] = {rd(count - 4), rd(count - 5), rd(count - 6), 0};
+        if ((CI & 037) == 2 || (CI & 037) == 3) dynamicLabel(data, 3, CI);
+        return done();
+    }
+    if (x_padInd != 2 || !((b[count - 1] >> 1) & 1)) return done();       // handle_variablePAD (:97-173), CI flag 0
+    int32_t base = count - 3, n_ci = 0;
+    uint8_t CI_table[4];
+    while ((rd(base) & 037) != 0 && n_ci < 4) CI_table[n_ci++] = rd(base--);
+    if (n_ci < 4) base -= 1;
+    for (int32_t i = 0; i < n_ci; i++) {
+        const uint8_t appType = CI_table[i] & 037;
+        const int32_t length = kPadSubfield[CI_table[i] >> 5];
+        if (appType == 1) {
+            const uint8_t byte_0 = rd(base), byte_1 = rd(base - 1);
+            rd(base - 2);                                                 // (the reference reads a crc it does not use)
+            rd(base - 3);
+            length_ = ((byte_0 & 077) << 8) | byte_1;
+            index_ = 0;
+            base -= 4;
+            lastAppType_ = 1;
+            lastSet_ = true;
+            continue;
+        }
+        if (appType != 2 && appType != 3 && appType != 12 && appType != 13) {
+            lastAppType_ = appType;
+            lastSet_ = true;
+            c_.unhandled++;
+            return done();
+        }
+        uint8_t data[49];
+        for (int32_t j = 0; j < length; j++) data[j] = rd(base - j);
+        data[length] = 0;
+        if (appType == 2 || appType == 3) {
+            dynamicLabel(data, length, CI_table[i]);
+        } else {
+            if (!lastSet_) touched_ |= 4;                                 // rule 3: last_appType is read
+            if ((appType == 12 && lastAppType_ == 1) || (appType == 13 && (lastAppType_ == 12 || lastAppType_ == 13)))
+                add_MSC_element(data, length);
+        }
+        lastAppType_ = appType;
+        lastSet_ = true;
+        base -= length;
+        if (base < 0 && i < n_ci - 1) return done();
+    }
+    done();
+}
+
+void padAssembler::append(const uint8_t *piece, int32_t n) {
+    if (!charSetSet_) touched_ |= 4;                                      // rule 3: charSet is read
+    if (text_.nbytes + n > 256 || text_.n_pieces + 1 > 64) {              // rule 4
+        touched_ |= 8;
+        text_.truncated = true;
+    }
+    for (int32_t i = 0; i < n && text_.text.size() < 256; i++) text_.text.push_back(piece[i]);
+    if (text_.piece_len.size() < 64) text_.piece_len.push_back((uint8_t)n);
+    text_.nbytes += n;
+    text_.n_pieces++;
+}
+
+void padAssembler::dynamicLabel(const uint8_t *data, int32_t length, uint8_t CI) {
+    auto show = [&]() {
+        c_.labels++;
+        text_.charset = charSet_;
+        if (onLabel_) onLabel_(text_);
+    };
+    if ((CI & 037) == 2) {                                                // start of segment
+        const uint16_t prefix = (uint16_t)((data[0] << 8) | data[1]);
+        const int32_t field_1 = (prefix >> 8) & 017;
+        const bool Cflag = (prefix >> 12) & 1, first = (prefix >> 14) & 1, last = (prefix >> 13) & 1;
+        if (first) {
+            charSet_ = (prefix >> 4) & 017;
+            charSetSet_ = true;
+            text_ = label();
+        }
+        if (Cflag) {                                                      // the clear command: moreXPad stays as it was
+            text_ = label();
+            return;
+        }
+        const int32_t totalDataLength = field_1 + 1;
+        int32_t dataLength;
+        if (length - 2 < totalDataLength) {
+            dataLength = length - 2;
+            moreXPad_ = true;
+        } else {
+            dataLength = totalDataLength;
+            moreXPad_ = false;
+        }
+        append(data + 2, dataLength);
+        if (last) {
+            if (!moreXPad_)
+                show();
+            else
+                isLastSegment_ = true;
+        } else {
+            isLastSegment_ = false;
+        }
+        remainDataLength_ = totalDataLength - dataLength;
+    } else if ((CI & 037) == 3 && moreXPad_) {
+        int32_t dataLength;
+        if (remainDataLength_ > length) {
+            dataLength = length;
+            remainDataLength_ -= length;
+        } else {
+            dataLength = remainDataLength_;
+            moreXPad_ = false;
+        }
+        append(data, dataLength);
+        if (!moreXPad_ && isLastSegment_) show();
+    }
+}
+
+void padAssembler::add_MSC_element(const uint8_t *data, int32_t length) {
+    if (index_ < 0) {                                                     // rule 3: no length indicator yet
+        touched_ |= 4;
+        return;
+    }
+    if (index_ + length >= 8192) {
+        c_.guard_dropped++;
+        return;
+    }
+    for (int32_t i = 0; i < length; i++) buffer_[(size_t)index_++] = data[i];
+    hiwater_ = std::max(hiwater_, index_);
+    if (index_ < length_) return;
+    build_MSC_segment(length_);
+    index_ = 0;
+}
+
+void padAssembler::build_MSC_segment(int32_t length) {
+    auto H = [&](int32_t i) -> uint8_t {                                  // rule 3: a byte nothing ever wrote reads 0
+        if (i >= hiwater_) touched_ |= 4;
+        return buffer_[(size_t)i];
+    };
+    datagroup g;
+    const uint8_t b0 = H(0);
+    H(1);
+    g.groupType = b0 & 0xF;
+    g.extension = b0 & 0x80;
+    g.crc = b0 & 0x40;
+    g.segment = b0 & 0x20;
+    g.user_access = b0 & 0x10;
+    bool good = true;
+    if (g.crc) {
+        if (length < 2) {                                                 // rule 3
+            touched_ |= 4;
+            good = false;
+        } else {                                                          // pad_crc (:360-381)
+            uint16_t acc = 0xFFFF;
+            for (int32_t i = 0; i < length - 2; i++) {
+                acc ^= (uint16_t)(buffer_[(size_t)i] << 8);
+                for (int j = 0; j < 8; j++) acc = (acc & 0x8000) ? (uint16_t)((acc << 1) ^ 0x1021) : (uint16_t)(acc << 1);
+            }
+            good = (uint16_t)~((buffer_[(size_t)length - 2] << 8) | buffer_[(size_t)length - 1]) == acc;
+        }
+        if (!good) c_.crc_failed++;
+    }
+    int32_t index = g.extension ? 4 : 2;
+    if (g.segment) {
+        g.last = H(index) & 0x80;
+        g.segmentNumber = (uint16_t)(((H(index) & 0x7F) << 8) | H(index + 1));
+        index += 2;
+    }
+    if (g.user_access) {
+        g.lengthInd = H(index) & 0x0F;
+        if (H(index) & 0x10) {
+            g.transportId = (uint16_t)((H(index + 1) << 8) | H(index + 2));
+            index += 3 + (g.lengthInd - 2);
+        } else {
+            g.transport = false;                                          // "sorry no transportId"
+        }
+    }
+    g.accepted = good && (g.groupType == 3 || g.groupType == 4) && g.transport;
+    g.data_offset = index;
+    g.data_nbytes = std::max(0, length - index - (g.crc ? 2 : 0));
+    g.bytes.assign(buffer_.begin(), buffer_.begin() + length);
+    g.data.assign(buffer_.begin() + index, buffer_.begin() + index + g.data_nbytes);
+    c_.groups++;
+    if (onGroup_) onGroup_(g);
+}
+
 }  // namespace dabgpu

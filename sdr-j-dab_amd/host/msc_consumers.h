@@ -145,4 +145,61 @@ private:
     int32_t objects_ = 0, malformed_ = 0, badSegments_ = 0, otherTypes_ = 0;
 };
 
+// padHandler (pad-handler.cpp) for one DAB+ stream: the PAD of every good AU whose first
+// syntactic element is a data stream element in, dynamic labels and X-PAD MSC data groups out
+// through callbacks, where the reference emits showLabel or calls process_mscGroup.  The same
+// function, byte for byte, as the GPU's PAD layer (dabgpu_pad_aus in include/dabgpu.h, whose
+// rules 1-4 for what the reference leaves undefined hold here too: a PAD shorter than 2 bytes is
+// ignored, reads below the PAD give 0, a new handler has last_appType 0, no group in progress,
+// charSet 0 and a zeroed group buffer, the label record keeps 256 bytes and 64 pieces).
+// dynamicLabel's function-local statics are members.  Charset conversion is the caller's: the
+// label is the bytes the reference hands to toQStringUsingCharset, with the piece boundaries.
+class padAssembler {
+public:
+    struct label {
+        int32_t charset = 0;
+        int32_t nbytes = 0, n_pieces = 0;       // the full counts
+        bool truncated = false;
+        std::vector<uint8_t> piece_len;         // the first 64
+        std::vector<uint8_t> text;              // the first 256 bytes
+    };
+    struct datagroup {                          // build_MSC_segment's parse (:299-357)
+        std::vector<uint8_t> bytes;             // the group, msc_dataGroupLength bytes
+        int32_t data_offset = 0, data_nbytes = 0;   // the reference's index; max(0, length - index - CRC bytes)
+        bool extension = false, crc = false, segment = false, user_access = false, last = false, transport = true;
+        bool accepted = false;                  // handed to process_mscGroup
+        uint16_t segmentNumber = 0xFFFF, transportId = 0xFFFF;
+        uint8_t groupType = 0, lengthInd = 0;
+        std::vector<uint8_t> data;              // what process_mscGroup's pointer shows: the buffer from index, data_nbytes of it
+    };
+    using label_cb = std::function<void(const label &)>;
+    using datagroup_cb = std::function<void(const datagroup &)>;
+    padAssembler(label_cb on_label, datagroup_cb on_group);
+    // mp4Processor's part (mp4processor.cpp:255-265): au readable for nbytes, aac_frame_length its
+    // length (negative: the AU failed its CRC); bytes past the length read 0
+    void processAU(const uint8_t *au, int32_t nbytes, int32_t aac_frame_length);
+    // padHandler::processPAD on a PAD of count bytes (AU[2 .. 2 + count))
+    void processPAD(const uint8_t *pad, int32_t count);
+    struct counters {
+        int32_t labels = 0, groups = 0, aus = 0, pads = 0, unhandled = 0, undefined[4] = {0, 0, 0, 0}, crc_failed = 0,
+                guard_dropped = 0;
+    };
+    const counters &count() const { return c_; }
+private:
+    void dynamicLabel(const uint8_t *data, int32_t length, uint8_t CI);
+    void append(const uint8_t *piece, int32_t n);
+    void add_MSC_element(const uint8_t *data, int32_t length);
+    void build_MSC_segment(int32_t length);
+    label_cb onLabel_;
+    datagroup_cb onGroup_;
+    counters c_;
+    uint32_t touched_ = 0;                      // rules the current PAD met (bit k-1: rule k)
+    int32_t lastAppType_ = 0, index_ = -1, length_ = 0, charSet_ = 0, hiwater_ = 0;
+    bool lastSet_ = false, charSetSet_ = false;
+    int32_t remainDataLength_ = 0;
+    bool isLastSegment_ = false, moreXPad_ = false;
+    label text_;
+    std::vector<uint8_t> buffer_;
+};
+
 }  // namespace dabgpu

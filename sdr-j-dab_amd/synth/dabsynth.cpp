@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
+#include <string>
 #include <vector>
 #include <thread>
 #include <algorithm>
@@ -252,7 +253,11 @@ static bool superframe_layout_ok(int rsdims, int layout) {
 // one DAB+ superframe of rsdims RS columns; layout = 2 * dacRate + sbr: 4, 2, 6 or 3
 // access units whose start addresses the header carries (12 bits each after byte 3,
 // the first one implicit: mp4processor.cpp:163-195)
-void make_superframe(Rng &rng, int rsdims, uint8_t *sf /*[120*rsdims]*/, int layout = 0) {
+struct PadProgramme {
+    std::vector<std::vector<uint8_t>> pads;        // DABSYNTH_PAD: the PADs sent round and round, one an AU
+    size_t next = 0;
+};
+void make_superframe(Rng &rng, int rsdims, uint8_t *sf /*[120*rsdims]*/, int layout = 0, PadProgramme *prog = nullptr) {
     int n = 110 * rsdims;
     std::vector<uint8_t> d(n);
     for (auto &b : d) b = (uint8_t)rng.next();
@@ -269,6 +274,16 @@ void make_superframe(Rng &rng, int rsdims, uint8_t *sf /*[120*rsdims]*/, int lay
             const int pos = bit + b, v = (au[i] >> (11 - b)) & 1;
             d[pos >> 3] = (uint8_t)((d[pos >> 3] & ~(0x80 >> (pos & 7))) | (v << (7 - (pos & 7))));
         }
+    }
+    // DABSYNTH_PAD: every AU opens with a data stream element (id_syn_ele 4) that carries the
+    // programme's next PAD: AU[1] = count, the PAD in AU[2 .. 2 + count)
+    for (int i = 0; prog && !prog->pads.empty() && i < nau; i++) {
+        const std::vector<uint8_t> &pad = prog->pads[prog->next];
+        if ((int)pad.size() + 2 > au[i + 1] - au[i] - 2) continue;     // (an AU too short for it stays random)
+        prog->next = (prog->next + 1) % prog->pads.size();
+        d[au[i]] = (uint8_t)(0x80 | (d[au[i]] & 0x1F));
+        d[au[i] + 1] = (uint8_t)pad.size();
+        std::memcpy(&d[au[i] + 2], pad.data(), pad.size());
     }
     for (int i = 0; i < nau; i++) {
         int len = au[i + 1] - au[i] - 2;
@@ -365,6 +380,74 @@ void make_mot_carousel(uint64_t seed, int sub, std::vector<std::vector<uint8_t>>
                                         std::vector<uint8_t>(body.begin() + 100 * k, body.begin() + std::min(nbody, 100 * (k + 1)))));
         }
         for (int r = 0; r < 2; r++) out.insert(out.end(), obj.begin(), obj.end());
+    }
+}
+// ---- DABSYNTH_PAD: the programme-associated data of a DAB+ subchannel (EN 300 401 7.4) ----
+// A variable-size X-PAD, written as the receiver reads it, from the PAD's last byte down: the
+// two F-PAD bytes (type 0, X-PAD indicator 2, CI flag), the content indicators (application
+// type, length index into 4, 6, 8, 12, 16, 24, 32, 48), an end marker behind fewer than four,
+// then the sub-fields, each padded with zeros to its length.
+static std::vector<uint8_t> xpad(const std::vector<std::pair<int, int>> &cis, const std::vector<std::vector<uint8_t>> &fields) {
+    static const int len[8] = {4, 6, 8, 12, 16, 24, 32, 48};
+    std::vector<uint8_t> l = {0x02, 0x20};
+    for (auto &c : cis) l.push_back((uint8_t)((c.second << 5) | c.first));
+    if (cis.size() < 4) l.push_back(0);
+    for (size_t i = 0; i < cis.size(); i++) {
+        std::vector<uint8_t> f = fields[i];
+        f.resize((size_t)len[cis[i].second], 0);
+        l.insert(l.end(), f.begin(), f.end());
+    }
+    return std::vector<uint8_t>(l.rbegin(), l.rend());
+}
+// a short X-PAD: F-PAD (X-PAD indicator 1), one CI, three bytes, over two bytes of filling
+static std::vector<uint8_t> short_pad(int app, const std::vector<uint8_t> &d3) {
+    std::vector<uint8_t> l = {0x00, 0x10, (uint8_t)app, d3[0], d3[1], d3[2], 0, 0};
+    return std::vector<uint8_t>(l.rbegin(), l.rend());
+}
+// the two-byte prefix of a dynamic label segment: toggle, first, last, command flag, length - 1
+// (or the command), then the charset (first segment) or the segment number
+static std::vector<uint8_t> seg_prefix(int nbytes, bool first, bool last, int charset_or_segno, bool cflag = false) {
+    return {(uint8_t)((first << 6) | (last << 5) | (cflag << 4) | ((nbytes - 1) & 15)), (uint8_t)((charset_or_segno & 15) << 4)};
+}
+// a label in segments of at most 16 bytes; each opens in a type-2 sub-field of `sub` bytes
+// (length index li) and goes on in type-3 sub-fields in the following PADs
+static void label_pads(const std::string &text, int charset, int li, std::vector<std::vector<uint8_t>> &out) {
+    static const int len[8] = {4, 6, 8, 12, 16, 24, 32, 48};
+    const int nseg = ((int)text.size() + 15) / 16;
+    for (int sgm = 0; sgm < nseg; sgm++) {
+        const std::string t = text.substr((size_t)16 * sgm, 16);
+        std::vector<uint8_t> stream = seg_prefix((int)t.size(), sgm == 0, sgm == nseg - 1, sgm == 0 ? charset : sgm);
+        stream.insert(stream.end(), t.begin(), t.end());
+        int app = 2;
+        for (size_t pos = 0; pos < stream.size(); pos += (size_t)len[li], app = 3)
+            out.push_back(xpad({{app, li}}, {std::vector<uint8_t>(stream.begin() + pos, stream.begin() + std::min(stream.size(), pos + len[li]))}));
+    }
+}
+// The programme of subchannel `sub`: a label carousel -- a three-segment label in charset 15
+// whose segments run over several AUs, a three-byte label in short PADs, a clear command, a
+// one-segment label in charset 0 -- then one MOT slide (object 0 of make_mot_carousel: header
+// group, three body segments, CRCs, sent twice) as X-PAD data groups: a length indicator and a
+// type-12 sub-field of 48 bytes, then type-13 sub-fields of 48 bytes, one a PAD.
+void make_pad_programme(uint64_t seed, int sub, std::vector<std::vector<uint8_t>> &out) {
+    char txt[64];
+    std::snprintf(txt, sizeof txt, "DABSYNTH s%d - now playing: track %d", sub, (int)(seed % 90) + 10);
+    label_pads(txt, 15, 2, out);
+    std::vector<uint8_t> a = seg_prefix(3, true, true, 0);
+    a.push_back('A');
+    out.push_back(short_pad(2, a));
+    out.push_back(short_pad(3, {'B', 'C', '.'}));
+    out.push_back(xpad({{2, 0}}, {seg_prefix(1, false, false, 0, true)}));       // the clear command
+    std::snprintf(txt, sizeof txt, "sub %d charset 0", sub);
+    label_pads(txt, 0, 5, out);
+    std::vector<std::vector<uint8_t>> groups;
+    make_mot_carousel(seed, sub, groups);
+    for (int g = 0; g < 8; g++) {                                                // object 0, twice
+        const std::vector<uint8_t> &G = groups[(size_t)g];
+        const size_t n = G.size();
+        out.push_back(xpad({{1, 0}, {12, 7}}, {{(uint8_t)((n >> 8) & 63), (uint8_t)(n & 255), 0, 0},
+                                                std::vector<uint8_t>(G.begin(), G.begin() + std::min<size_t>(48, n))}));
+        for (size_t pos = 48; pos < n; pos += 48)
+            out.push_back(xpad({{13, 7}}, {std::vector<uint8_t>(G.begin() + pos, G.begin() + std::min(n, pos + 48))}));
     }
 }
 void make_packet_cif(Rng &rng, PacketState &st, int bitRate, int addr, uint8_t *info) {
@@ -566,6 +649,8 @@ static int gen_core(const dabsynth_cfg *cfg, uint64_t seed, int P, float *iq, ui
         if (cyc && sc.dabplus && NC % 5) return -3;      // superframes must tile the period
         if (cyc && !sc.dabplus && (sc.content == DABSYNTH_PACKET || sc.content == DABSYNTH_MOT)) return -4;   // groups do not wrap (dabsynth.h)
         if (!sc.dabplus && sc.content == DABSYNTH_MOT) make_mot_carousel(seed, s, pst[s].carousel);
+        PadProgramme prog;
+        if (sc.dabplus && sc.content == DABSYNTH_PAD) make_pad_programme(seed, s, prog.pads);
         frag_len[s] = sc.length * 64;
         enc_frag[s].assign((size_t)NE * frag_len[s], 0);
         std::vector<uint8_t> info(nb), mother(4 * (nb + 6)), punct(std::max<size_t>(frag_len[s], mother.size()));
@@ -595,7 +680,7 @@ static int gen_core(const dabsynth_cfg *cfg, uint64_t seed, int P, float *iq, ui
                             }
                             sf_count++;
                         }
-                        make_superframe(rng, rsdims, sf.data(), layout);
+                        make_superframe(rng, rsdims, sf.data(), layout, &prog);
                     }
                     const uint8_t v = sf[pos];
                     for (int b = 0; b < 8; b++) grid[(size_t)u * nb + 8 * byte + b] = (uint8_t)((v >> (7 - b)) & 1);
@@ -620,7 +705,7 @@ static int gen_core(const dabsynth_cfg *cfg, uint64_t seed, int P, float *iq, ui
                             }
                             sf_count++;
                         }
-                        make_superframe(rng, rsdims, sf.data(), layout);
+                        make_superframe(rng, rsdims, sf.data(), layout, &prog);
                     }
                     uint8_t v = sf[sf_pos];
                     for (int b = 0; b < 8; b++) info[8 * byte + b] = (uint8_t)((v >> (7 - b)) & 1);

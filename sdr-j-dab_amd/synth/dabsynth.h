@@ -39,12 +39,19 @@ typedef struct {
                             last with header and body in one segment);
                             with dabplus: 0 every superframe dacRate 0 / SBR 0 (4 AUs),
                             DABSYNTH_AU_MIX the superframes cycle through the four (dacRate, SBR)
-                            layouts of mp4processor.cpp:163-195 (4, 2, 6, 3 AUs) */
+                            layouts of mp4processor.cpp:163-195 (4, 2, 6, 3 AUs); DABSYNTH_PAD: layout
+                            0, every AU opening with a data stream element whose PAD carries a seeded
+                            programme, one PAD an AU, round and round: a label carousel (a
+                            three-segment label in charset 15 continued over several AUs, a label
+                            in short PADs, a clear command, a label in charset 0) and one MOT slide
+                            (transport id 0x1000 + 16 * subchannel, 230 bytes, header and three
+                            body segments with CRCs, sent twice) as X-PAD data groups */
 } dabsynth_subch;
 #define DABSYNTH_MP2 2
 #define DABSYNTH_PACKET 3
 #define DABSYNTH_AU_MIX 4
 #define DABSYNTH_MOT 5
+#define DABSYNTH_PAD 6
 
 typedef struct {
     int32_t n_frames;    /* frames after the pre-roll */
