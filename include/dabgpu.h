@@ -606,6 +606,110 @@ int dabgpu_pad_aus(dabgpu_ctx *ctx, void *state_d, int n_slots, const uint8_t *a
                    dabgpu_datagroup *groups_d, int group_slots, uint8_t *bytes_d, int64_t arena_bytes,
                    dabgpu_pad_run *run_d);
 
+/* ---- FIC layer: FIBs to the service database and the subchannel table (fib-processor.cpp) ----
+ * dabgpu_fic_db is what a fib_processor holds, as a plain record: the per-slot device state of
+ * dabgpu_fib_parse and what a caller downloads (host/fib_processor's export_db / import_db speak
+ * it too).  All zero is a new fib_processor; padding and reserved bytes stay zero, so two
+ * databases compare with memcmp.  Fields the reference never reads in a free entry are kept
+ * canonical: a service that is not inUse has serviceId 0 (the reference's -1 is never read), a
+ * component that was never bound has service 0.  Labels are the 16 bytes as transmitted with
+ * their charset (host: label_text for UTF-8). */
+typedef struct {            /* ficList[SubChId] (fib-processor.h: channelMap) */
+    int16_t SubChId;        /* never written by a FIG (FIG 0/14 matches it: only id 0 takes effect) */
+    int16_t StartAddr, Length, uepFlag, protLevel, BitRate, FEC_scheme;
+    uint8_t inUse;          /* a FIG 0/1 described it */
+    uint8_t reserved;
+} dabgpu_fic_subch;
+typedef struct {            /* components[i] (serviceComponent) */
+    uint8_t inUse;
+    int8_t TMid;
+    int16_t service;        /* index into services */
+    int16_t componentNr, ASCTy, PS_flag, subchannelId;
+    uint16_t SCId;
+    uint8_t CAflag;
+    int8_t DGflag;
+    int16_t DSCTy, packetAddress;
+} dabgpu_fic_component;
+typedef struct {            /* listofServices[i] (serviceId) */
+    int32_t serviceId;
+    uint8_t inUse, hasName, hasLanguage;
+    uint8_t charset;        /* of label */
+    int16_t language, programType;
+    uint8_t data_suffix;    /* the label came by FIG 1/5: its text ends in " (data)" */
+    uint8_t reserved[3];
+    uint8_t label[16];
+} dabgpu_fic_service;
+typedef struct {            /* what fib_processor::subchannels returns: the table dabgpu_pipe_set_subch takes */
+    int32_t n;
+    int32_t reserved[3];
+    dabgpu_subch sub[64];   /* the first n, in SubChId order; the rest zero */
+    uint8_t ids[64];        /* each entry's SubChId */
+} dabgpu_fic_table;
+typedef struct {
+    dabgpu_fic_subch sub[64];
+    dabgpu_fic_component components[64];
+    dabgpu_fic_service services[64];
+    int32_t EId;            /* of the nameofEnsemble signal */
+    uint8_t charset;
+    uint8_t named;          /* nameofEnsemble has been raised: the reference's firstTime, inverted */
+    uint8_t reserved[2];
+    uint8_t label[16];      /* the ensemble label of that signal */
+    uint8_t reserved2[8];
+    dabgpu_fic_table table; /* the table of the last dabgpu_fib_parse call on this record (all zero
+                               before the first; export_db leaves it alone, clearEnsemble too) */
+} dabgpu_fic_db;
+#define DABGPU_FIC_NAME_ENSEMBLE 1  /* nameofEnsemble (id, label): id = EId */
+#define DABGPU_FIC_ADD_SERVICE   2  /* addtoEnsemble (label): id = the service's slot */
+typedef struct {
+    int32_t kind;           /* DABGPU_FIC_* */
+    int32_t fib;            /* index in the call of the FIB that raised it */
+    int32_t id;
+    int32_t charset;
+    uint8_t label[16];
+} dabgpu_fic_event;
+#define DABGPU_FIC_EVENT_SLOTS 65   /* the most one call can raise without a clear between */
+typedef struct {
+    int32_t parsed, skipped;        /* FIBs walked / with ok == 0 */
+    int32_t figs[8];                /* FIG headers met, by type (7: the end marker) */
+    int32_t n_events;               /* raised; the first min(n_events, event_slots) are recorded */
+    int32_t overrun;                /* FIBs that met the overrun rule */
+    int32_t table_changed;          /* the table differs from the record's previous one */
+    int32_t reserved[3];
+} dabgpu_fic_run;
+/* fib_processor::process_FIB per slot: n_slots independent databases db_d [n_slots], updated in
+ * place.  Slot s takes the FIBs fibs_d + s * fib_stride + 32 * i, i < n_fibs, in order: 32 bytes
+ * each, msb first, the CRC bytes as delivered; FIBs with ok_d [n_slots][n_fibs] == 0 are skipped.
+ * Parsed as host/fib_processor.cpp does it, which cites the reference line by line: FIG 0/1, 0/2,
+ * 0/3, 0/14, 0/16, 0/17, FIG 1/0, 1/1, 1/5, FIG 2/5; find_service (the in-use entry, else the
+ * first free slot, else entry 0), find_packet_component and bind (once per service and
+ * component number, in the first free slot).
+ * Outputs per slot: events_d [n_slots][event_slots] in the order raised, each with the FIB that
+ * caused it (events past event_slots are counted and not recorded; the slots a call does not
+ * fill are zeroed); table_d [n_slots]:
+ * fib_processor::subchannels(ids, classic_audio, packet_data, mot, pad) at the end of the call,
+ * the four booleans being the bits DABGPU_SUBCH_MP2 | PACKET | MOT | PAD of want_flags; run_d
+ * [n_slots].
+ * Where the reference is undefined:
+ *   1. the overrun rule: a read at or past bit 256 of the FIB reads 0, control flow otherwise the
+ *      reference's (a FIG near the end of the data field whose length, component list or label
+ *      runs on; the reference reads whatever follows in its FIC buffer).  Such a FIB is counted
+ *      in overrun.  Counted are the reads host/fib_processor.cpp makes, in its order: the fields
+ *      this parser stores or branches on (the reference also reads fields it then drops, such as
+ *      FIG 0/3's CAOrg or the labels of FIG 1/3, 1/4 and 1/6);
+ *   2. a bind with the component table full writes nothing (the reference writes slot -1).
+ * Every index into the database, the event slots and the table is checked: no FIB makes the
+ * kernel leave its slot.  DABGPU_E_ARG for negative sizes or fib_stride < 32 * n_fibs.
+ * Asynchronous on the context stream. */
+size_t dabgpu_fic_db_bytes(void);
+int dabgpu_fib_parse(dabgpu_ctx *ctx, dabgpu_fic_db *db_d, int n_slots, const uint8_t *fibs_d, int64_t fib_stride,
+                     const uint8_t *ok_d, int n_fibs, int want_flags, dabgpu_fic_event *events_d, int event_slots,
+                     dabgpu_fic_table *table_d, dabgpu_fic_run *run_d);
+/* fib_processor::clearEnsemble for the slots with which_h[s] != 0 (host array [n_slots]; NULL:
+ * all): components, subchannels, services' inUse / serviceId / label and the ensemble's name go;
+ * each service's language, programType, hasLanguage (and hasName, until the entry is taken again)
+ * stay, as in the reference (:1149-1163). */
+int dabgpu_fic_clear(dabgpu_ctx *ctx, dabgpu_fic_db *db_d, int n_slots, const uint8_t *which_h);
+
 /* ---- streaming pipeline (ofdmProcessor::run + ficHandler + mscHandler) ---
  * n_streams independent ensembles; each call decodes n_frames frames per
  * stream.  Sync, AFC, DQPSK references and the 16-CIF time de-interleaver
@@ -852,6 +956,30 @@ int dabgpu_pipe_pad(dabgpu_pipe *p, const uint8_t *sf_bytes_d, int32_t sf_stride
  * hold is kept.  DABGPU_E_ARG for a negative value, max_pad > max_dabplus or fewer slots than an
  * applied table flags. */
 int dabgpu_pipe_pad_caps(dabgpu_pipe *p, int max_pad);
+/* FIC layer for the FIBs of the last dabgpu_pipe_run (call once per run, after it, in any order
+ * with the MSC layers): dabgpu_fib_parse on one database per stream, which is carried across
+ * runs.  fic_bits_d and fic_crc_d are those of that run (DABGPU_E_ARG otherwise), read as it wrote
+ * them -- one bit per byte [4][768] or DABGPU_PACK_FIC bytes [4][96] per frame -- and never
+ * written: each stream's 12 * n_frames FIBs in order, fic_crc_d as the ok flags (frames past
+ * frames_run have flags 0: a stream that ran out of samples commits fewer FIBs).  Outputs
+ * (device):
+ *   events_d [n_streams][DABGPU_FIC_EVENT_SLOTS]  (fib = 12 * frame + FIB of the frame)
+ *   table_d  [n_streams]: what dabgpu_pipe_set_subch takes (table.sub, table.n), with want_flags
+ *   run_d    [n_streams]
+ * Runs on the run's back-end stream behind its FIC decode (dabgpu_pipe_sync to wait).  The table
+ * is not applied on the device: dabgpu_pipe_set_subch is the host's call.  DABGPU_E_STATE without
+ * a layer (dabgpu_pipe_fic_caps), without a run with FIC output and CRC flags to consume, or on a
+ * second call for the same run. */
+int dabgpu_pipe_fic(dabgpu_pipe *p, const uint8_t *fic_bits_d, const uint8_t *fic_crc_d, int want_flags,
+                    dabgpu_fic_event *events_d, dabgpu_fic_table *table_d, dabgpu_fic_run *run_d);
+/* The FIC layer on (one new database per stream; a layer that is on keeps its databases) or off
+ * (they are freed).  A pipeline starts without it and then allocates and launches nothing for
+ * it.  Between runs; waits for everything enqueued. */
+int dabgpu_pipe_fic_caps(dabgpu_pipe *p, int on);
+/* one stream's database to db_h (host); waits for everything enqueued */
+int dabgpu_pipe_fic_db(dabgpu_pipe *p, int stream, dabgpu_fic_db *db_h);
+/* fib_processor::clearEnsemble for one stream's database (-1: every stream's), see dabgpu_fic_clear */
+int dabgpu_pipe_fic_clear(dabgpu_pipe *p, int stream);
 /* Compact superframe bytes for the following dabgpu_pipe_dabplus calls (on = 1): only the
  * superframes that complete in the run are stored, per (stream, DAB+ subchannel) in CIF
  * order -- sf_bytes_d [n_streams][n_dabplus][DABGPU_SF_SLOTS(n_frames)][sf_stride], the

@@ -343,6 +343,25 @@ struct PadJob {
     dabgpu_pad_run *run;            // [n_slots]
 };
 
+// FIC layer (k_fib.hip): n_slots fib_processors, each over its FIBs in order
+static_assert(sizeof(dabgpu_fic_subch) == 16 && sizeof(dabgpu_fic_component) == 20 && sizeof(dabgpu_fic_service) == 32 &&
+                  sizeof(dabgpu_fic_table) == 848 && sizeof(dabgpu_fic_db) == 5232 && sizeof(dabgpu_fic_db) % 16 == 0 &&
+                  sizeof(dabgpu_fic_event) == 32 && sizeof(dabgpu_fic_run) == 64,
+              "the FIC records are read as bytes by the bindings");
+struct FibJob {
+    int32_t n_slots, n_fibs;
+    dabgpu_fic_db *db;              // [n_slots], 16-byte aligned
+    const uint8_t *fibs;            // slot s, FIB i at fibs + s * stride + i * (bit_src ? 256 : 32)
+    int64_t stride;
+    int32_t bit_src;                // the FIBs are one bit per byte (the pipeline's unpacked FIC)
+    const uint8_t *ok;              // [n_slots][n_fibs]
+    int32_t want;                   // DABGPU_SUBCH_MP2 | PACKET | MOT | PAD
+    dabgpu_fic_event *events;       // [n_slots][event_slots]
+    int32_t event_slots;
+    dabgpu_fic_table *table;        // [n_slots]
+    dabgpu_fic_run *run;            // [n_slots]
+};
+
 
 // iq: samples in format fmt (DABGPU_IQ_*); frame descriptors count samples
 hipError_t launch_prs_sync(hipStream_t st, const void *iq, int fmt, const dabgpu_frame *fr, int n, const OfdmTables &T,
@@ -381,5 +400,7 @@ hipError_t launch_mp2_sync(hipStream_t st, const Mp2SyncJob &job);
 hipError_t launch_packet(hipStream_t st, const PkJob &job);
 hipError_t launch_mot(hipStream_t st, const MotJob &job);
 hipError_t launch_pad(hipStream_t st, const PadJob &job);
+hipError_t launch_fib(hipStream_t st, const FibJob &job);
+hipError_t launch_fic_clear(hipStream_t st, dabgpu_fic_db *db, int n_slots);
 
 }  // namespace dab

@@ -782,6 +782,50 @@ int dabgpu_pad_aus(dabgpu_ctx *c, void *state, int n_slots, const uint8_t *aus, 
     return 0;
 }
 
+size_t dabgpu_fic_db_bytes(void) { return sizeof(dabgpu_fic_db); }
+
+int dabgpu_fib_parse(dabgpu_ctx *c, dabgpu_fic_db *db, int n_slots, const uint8_t *fibs, int64_t fib_stride, const uint8_t *ok,
+                     int n_fibs, int want_flags, dabgpu_fic_event *events, int event_slots, dabgpu_fic_table *table,
+                     dabgpu_fic_run *run) {
+    if (!c || !db || !table || !run || n_slots < 0 || n_fibs < 0 || event_slots < 0 || (n_fibs && (!fibs || !ok)) ||
+        (event_slots && !events))
+        return fail(DABGPU_E_ARG, "bad args");
+    if (fib_stride < (int64_t)32 * n_fibs) return fail(DABGPU_E_ARG, "fib_stride %lld below 32 * n_fibs", (long long)fib_stride);
+    if ((uintptr_t)db & 15) return fail(DABGPU_E_ARG, "db_d must be 16-byte aligned");
+    if (event_slots > (1 << 24)) return fail(DABGPU_E_ARG, "event_slots %d", event_slots);
+    if (!n_slots) return 0;
+    FibJob J;
+    memset(&J, 0, sizeof J);
+    J.n_slots = n_slots;
+    J.n_fibs = n_fibs;
+    J.db = db;
+    J.fibs = fibs;
+    J.stride = fib_stride;
+    J.ok = ok;
+    J.want = want_flags & (DABGPU_SUBCH_MP2 | DABGPU_SUBCH_PACKET | DABGPU_SUBCH_MOT | DABGPU_SUBCH_PAD);
+    J.events = events;
+    J.event_slots = event_slots;
+    J.table = table;
+    J.run = run;
+    HIPCHK(launch_fib(c->stream, J));
+    return 0;
+}
+
+int dabgpu_fic_clear(dabgpu_ctx *c, dabgpu_fic_db *db, int n_slots, const uint8_t *which) {
+    if (!c || !db || n_slots < 0) return fail(DABGPU_E_ARG, "bad args");
+    for (int s = 0; s < n_slots;) {                // one launch per run of chosen slots
+        if (which && !which[s]) {
+            s++;
+            continue;
+        }
+        int e = s;
+        while (e < n_slots && (!which || which[e])) e++;
+        HIPCHK(launch_fic_clear(c->stream, db + s, e - s));
+        s = e;
+    }
+    return 0;
+}
+
 size_t dabgpu_mot_state_bytes(int max_body_bytes) {
     if (max_body_bytes < 0 || max_body_bytes > (1 << 24)) return 0;
     const size_t cap = ((size_t)(max_body_bytes ? max_body_bytes : DABGPU_MOT_BODY_BYTES) + 15) / 16 * 16;

@@ -109,6 +109,13 @@ struct PadLayer {
     Event ev;                     // the last pass
 };
 
+// FIC layer (a fib_processor's database per stream): allocated only while dabgpu_pipe_fic_caps is on
+struct FicLayer {
+    DevBuf<uint8_t> db_d;         // [S] dabgpu_fic_db, updated in place
+    Event ev;                     // the last pass
+    bool on = false;
+};
+
 struct dabgpu_pipe {
     dabgpu_ctx *c = nullptr;
     int S = 0, F = 0, NSUB = 0, R = 0, NDP = 0, NMP = 0, NPK = 0, NMOT = 0, NPAD = 0;
@@ -190,6 +197,11 @@ struct dabgpu_pipe {
     int32_t dp_sf_stride = 0;
     bool dp_sf_compact = false;
     bool pad_pending = false;        // ... have not entered the PAD layer yet
+    FicLayer fic;
+    // the FIC outputs of the last run, which dabgpu_pipe_fic reads
+    const uint8_t *last_fic = nullptr, *last_crc = nullptr;
+    bool last_fic_packed = false;
+    bool fic_pending = false;        // ... have not entered the FIC layer yet
     const uint8_t *last_msc = nullptr; // MSC bits of the last run
     bool dp_pending = false, mp2_pending = false, pk_pending = false;   // the last run's CIFs have not entered the layer yet
     int32_t last_msc_stride = 0;
@@ -1159,6 +1171,7 @@ int dabgpu_pipe_run(dabgpu_pipe *p, const void *iq, int64_t stride, const int64_
     p->last_frames.assign((size_t)S * F, dabgpu_frame());
     p->last_info.assign((size_t)S * F, dabgpu_frame_info());
     p->last_msc = nullptr;
+    p->fic_pending = false;
     if (p->profiling == 1) p->ev_rec.clear();   // modes 2, 3 accumulate over runs
     p->ev_front_demod = false;
     // at most one run of overlap: run r-2's ACS, the last reader of the ring slots this
@@ -1220,6 +1233,10 @@ int dabgpu_pipe_run(dabgpu_pipe *p, const void *iq, int64_t stride, const int64_
     p->dp_pending = p->mp2_pending = p->pk_pending = have_rows;
     p->mot_pending = false;                    // until this run's dabgpu_pipe_packet
     p->pad_pending = false;                    // until this run's dabgpu_pipe_dabplus
+    p->last_fic = fic_bits;
+    p->last_crc = fic_crc;
+    p->last_fic_packed = p->fic_packed;
+    p->fic_pending = fic_bits && fic_crc;
     p->last_msc_stride = msc_stride;
     p->last_msc_packed = p->packed;
     publish_validity(p, done, have_rows, msc_valid);
@@ -1373,6 +1390,72 @@ int dabgpu_pipe_pad_caps(dabgpu_pipe *p, int max_pad) {
     if (int rc = pad_size(p, max_pad)) return rc;
     p->pad_pending = false;
     return rebuild_tables(p);
+}
+
+int dabgpu_pipe_fic_caps(dabgpu_pipe *p, int on) {
+    if (!p) return fail(DABGPU_E_ARG, "null pipe");
+    if (int rc = sync_streams(p)) return rc;
+    p->fic_pending = false;
+    if (!on) {
+        p->fic = FicLayer();
+        return 0;
+    }
+    if (p->fic.on) return 0;                   // the databases stay
+    const size_t nb = (size_t)p->S * sizeof(dabgpu_fic_db);
+    HIPCHK(p->fic.db_d.alloc(nb));
+    HIPCHK(p->fic.ev.create(hipEventDisableTiming));
+    HIPCHK(hipMemset(p->fic.db_d, 0, nb));
+    p->fic.on = true;
+    return 0;
+}
+
+int dabgpu_pipe_fic(dabgpu_pipe *p, const uint8_t *fic_bits, const uint8_t *fic_crc, int want_flags, dabgpu_fic_event *events,
+                    dabgpu_fic_table *table, dabgpu_fic_run *run) {
+    if (!p || !fic_bits || !fic_crc || !events || !table || !run) return fail(DABGPU_E_ARG, "null arg");
+    if (!p->fic.on) return fail(DABGPU_E_STATE, "no FIC layer in this pipeline (dabgpu_pipe_fic_caps)");
+    if (!p->fic_pending) return fail(DABGPU_E_STATE, "no dabgpu_pipe_run with FIC output to consume");
+    if (fic_bits != p->last_fic || fic_crc != p->last_crc)
+        return fail(DABGPU_E_ARG, "fic_bits_d and fic_crc_d are not those of the last dabgpu_pipe_run");
+    FibJob J;
+    memset(&J, 0, sizeof J);
+    J.n_slots = p->S;
+    J.n_fibs = 12 * p->F;
+    J.db = (dabgpu_fic_db *)(uint8_t *)p->fic.db_d;
+    J.fibs = fic_bits;
+    J.bit_src = p->last_fic_packed ? 0 : 1;
+    J.stride = (int64_t)J.n_fibs * (J.bit_src ? 256 : 32);
+    J.ok = fic_crc;
+    J.want = want_flags & (DABGPU_SUBCH_MP2 | DABGPU_SUBCH_PACKET | DABGPU_SUBCH_MOT | DABGPU_SUBCH_PAD);
+    J.events = events;
+    J.event_slots = DABGPU_FIC_EVENT_SLOTS;
+    J.table = table;
+    J.run = run;
+    // on the run's back-end stream, behind its FIC decode; after the previous pass (the
+    // databases are updated in place)
+    hipStream_t bs = p->back[p->cur].stream;
+    HIPCHK(p->fic.ev.wait_on(bs));
+    HIPCHK(launch_fib(bs, J));
+    HIPCHK(p->fic.ev.record(bs));
+    p->fic_pending = false;                    // each run's FIBs enter the layer once
+    return 0;
+}
+
+int dabgpu_pipe_fic_db(dabgpu_pipe *p, int stream, dabgpu_fic_db *db_h) {
+    if (!p || !db_h || stream < 0 || stream >= p->S) return fail(DABGPU_E_ARG, "bad args");
+    if (!p->fic.on) return fail(DABGPU_E_STATE, "no FIC layer in this pipeline (dabgpu_pipe_fic_caps)");
+    if (int rc = sync_streams(p)) return rc;
+    HIPCHK(hipMemcpy(db_h, p->fic.db_d + (size_t)stream * sizeof(dabgpu_fic_db), sizeof(dabgpu_fic_db), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int dabgpu_pipe_fic_clear(dabgpu_pipe *p, int stream) {
+    if (!p || stream < -1 || stream >= p->S) return fail(DABGPU_E_ARG, "bad args");
+    if (!p->fic.on) return fail(DABGPU_E_STATE, "no FIC layer in this pipeline (dabgpu_pipe_fic_caps)");
+    if (int rc = sync_streams(p)) return rc;
+    dabgpu_fic_db *db = (dabgpu_fic_db *)(uint8_t *)p->fic.db_d;
+    HIPCHK(launch_fic_clear(p->c->stream, stream < 0 ? db : db + stream, stream < 0 ? p->S : 1));
+    HIPCHK(hipStreamSynchronize(p->c->stream));
+    return 0;
 }
 
 int dabgpu_pipe_mp2(dabgpu_pipe *p, int16_t *pcm, dabgpu_mp2_info *info) {

@@ -188,6 +188,73 @@ def pad_aus(ctx: "Context", aus: np.ndarray, lengths: np.ndarray, state: Optiona
             b.free()
 
 
+# ---- FIC layer: the records of dabgpu_fib_parse (dabgpu.h) ----
+_SUBCH_DTYPE = np.dtype([("startAddr", "<i2"), ("length", "<i2"), ("bitRate", "<i2"), ("protLevel", "<i2"),
+                         ("uepFlag", "<i2"), ("flags", "<i2")])                                          # dabgpu_subch
+FIC_TABLE_DTYPE = np.dtype([("n", "<i4"), ("reserved", "<i4", (3,)), ("sub", _SUBCH_DTYPE, (64,)),
+                            ("ids", "u1", (64,))])                                                       # dabgpu_fic_table
+FIC_DB_DTYPE = np.dtype([
+    ("sub", np.dtype([("SubChId", "<i2"), ("StartAddr", "<i2"), ("Length", "<i2"), ("uepFlag", "<i2"), ("protLevel", "<i2"),
+                      ("BitRate", "<i2"), ("FEC_scheme", "<i2"), ("inUse", "u1"), ("reserved", "u1")]), (64,)),
+    ("components", np.dtype([("inUse", "u1"), ("TMid", "i1"), ("service", "<i2"), ("componentNr", "<i2"), ("ASCTy", "<i2"),
+                             ("PS_flag", "<i2"), ("subchannelId", "<i2"), ("SCId", "<u2"), ("CAflag", "u1"), ("DGflag", "i1"),
+                             ("DSCTy", "<i2"), ("packetAddress", "<i2")]), (64,)),
+    ("services", np.dtype([("serviceId", "<i4"), ("inUse", "u1"), ("hasName", "u1"), ("hasLanguage", "u1"), ("charset", "u1"),
+                           ("language", "<i2"), ("programType", "<i2"), ("data_suffix", "u1"), ("reserved", "u1", (3,)),
+                           ("label", "u1", (16,))]), (64,)),
+    ("EId", "<i4"), ("charset", "u1"), ("named", "u1"), ("reserved", "u1", (2,)), ("label", "u1", (16,)),
+    ("reserved2", "u1", (8,)), ("table", FIC_TABLE_DTYPE)])                                              # dabgpu_fic_db
+FIC_EVENT_DTYPE = np.dtype([("kind", "<i4"), ("fib", "<i4"), ("id", "<i4"), ("charset", "<i4"),
+                            ("label", "u1", (16,))])                                                     # dabgpu_fic_event
+FIC_RUN_DTYPE = np.dtype([("parsed", "<i4"), ("skipped", "<i4"), ("figs", "<i4", (8,)), ("n_events", "<i4"),
+                          ("overrun", "<i4"), ("table_changed", "<i4"), ("reserved", "<i4", (3,))])      # dabgpu_fic_run
+FIC_NAME_ENSEMBLE, FIC_ADD_SERVICE, FIC_EVENT_SLOTS = 1, 2, 65
+
+
+def fic_db_bytes() -> int:
+    """dabgpu_fic_db_bytes: a fib_processor's database as a record (all zero: a new one)"""
+    return int(lib().dabgpu_fic_db_bytes())
+
+
+def table_subch(table) -> list:
+    """the Subch list of one FIC_TABLE_DTYPE record, as Pipeline.set_subch takes it"""
+    return [Subch(*[int(x) for x in e]) for e in table["sub"][:int(table["n"])]]
+
+
+def fib_parse(ctx: "Context", fibs: np.ndarray, ok: np.ndarray, db: Optional[np.ndarray] = None, want: int = 0,
+              event_slots: int = FIC_EVENT_SLOTS, clear=None):
+    """fib_processor::process_FIB per slot (dabgpu_fib_parse; fib-processor.cpp): fibs [n_slots,
+    n_fibs, 32] uint8 (msb first, CRC bytes as delivered), ok [n_slots, n_fibs] uint8 (0: the FIB
+    is skipped), db [n_slots] FIC_DB_DTYPE carried from an earlier call (None: new
+    fib_processors), want the SUBCH_MP2 | PACKET | MOT | PAD bits the table may flag.  clear
+    [n_slots] (optional): clearEnsemble for the slots it marks, before the parse
+    (dabgpu_fic_clear).  Returns (db [n_slots] FIC_DB_DTYPE, events [n_slots, event_slots]
+    FIC_EVENT_DTYPE -- the first min(run.n_events, event_slots) of a row --, table [n_slots]
+    FIC_TABLE_DTYPE, run [n_slots] FIC_RUN_DTYPE)."""
+    fibs = np.ascontiguousarray(fibs, dtype=np.uint8)
+    n, nf = fibs.shape[:2]
+    assert fibs.shape == (n, nf, 32)
+    ok = np.ascontiguousarray(ok, dtype=np.uint8).reshape(n, nf)
+    st = np.zeros(n, FIC_DB_DTYPE) if db is None else np.ascontiguousarray(db, dtype=FIC_DB_DTYPE).reshape(n)
+    es = int(event_slots)
+    ds = ctx.put(st.view(np.uint8)) if n else ctx.buf(16)
+    df, dk = ctx.put(fibs) if fibs.size else ctx.buf(16), ctx.put(ok) if ok.size else ctx.buf(16)
+    de = ctx.buf(max(16, n * max(es, 0) * FIC_EVENT_DTYPE.itemsize)).zero()
+    dt, dr = ctx.buf(max(16, n * FIC_TABLE_DTYPE.itemsize)).zero(), ctx.buf(max(16, n * FIC_RUN_DTYPE.itemsize)).zero()
+    try:
+        if clear is not None:
+            which = np.ascontiguousarray(clear, dtype=np.uint8).reshape(n)
+            _chk(lib().dabgpu_fic_clear(ctx.h, ds.ptr, n, _p(which)), "dabgpu_fic_clear")
+        _chk(lib().dabgpu_fib_parse(ctx.h, ds.ptr, n, df.ptr, 32 * nf, dk.ptr, nf, int(want), de.ptr, es, dt.ptr, dr.ptr),
+             "dabgpu_fib_parse")
+        ctx.sync()
+        return (_records(ds, FIC_DB_DTYPE, (n,)), _records(de, FIC_EVENT_DTYPE, (n, max(es, 0))),
+                _records(dt, FIC_TABLE_DTYPE, (n,)), _records(dr, FIC_RUN_DTYPE, (n,)))
+    finally:
+        for b in (ds, df, dk, de, dt, dr):
+            b.free()
+
+
 SUPERFRAME_DTYPE = np.dtype([("status", "i1"), ("num_aus", "i1"), ("n_corrected", "<i2"), ("au_start", "<i2", (7,)),
                              ("au_crc_ok", "u1"), ("reserved", "u1")])
 
@@ -284,6 +351,13 @@ def lib() -> C.CDLL:
             "dabgpu_mot_groups": ([vp, vp, i32, i32, vp, i32, vp, i64, vp, vp, vp, i64, vp], i32),
             "dabgpu_pad_state_bytes": ([], sz),
             "dabgpu_pad_aus": ([vp, vp, i32, vp, i64, vp, i32, vp, vp, i32, vp, i32, vp, i64, vp], i32),
+            "dabgpu_fic_db_bytes": ([], sz),
+            "dabgpu_fib_parse": ([vp, vp, i32, vp, i64, vp, i32, i32, vp, i32, vp, vp], i32),
+            "dabgpu_fic_clear": ([vp, vp, i32, vp], i32),
+            "dabgpu_pipe_fic_caps": ([vp, i32], i32),
+            "dabgpu_pipe_fic": ([vp, vp, vp, i32, vp, vp, vp], i32),
+            "dabgpu_pipe_fic_db": ([vp, i32, vp], i32),
+            "dabgpu_pipe_fic_clear": ([vp, i32], i32),
             "dabgpu_pipe_mot": ([vp, vp, vp, vp], i32),
             "dabgpu_pipe_pad": ([vp, vp, i32, vp, vp, vp, vp, vp], i32),
             "dabgpu_pipe_pad_caps": ([vp, i32], i32),
@@ -929,6 +1003,7 @@ class Pipeline:
         self._pad = []
         self.max_pad = sum(1 for s in self.subch if s.flags & SUBCH_PAD)
         self._pad_bufs()
+        self._fic = []                   # the FIC layer's outputs, while fic_caps is on
 
     def _pad_bufs(self) -> None:
         for o in self._pad:
@@ -966,6 +1041,45 @@ class Pipeline:
         S, NP, ns = self.S, self.max_pad, 4 * pad_au_slots(self.F)
         return (_records(self.padl_d, PAD_LABEL_DTYPE, (S, NP, ns)), _records(self.padg_d, DATAGROUP_DTYPE, (S, NP, ns)),
                 self.padb_d.download(np.uint8, (S, NP, pad_arena_bytes(self.F))), _records(self.padr_d, PAD_RUN_DTYPE, (S, NP)))
+
+    def fic_caps(self, on: bool = True) -> None:
+        """the FIC layer on (a new database per stream) or off (dabgpu_pipe_fic_caps), between runs"""
+        _chk(lib().dabgpu_pipe_fic_caps(self.h, 1 if on else 0), "dabgpu_pipe_fic_caps")
+        for o in self._fic:
+            for b in o:
+                b.free()
+        self._fic = []
+        if on:
+            S = self.S
+            self._fic = [(self.ctx.buf(S * FIC_EVENT_SLOTS * FIC_EVENT_DTYPE.itemsize), self.ctx.buf(S * FIC_TABLE_DTYPE.itemsize),
+                          self.ctx.buf(S * FIC_RUN_DTYPE.itemsize)) for _ in range(2)]
+
+    def fic(self, want: int = 0, download: bool = True):
+        """FIC layer over the FIBs of this run (dabgpu_pipe_fic; fib-processor.cpp).  Returns
+        (events [S, FIC_EVENT_SLOTS] FIC_EVENT_DTYPE -- the first run.n_events of a row --,
+        table [S] FIC_TABLE_DTYPE, run [S] FIC_RUN_DTYPE)."""
+        if not self._fic:                # no layer: there are no output buffers to hand to the library,
+            e = DabError("dabgpu_pipe_fic: no FIC layer in this pipeline (fic_caps)")   # which would refuse as well
+            e.code = -6
+            raise e
+        self.fice_d, self.fict_d, self.ficr_d = self._fic[(self._run - 1) & 1]
+        _chk(lib().dabgpu_pipe_fic(self.h, self.fic_d.ptr, self.crc_d.ptr, int(want), self.fice_d.ptr, self.fict_d.ptr,
+                                   self.ficr_d.ptr), "dabgpu_pipe_fic")
+        if not download:
+            return None
+        self.sync()
+        return (_records(self.fice_d, FIC_EVENT_DTYPE, (self.S, FIC_EVENT_SLOTS)), _records(self.fict_d, FIC_TABLE_DTYPE, (self.S,)),
+                _records(self.ficr_d, FIC_RUN_DTYPE, (self.S,)))
+
+    def fic_db(self, stream: int) -> np.ndarray:
+        """one stream's database, a FIC_DB_DTYPE record (dabgpu_pipe_fic_db)"""
+        db = np.zeros(1, FIC_DB_DTYPE)
+        _chk(lib().dabgpu_pipe_fic_db(self.h, int(stream), _p(db)), "dabgpu_pipe_fic_db")
+        return db[0]
+
+    def fic_clear(self, stream: int = -1) -> None:
+        """clearEnsemble for one stream's database, -1 for all (dabgpu_pipe_fic_clear)"""
+        _chk(lib().dabgpu_pipe_fic_clear(self.h, int(stream)), "dabgpu_pipe_fic_clear")
 
     def _mot_bufs(self) -> None:
         for o in self._mot:
@@ -1244,7 +1358,7 @@ class Pipeline:
 
     def close(self) -> None:
         if self.h:
-            for o in self._outs + self._sf + self._mp2 + self._pkt + self._mot + self._pad:
+            for o in self._outs + self._sf + self._mp2 + self._pkt + self._mot + self._pad + self._fic:
                 for b in o:
                     b.free()
             lib().dabgpu_pipe_destroy(self.h)

@@ -258,6 +258,19 @@ ensembleDecoder::ensembleDecoder(const config &cfg) : cfg_(cfg) {
     if (cfg.auto_layout) {
         fibs_.resize(cfg.n_streams);
         parsed_.resize(cfg.n_streams);
+        for (int s = 0; s < cfg.n_streams; s++)
+            fibs_[s].on_event([this, s](int kind, int32_t id, const uint8_t *raw, int charset) {
+                const std::string text = fib_processor::label_text(raw, 16, charset);
+                if (kind == DABGPU_FIC_NAME_ENSEMBLE && ens_name_cb_) ens_name_cb_(s, fib_frame_, (uint32_t)id, text);
+                if (kind == DABGPU_FIC_ADD_SERVICE && svc_name_cb_) svc_name_cb_(s, fib_frame_, text);
+            });
+        if (cfg.fic_on_gpu) {
+            chk(dabgpu_pipe_fic_caps(pipe_, 1), "dabgpu_pipe_fic_caps");
+            fce_.resize((size_t)cfg.n_streams * DABGPU_FIC_EVENT_SLOTS * sizeof(dabgpu_fic_event));
+            fct_.resize((size_t)cfg.n_streams * sizeof(dabgpu_fic_table));
+            fcr_.resize((size_t)cfg.n_streams * sizeof(dabgpu_fic_run));
+            fic_tab_.resize(cfg.n_streams);
+        }
     }
     // the MSC and the FIBs leave the GPU packed (8 bits per byte, 1/8 of the bytes over
     // PCIe) and are unpacked here for the one-bit-per-byte consumers (dab-concurrent.cpp:191,
@@ -501,27 +514,54 @@ bool ensembleDecoder::step() {
                                    valid.data());
     if (rc != DABGPU_OK && rc != DABGPU_E_STATE) chk(rc, "dabgpu_pipe_run");
     const bool ok = rc == DABGPU_OK;
+    const bool gpu_fic = cfg_.auto_layout && cfg_.fic_on_gpu;
+    if (gpu_fic) {                 // behind the run's FIC decode, on its back-end stream
+        const int want = (pcm_cb_ && nmp_ > 0 ? DABGPU_SUBCH_MP2 : 0) | (dg_cb_ && npk_ > 0 ? DABGPU_SUBCH_PACKET : 0) |
+                         (mot_cb_ && nmot_ > 0 ? DABGPU_SUBCH_MOT : 0) |
+                         ((label_cb_ || pad_dg_cb_ || pad_obj_cb_) && npad_ > 0 ? DABGPU_SUBCH_PAD : 0);
+        chk(dabgpu_pipe_fic(pipe_, (const uint8_t *)fic_.get(), (const uint8_t *)crc_.get(), want, (dabgpu_fic_event *)fce_.get(),
+                            (dabgpu_fic_table *)fct_.get(), (dabgpu_fic_run *)fcr_.get()), "dabgpu_pipe_fic");
+    }
     chk(dabgpu_pipe_sync(pipe_), "dabgpu_pipe_sync");
     // frames committed per stream (a stream that lost sync re-acquired inside the run;
     // one that ran out of samples committed fewer): FIC and MSC for those
     std::vector<dabgpu_frame_info> fr((size_t)S * F);
     chk(dabgpu_pipe_frame_info(pipe_, fr.data()), "dabgpu_pipe_frame_info");
-    std::vector<uint8_t> fic((size_t)S * F * 4 * 96), crc((size_t)S * F * 12);
-    fic_.download(fic.data(), fic.size());
-    crc_.download(crc.data(), crc.size());
-    uint8_t fib[256];
-    for (int s = 0; s < S && (fib_cb_ || cfg_.auto_layout); s++)
-        for (int f = 0; f < F; f++) {
-            if (!fr[(size_t)s * F + f].committed) continue;
-            for (int b = 0; b < 4; b++)
-                for (int k = 0; k < 3; k++) {
-                    const uint8_t *pk = fic.data() + (((size_t)s * F + f) * 4 + b) * 96 + 32 * k;   // FIB bytes
-                    for (int i = 0; i < 256; i++) fib[i] = (uint8_t)((pk[i >> 3] >> (7 - (i & 7))) & 1);
-                    const bool good = crc[((size_t)s * F + f) * 12 + 3 * b + k] != 0;
-                    if (cfg_.auto_layout && good) fibs_[s].process_FIB(fib, (uint16_t)b);
-                    if (fib_cb_) fib_cb_(s, frames_done_[s] + f, b, fib, good);
-                }
-        }
+    if (gpu_fic) {                 // the names, where the host's parse delivers them; the tables for the end of the step
+        std::vector<dabgpu_fic_run> run(S);
+        std::vector<dabgpu_fic_event> ev((size_t)S * DABGPU_FIC_EVENT_SLOTS);
+        fcr_.download(run.data(), run.size() * sizeof(dabgpu_fic_run));
+        fct_.download(fic_tab_.data(), fic_tab_.size() * sizeof(dabgpu_fic_table));
+        bool any = false;
+        for (const dabgpu_fic_run &r : run) any |= r.n_events > 0;
+        if (any && (ens_name_cb_ || svc_name_cb_)) fce_.download(ev.data(), ev.size() * sizeof(dabgpu_fic_event));
+        for (int s = 0; s < S && (ens_name_cb_ || svc_name_cb_); s++)
+            for (int i = 0; i < std::min(run[s].n_events, DABGPU_FIC_EVENT_SLOTS); i++) {
+                const dabgpu_fic_event &e = ev[(size_t)s * DABGPU_FIC_EVENT_SLOTS + i];
+                const std::string text = fib_processor::label_text(e.label, 16, e.charset);
+                if (e.kind == DABGPU_FIC_NAME_ENSEMBLE && ens_name_cb_) ens_name_cb_(s, frames_done_[s] + e.fib / 12, (uint32_t)e.id, text);
+                if (e.kind == DABGPU_FIC_ADD_SERVICE && svc_name_cb_) svc_name_cb_(s, frames_done_[s] + e.fib / 12, text);
+            }
+    }
+    if (fib_cb_ || (cfg_.auto_layout && !gpu_fic)) {
+        std::vector<uint8_t> fic((size_t)S * F * 4 * 96), crc((size_t)S * F * 12);
+        fic_.download(fic.data(), fic.size());
+        crc_.download(crc.data(), crc.size());
+        uint8_t fib[256];
+        for (int s = 0; s < S; s++)
+            for (int f = 0; f < F; f++) {
+                if (!fr[(size_t)s * F + f].committed) continue;
+                fib_frame_ = frames_done_[s] + f;
+                for (int b = 0; b < 4; b++)
+                    for (int k = 0; k < 3; k++) {
+                        const uint8_t *pk = fic.data() + (((size_t)s * F + f) * 4 + b) * 96 + 32 * k;   // FIB bytes
+                        for (int i = 0; i < 256; i++) fib[i] = (uint8_t)((pk[i >> 3] >> (7 - (i & 7))) & 1);
+                        const bool good = crc[((size_t)s * F + f) * 12 + 3 * b + k] != 0;
+                        if (cfg_.auto_layout && !gpu_fic && good) fibs_[s].process_FIB(fib, (uint16_t)b);
+                        if (fib_cb_) fib_cb_(s, frames_done_[s] + f, b, fib, good);
+                    }
+            }
+    }
     if (NS && msc_cb_) {
         std::vector<uint8_t> msc((size_t)S * 4 * F * NS * msc_stride_), bits(maxbits_), ev((size_t)S * 4 * F * NS);
         msc_.download(msc.data(), msc.size());
@@ -735,10 +775,15 @@ bool ensembleDecoder::step() {
     // FIC first: a table parsed twice alike (two steps) and not yet applied is applied now
     for (int s = 0; s < S && cfg_.auto_layout; s++) {
         std::vector<dabgpu_subch> now;
-        for (const fib_subch &e : fibs_[s].subchannels(nullptr, pcm_cb_ != nullptr && nmp_ > 0, dg_cb_ != nullptr && npk_ > 0,
-                                                       mot_cb_ != nullptr && nmot_ > 0,
-                                                       (label_cb_ || pad_dg_cb_ || pad_obj_cb_) && npad_ > 0))
-            now.push_back({e.startAddr, e.length, e.bitRate, e.protLevel, e.uepFlag, e.flags});
+        if (cfg_.fic_on_gpu) {     // the device's table of this step (dabgpu_pipe_fic)
+            const dabgpu_fic_table &t = fic_tab_[s];
+            now.assign(t.sub, t.sub + std::max(0, std::min(t.n, 64)));
+        } else {
+            for (const fib_subch &e : fibs_[s].subchannels(nullptr, pcm_cb_ != nullptr && nmp_ > 0, dg_cb_ != nullptr && npk_ > 0,
+                                                           mot_cb_ != nullptr && nmot_ > 0,
+                                                           (label_cb_ || pad_dg_cb_ || pad_obj_cb_) && npad_ > 0))
+                now.push_back({e.startAddr, e.length, e.bitRate, e.protLevel, e.uepFlag, e.flags});
+        }
         auto same = [](const std::vector<dabgpu_subch> &x, const std::vector<dabgpu_subch> &y) {
             return x.size() == y.size() && (x.empty() || !std::memcmp(x.data(), y.data(), x.size() * sizeof(dabgpu_subch)));
         };
@@ -746,6 +791,35 @@ bool ensembleDecoder::step() {
         parsed_[s] = now;
     }
     return ok;
+}
+
+// the two spellings of the database record are one layout (fib_processor.h stands without dabgpu.h)
+static_assert(sizeof(fib_db) == sizeof(dabgpu_fic_db) && sizeof(fib_db::subch) == sizeof(dabgpu_fic_subch) &&
+                  sizeof(fib_db::component) == sizeof(dabgpu_fic_component) && sizeof(fib_db::service) == sizeof(dabgpu_fic_service) &&
+                  offsetof(fib_db, components) == offsetof(dabgpu_fic_db, components) &&
+                  offsetof(fib_db, services) == offsetof(dabgpu_fic_db, services) && offsetof(fib_db, EId) == offsetof(dabgpu_fic_db, EId) &&
+                  offsetof(fib_db, named) == offsetof(dabgpu_fic_db, named) && offsetof(fib_db, label) == offsetof(dabgpu_fic_db, label) &&
+                  offsetof(fib_db, table) == offsetof(dabgpu_fic_db, table) &&
+                  offsetof(fib_db::component, SCId) == offsetof(dabgpu_fic_component, SCId) &&
+                  offsetof(fib_db::component, packetAddress) == offsetof(dabgpu_fic_component, packetAddress) &&
+                  offsetof(fib_db::service, data_suffix) == offsetof(dabgpu_fic_service, data_suffix) &&
+                  offsetof(fib_db::service, label) == offsetof(dabgpu_fic_service, label) &&
+                  offsetof(fib_db::subch, inUse) == offsetof(dabgpu_fic_subch, inUse),
+              "fib_db (fib_processor.h) is dabgpu_fic_db (dabgpu.h)");
+
+fib_processor ensembleDecoder::database(int stream) const {
+    if (!cfg_.auto_layout || stream < 0 || stream >= cfg_.n_streams)
+        throw error(DABGPU_E_ARG, "ensembleDecoder::database: auto_layout and a stream of this decoder");
+    if (!cfg_.fic_on_gpu) {
+        fib_processor p = fibs_[stream];
+        p.on_event(nullptr);                   // (the copy signals nobody)
+        return p;
+    }
+    fib_db db;
+    chk(dabgpu_pipe_fic_db(pipe_, stream, reinterpret_cast<dabgpu_fic_db *>(&db)), "dabgpu_pipe_fic_db");
+    fib_processor p;
+    p.import_db(db);
+    return p;
 }
 
 dabgpu_stream_state ensembleDecoder::state(int stream) const {

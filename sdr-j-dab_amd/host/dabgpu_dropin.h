@@ -507,6 +507,11 @@ public:
         // previous step and differs from the applied one; one that exceeds the caps throws
         // dabgpu::error.
         bool auto_layout = false;
+        // With auto_layout: the FIBs are parsed on the GPU (dabgpu_pipe_fic, a database per stream
+        // on the device) instead of by the host's fib_processors.  step() then downloads the run
+        // records, tables and events, applies the same rule to the device's table, and moves the
+        // FIC to the host only while on_fib is set.
+        bool fic_on_gpu = false;
     };
     using fib_cb = std::function<void(int stream, int64_t frame, int ficno, const uint8_t *bits256, bool crc_ok)>;
     using msc_cb = std::function<void(int stream, int64_t cif, int subch, const uint8_t *bits, int nbits)>;
@@ -517,6 +522,18 @@ public:
     void on_fib(fib_cb f) { fib_cb_ = std::move(f); }
     void on_msc(msc_cb f) { msc_cb_ = std::move(f); }
     void on_superframe(sf_cb f) { sf_cb_ = std::move(f); }
+    // With auto_layout: the signals nameofEnsemble (FIG 1/0, once until clearEnsemble) and
+    // addtoEnsemble (FIG 1/1, once per service) of each stream's fib_processor, from the host's
+    // parse or, with fic_on_gpu, from the device's events: frame is the frame whose FIB carried
+    // the label, the text UTF-8 (fib_processor::label_text), 16 characters as transmitted.
+    using ensemble_name_cb = std::function<void(int stream, int64_t frame, uint32_t EId, const std::string &name)>;
+    using service_name_cb = std::function<void(int stream, int64_t frame, const std::string &label)>;
+    void on_ensemble_name(ensemble_name_cb f) { ens_name_cb_ = std::move(f); }
+    void on_service_name(service_name_cb f) { svc_name_cb_ = std::move(f); }
+    // With auto_layout: the stream's service database as a fib_processor -- the host's own, or
+    // with fic_on_gpu one loaded from the device's record (dabgpu_pipe_fic_db, import_db) -- to ask
+    // kindofService / dataforAudioService / dataforDataService / serviceLabels.
+    fib_processor database(int stream) const;
     // Decoded classic DAB audio, where audioSink::audioOut stands in the reference
     // (mp2processor.cpp:584-588): one call per MPEG layer II frame of an entry flagged
     // DABGPU_SUBCH_MP2 that mp2decodeFrame accepted (dabgpu_pipe_mp2), pcm = n_samples
@@ -618,6 +635,11 @@ private:
     std::vector<std::vector<dabgpu_subch>> tab_;      // [stream] the applied tables
     std::vector<fib_processor> fibs_;                 // auto_layout: [stream]
     std::vector<std::vector<dabgpu_subch>> parsed_;   // auto_layout: [stream] parsed at the end of the last step
+    devbuf fce_, fct_, fcr_;                          // fic_on_gpu: the FIC layer's events, tables, run records
+    std::vector<dabgpu_fic_table> fic_tab_;           // fic_on_gpu: [stream] the tables of this step
+    ensemble_name_cb ens_name_cb_;
+    service_name_cb svc_name_cb_;
+    int64_t fib_frame_ = 0;                           // the frame of the FIB the host's fib_processor is parsing
     std::vector<int64_t> frames_done_;     // frames delivered per stream
     fib_cb fib_cb_;
     msc_cb msc_cb_;

@@ -3,16 +3,10 @@
 #include "fib_processor.h"
 
 #include <cstdio>
+#include <cstring>
 
 namespace dabgpu {
 namespace {
-
-// MSB-first bit fields of a bit array, one bit per byte (dab-constants.h:182-308)
-uint32_t bits(const uint8_t *d, int off, int n) {
-    uint32_t r = 0;
-    for (int i = 0; i < n; i++) r = (r << 1) | (d[off + i] & 1u);
-    return r;
-}
 
 // Short-form sub-channel table (ETSI EN 300 401 table 8, fib-processor.cpp:30-94):
 // for table index 0..63 the sub-channel size in CUs, protection level and bit
@@ -81,8 +75,10 @@ void put_utf8(std::string &s, uint32_t u) {
     }
 }
 
+}  // namespace
+
 // toQStringUsingCharset (charsets.cpp:69-95) for the 16 label bytes
-std::string label_text(const uint8_t *b, int n, int charset) {
+std::string fib_processor::label_text(const uint8_t *b, int n, int charset) {
     std::string s;
     if (charset == 0x0F) {                          // UnicodeUtf8
         for (int i = 0; i < n && b[i]; i++) s += (char)b[i];
@@ -102,12 +98,23 @@ std::string label_text(const uint8_t *b, int n, int charset) {
     return s;
 }
 
-}  // namespace
-
 fib_processor::fib_processor() { clearEnsemble(); }
 
-// fib-processor.cpp:123-160
-void fib_processor::process_FIB(const uint8_t *p, uint16_t) {
+// MSB-first bit fields of a bit array, one bit per byte (dab-constants.h:182-308)
+uint32_t fib_processor::bits(const uint8_t *d, int off, int n) {
+    if (d + off + n > fib_end_) overrun_ = true;
+    uint32_t r = 0;
+    for (int i = 0; i < n; i++) r = (r << 1) | (d[off + i] & 1u);
+    return r;
+}
+
+// fib-processor.cpp:123-160, on a zero-extended copy (the overrun rule): the furthest read is a
+// FIG 0/2 at byte 29 with length 31 and 15 components, below bit 1024
+void fib_processor::process_FIB(const uint8_t *fib, uint16_t) {
+    uint8_t p[1280] = {};
+    memcpy(p, fib, 256);
+    fib_end_ = p + 256;
+    overrun_ = false;
     int processed = 0;
     const uint8_t *d = p;
     while (processed < 30) {
@@ -200,19 +207,26 @@ int fib_processor::fig0_2(const uint8_t *d, int used, int pd) {
         const int8_t tmid = (int8_t)bits(d, o, 2);
         // a new binding writes only these fields: the slot keeps whatever else its
         // previous component left (sub-channel, DSCTy, ... until a FIG 0/3)
+        // (the fields are read before the bind, as the reference's calls do: it matters to the
+        // overrun rule alone)
         if (tmid == 0) {                           // audio
+            const int16_t ascty = (int16_t)bits(d, o + 2, 6), subch = (int16_t)bits(d, o + 8, 6);
+            const int16_t ps = (int16_t)bits(d, o + 14, 1);
             const int k = bind(tmid, sid, (int16_t)i);
             if (k >= 0) {
-                components_[k].ASCTy = (int16_t)bits(d, o + 2, 6);
-                components_[k].subchannelId = (int16_t)bits(d, o + 8, 6);
-                components_[k].PS_flag = (int16_t)bits(d, o + 14, 1);
+                components_[k].ASCTy = ascty;
+                components_[k].subchannelId = subch;
+                components_[k].PS_flag = ps;
             }
         } else if (tmid == 3) {                    // packet data
+            const uint16_t scid = (uint16_t)bits(d, o + 2, 12);
+            const int16_t ps = (int16_t)bits(d, o + 14, 1);
+            const uint8_t ca = (uint8_t)bits(d, o + 15, 1);
             const int k = bind(tmid, sid, (int16_t)i);
             if (k >= 0) {
-                components_[k].SCId = (uint16_t)bits(d, o + 2, 12);
-                components_[k].PS_flag = (int16_t)bits(d, o + 14, 1);
-                components_[k].CAflag = (uint8_t)bits(d, o + 15, 1);
+                components_[k].SCId = scid;
+                components_[k].PS_flag = ps;
+                components_[k].CAflag = ca;
             }
         }
         o += 16;
@@ -288,7 +302,11 @@ void fib_processor::fig1(const uint8_t *d) {
                 const std::string name = label_text(raw, 16, charset);
                 if (firstTime_) {
                     ensemble_ = name;
+                    eid_ = eid;
+                    memcpy(ens_raw_, raw, 16);
+                    ens_charset_ = (uint8_t)charset;
                     if (ens_cb_) ens_cb_(eid, name);
+                    if (ev_cb_) ev_cb_(1, (int32_t)eid, raw, charset);
                 }
                 firstTime_ = false;
             }
@@ -299,11 +317,15 @@ void fib_processor::fig1(const uint8_t *d) {
         if (!s.hasName && charset <= 16) {
             read_label(ext == 1 ? 32 : 48);
             s.label += label_text(raw, 16, charset);
+            memcpy(s.raw, raw, 16);
+            s.charset = (uint8_t)charset;
+            s.data_suffix = ext == 5;
             if (ext == 5) {                          // addtoEnsemble only without MSC_DATA__ for 1/5
                 static const uint8_t suffix[8] = {' ', '(', 'd', 'a', 't', 'a', ')', 0};
                 s.label += label_text(suffix, 8, charset);
-            } else if (svc_cb_) {
-                svc_cb_(s.label);
+            } else {
+                if (svc_cb_) svc_cb_(s.label);
+                if (ev_cb_) ev_cb_(2, (int32_t)(&s - services_), raw, charset);
             }
             s.hasName = true;
         }
@@ -319,6 +341,9 @@ void fib_processor::fig2(const uint8_t *d) {
         uint8_t raw[16];
         for (int i = 0; i < 16; i++) raw[i] = (uint8_t)bits(d, 48 + 8 * i, 8);
         s.label += label_text(raw, 16, charset);
+        memcpy(s.raw, raw, 16);
+        s.charset = (uint8_t)charset;
+        s.data_suffix = false;
         s.hasName = true;
     }
 }
@@ -408,9 +433,112 @@ void fib_processor::clearEnsemble() {
         s.inUse = false;
         s.serviceId = -1;
         s.label.clear();
+        memset(s.raw, 0, 16);
+        s.charset = 0;
+        s.data_suffix = false;
     }
     ensemble_.clear();
+    eid_ = 0;
+    memset(ens_raw_, 0, 16);
+    ens_charset_ = 0;
     firstTime_ = true;
+}
+
+static const uint8_t kDataSuffix[8] = {' ', '(', 'd', 'a', 't', 'a', ')', 0};
+
+void fib_processor::export_db(fib_db *db) const {
+    const auto keep = db->table;
+    memset(db, 0, sizeof *db);
+    db->table = keep;
+    for (int i = 0; i < 64; i++) {
+        const subchannel &a = sub_[i];
+        fib_db::subch &x = db->sub[i];
+        x.SubChId = (int16_t)a.SubChId;
+        x.StartAddr = (int16_t)a.StartAddr;
+        x.Length = (int16_t)a.Length;
+        x.uepFlag = (int16_t)a.uepFlag;
+        x.protLevel = (int16_t)a.protLevel;
+        x.BitRate = (int16_t)a.BitRate;
+        x.FEC_scheme = a.FEC_scheme;
+        x.inUse = a.inUse;
+        const component &c = components_[i];
+        fib_db::component &y = db->components[i];
+        y.inUse = c.inUse;
+        y.TMid = c.TMid;
+        y.service = (int16_t)(c.service < 0 ? 0 : c.service);
+        y.componentNr = c.componentNr;
+        y.ASCTy = c.ASCTy;
+        y.PS_flag = c.PS_flag;
+        y.subchannelId = c.subchannelId;
+        y.SCId = c.SCId;
+        y.CAflag = c.CAflag;
+        y.DGflag = c.DGflag;
+        y.DSCTy = c.DSCTy;
+        y.packetAddress = c.packetAddress;
+        const service &s = services_[i];
+        fib_db::service &z = db->services[i];
+        z.serviceId = s.inUse ? s.serviceId : 0;
+        z.inUse = s.inUse;
+        z.hasName = s.hasName;
+        z.hasLanguage = s.hasLanguage;
+        z.charset = s.charset;
+        z.language = s.language;
+        z.programType = s.programType;
+        z.data_suffix = s.data_suffix;
+        memcpy(z.label, s.raw, 16);
+    }
+    db->EId = (int32_t)eid_;
+    db->charset = ens_charset_;
+    db->named = !firstTime_;
+    memcpy(db->label, ens_raw_, 16);
+}
+
+void fib_processor::import_db(const fib_db &db) {
+    for (int i = 0; i < 64; i++) {
+        const fib_db::subch &x = db.sub[i];
+        subchannel &a = sub_[i];
+        a = subchannel();
+        a.SubChId = x.SubChId;
+        a.StartAddr = x.StartAddr;
+        a.Length = x.Length;
+        a.uepFlag = x.uepFlag;
+        a.protLevel = x.protLevel;
+        a.BitRate = x.BitRate;
+        a.FEC_scheme = x.FEC_scheme;
+        a.inUse = x.inUse;
+        const fib_db::component &y = db.components[i];
+        component &c = components_[i];
+        c.inUse = y.inUse;
+        c.TMid = y.TMid;
+        c.service = y.service & 63;            // (an index: a record from anywhere stays inside the table)
+        c.componentNr = y.componentNr;
+        c.ASCTy = y.ASCTy;
+        c.PS_flag = y.PS_flag;
+        c.subchannelId = y.subchannelId & 63;
+        c.SCId = y.SCId;
+        c.CAflag = y.CAflag;
+        c.DGflag = y.DGflag;
+        c.DSCTy = y.DSCTy;
+        c.packetAddress = y.packetAddress;
+        const fib_db::service &z = db.services[i];
+        service &s = services_[i];
+        s.inUse = z.inUse;
+        s.serviceId = z.inUse ? z.serviceId : -1;
+        s.hasName = z.hasName;
+        s.hasLanguage = z.hasLanguage;
+        s.charset = z.charset;
+        s.language = z.language;
+        s.programType = z.programType;
+        s.data_suffix = z.data_suffix;
+        memcpy(s.raw, z.label, 16);
+        s.label = label_text(s.raw, 16, s.charset);
+        if (s.data_suffix) s.label += label_text(kDataSuffix, 8, s.charset);
+    }
+    eid_ = (uint32_t)db.EId;
+    ens_charset_ = db.charset;
+    firstTime_ = !db.named;
+    memcpy(ens_raw_, db.label, 16);
+    ensemble_ = db.named ? label_text(ens_raw_, 16, ens_charset_) : std::string();
 }
 
 // fib-processor.cpp:1197-1229

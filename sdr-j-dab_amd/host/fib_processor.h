@@ -2,11 +2,16 @@
 // drop-in ficHandler: fib_processor of sdr-j-dab
 // (includes/backend/fib-processor.h, src/backend/fib-processor.cpp), without Qt.
 //
-// Host code, scalar and tiny: a FIB is 30 bytes of FIGs once a frame, nothing to
-// put on a GPU.  It consumes the CRC-good FIBs the GPU FIC decoder delivers
-// (ficHandler / ensembleDecoder::on_fib) and answers the service lookups that
-// configure the MSC decoder (kindofService, dataforAudioService,
+// Host code, scalar and tiny: for one stream a FIB is 30 bytes of FIGs, twelve a frame.
+// For many ensembles at once the same parse runs on the GPU, one wave per database
+// (dabgpu_fib_parse, csrc/k_fib.hip), and this class is its definition and its host
+// end: export_db / import_db speak the library's dabgpu_fic_db record, so the lookups
+// below answer from a database the GPU built.  It consumes the CRC-good FIBs the GPU FIC
+// decoder delivers (ficHandler / ensembleDecoder::on_fib) and answers the service
+// lookups that configure the MSC decoder (kindofService, dataforAudioService,
 // dataforDataService).
+// The overrun rule (dabgpu.h, dabgpu_fib_parse): a read at or past bit 256 of a FIB reads
+// 0, control flow otherwise the reference's; process_FIB works on a zero-extended copy.
 //
 // Parsed as the reference does (same bit positions, same tables, same quirks):
 //   FIG 0/1  sub-channel organisation (short form via the UEP table, long form EEP
@@ -72,6 +77,42 @@ struct fib_subch {
     int16_t startAddr, length, bitRate, protLevel, uepFlag, flags;
 };
 
+// The database as a plain record: the fields and layout of dabgpu_fic_db (dabgpu.h; this
+// header stands without the GPU library's, the drop-in ties the two with a static_assert).
+// All zero is a new fib_processor; a free service entry has serviceId 0 and a component
+// never bound has service 0 (the class's -1 in both is never read).
+struct fib_db {
+    struct subch {
+        int16_t SubChId, StartAddr, Length, uepFlag, protLevel, BitRate, FEC_scheme;
+        uint8_t inUse, reserved;
+    } sub[64];
+    struct component {
+        uint8_t inUse;
+        int8_t TMid;
+        int16_t service, componentNr, ASCTy, PS_flag, subchannelId;
+        uint16_t SCId;
+        uint8_t CAflag;
+        int8_t DGflag;
+        int16_t DSCTy, packetAddress;
+    } components[64];
+    struct service {
+        int32_t serviceId;
+        uint8_t inUse, hasName, hasLanguage, charset;
+        int16_t language, programType;
+        uint8_t data_suffix, reserved[3];
+        uint8_t label[16];
+    } services[64];
+    int32_t EId;
+    uint8_t charset, named, reserved[2];
+    uint8_t label[16];
+    uint8_t reserved2[8];
+    struct {                                   // dabgpu_fic_table: the last dabgpu_fib_parse call's (export_db leaves it alone)
+        int32_t n, reserved[3];
+        fib_subch sub[64];
+        uint8_t ids[64];
+    } table;
+};
+
 class fib_processor {
 public:
     // stand-ins for the Qt signals nameofEnsemble / addtoEnsemble
@@ -80,6 +121,10 @@ public:
     fib_processor();
     void on_ensemble(ensemble_cb f) { ens_cb_ = std::move(f); }
     void on_service(service_cb f) { svc_cb_ = std::move(f); }
+    // both signals as a dabgpu_fic_event carries them: kind 1 nameofEnsemble (id: EId), kind 2
+    // addtoEnsemble (id: the service's slot), with the 16 label bytes as transmitted
+    using event_cb = std::function<void(int kind, int32_t id, const uint8_t *raw, int charset)>;
+    void on_event(event_cb f) { ev_cb_ = std::move(f); }
 
     // fib: 256 bits, one per byte (as ficHandler hands them over); fib number unused
     void process_FIB(const uint8_t *fib, uint16_t ficno);
@@ -109,6 +154,15 @@ public:
                                        bool packet_data = false, bool mot = false,
                                        bool pad = false) const;   // pad: DAB+ entries also get DABGPU_SUBCH_PAD (32)
 
+    // to and from the public record; import_db rebuilds the UTF-8 labels with label_text.
+    // export_db writes everything but db->table.
+    void export_db(fib_db *db) const;
+    void import_db(const fib_db &db);
+    // the last process_FIB met the overrun rule
+    bool overran() const { return overrun_; }
+    // toQStringUsingCharset (charsets.cpp:69-95) for n label bytes
+    static std::string label_text(const uint8_t *bytes, int n, int charset);
+
     std::string ensembleName() const { return ensemble_; }
     std::vector<std::string> serviceLabels() const;
 
@@ -116,6 +170,8 @@ private:
     struct service {
         int32_t serviceId = -1;
         std::string label;
+        uint8_t raw[16] = {}, charset = 0;     // the label as transmitted (export_db)
+        bool data_suffix = false;
         bool hasName = false, inUse = false, hasLanguage = false;
         int16_t language = 0, programType = 0;
     };
@@ -135,6 +191,7 @@ private:
         int16_t language = 0, FEC_scheme = 0;
         bool inUse = false;                    // a FIG 0/1 described it (subchannels())
     };
+    uint32_t bits(const uint8_t *d, int off, int n);   // with the overrun rule's bookkeeping
     void fig0(const uint8_t *d);
     void fig1(const uint8_t *d);
     int fig0_1(const uint8_t *d, int used);
@@ -153,9 +210,14 @@ private:
     component components_[64];
     subchannel sub_[64];
     std::string ensemble_;
+    uint32_t eid_ = 0;
+    uint8_t ens_raw_[16] = {}, ens_charset_ = 0;
     bool firstTime_ = true;
+    const uint8_t *fib_end_ = nullptr;         // one past bit 255 of the copy process_FIB walks
+    bool overrun_ = false;
     ensemble_cb ens_cb_;
     service_cb svc_cb_;
+    event_cb ev_cb_;
 };
 
 }  // namespace dabgpu
