@@ -1,5 +1,6 @@
-// dabgpu_internal.h -- what the two host translation units of the C ABI share:
-// dabgpu_ctx.cpp (errors, host tables, context, operators) and dabgpu_pipe.cpp (streaming pipeline).
+// dabgpu_internal.h -- what the host translation units of the C ABI share: dabgpu_ctx.cpp (errors,
+// host tables, context, operators) and the streaming pipeline's two, dabgpu_pipe.cpp and
+// dabgpu_layers.cpp (which share the pipeline's own state through dabgpu_pipe.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -34,6 +35,10 @@ struct DevBuf {                                          // device memory: n ele
         if (e == hipSuccess) n = count;
         else ptr = nullptr;
         return e;
+    }
+    hipError_t zalloc(size_t count) {                    // allocate, all bytes zero
+        const hipError_t e = alloc(count);
+        return e != hipSuccess ? e : hipMemset(ptr, 0, count * sizeof(T));
     }
     hipError_t put(const std::vector<T> &v) {            // allocate and upload
         const hipError_t e = alloc(v.size());

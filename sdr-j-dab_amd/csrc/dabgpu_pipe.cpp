@@ -1,237 +1,16 @@
 // dabgpu_pipe.cpp -- the C ABI (include/dabgpu.h), second half: the streaming pipeline that replaces
-// ofdmProcessor::run + ficHandler + mscHandler for many ensembles at once (its receiver logic: front_replay.h)
+// ofdmProcessor::run + ficHandler + mscHandler for many ensembles at once (its receiver logic:
+// front_replay.h; its state: dabgpu_pipe.h; the layers behind its outputs: dabgpu_layers.cpp)
 #include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <algorithm>
-#include "dabgpu_internal.h"
-#include "front_replay.h"
+#include "dabgpu_pipe.h"
 
 using namespace dab;
 using front::StreamSt;
 
-// Channel decoding (FIC/MSC Viterbi, DAB+) of run r runs on back-end stream back[r & 1], so
-// run r's back end overlaps run r+1's front end AND run r+1's back end (whose first waves
-// fill the SIMDs run r's last Viterbi waves leave idle).  The ring holds 2F+4 frames per
-// stream so run r+1's demod and MSC never touch a slot run r's MSC still reads; run r+2's
-// front end waits for run r's ACS.  The caller gives consecutive runs different output
-// buffers (or syncs).
-//
-// Destruction order, for every struct below: members go in reverse order of declaration, so
-// each struct declares its stream last and dabgpu_pipe declares `back` and `acq` after its
-// buffers -- a stream has drained and gone before the memory its kernels used is freed.
-struct BackSlot {
-    DevBuf<uint32_t> dec;            // Viterbi decisions: the MSC's, then the FIC's
-    Event ev_copy;                   // the descriptor block's upload done (before its staging is reused)
-    Event ev_back;                   // the run's back end done
-    Event ev_acs;                    // the run's ACS done (the ring's last reader)
-    Stream stream;
-};
-// Background null search (DABGPU_CTL_ACQ_ASYNC, the default since round 6): a stream that
-// loses sync after an acquisition is searched on its own low-priority stream while the
-// others keep decoding; its results are taken by the first dabgpu_pipe_run after they arrive
-struct AcqBg {
-    bool async = false;              // set true by dabgpu_pipe_create
-    bool inflight = false;           // results pending (the event alone says recorded, not taken)
-    Event ev;
-    DevBuf<AcqJob> jobs_d;           // [S], and its pinned staging
-    PinBuf<AcqJob> h_jobs;
-    DevBuf<AcqResult> res_d;         // [S]
-    PinBuf<AcqResult> h_res;
-    std::vector<int> who;
-    std::vector<char> acquiring;                     // [S]
-    Stream stream;
-};
-// DAB+ superframe layer (mp4Processor per DAB+ subchannel and stream)
-struct DabPlus {
-    int max_rs = 0;
-    // compact superframe output (dabgpu_pipe_set_dabplus_compact): the layer decodes into
-    // this sparse scratch and stores the run's superframes in CIF order for the caller
-    bool compact = false;
-    DevBuf<uint8_t> sf_sparse_d;
-    DevBuf<int32_t> sub_d;
-    DevBuf<int16_t> br_d;
-    DevBuf<int64_t> since_d;      // [S][NDP]
-    DevBuf<uint8_t> ring_d;       // [S][NDP][120*DP_MAX_RS]
-    DevBuf<DpState> state_d;      // [S][NDP]
-    DevBuf<uint8_t> code_d;       // [S][NDP][4F] superframe verdict per candidate CIF
-    Event ev;                     // the last superframe pass
-};
-// MPEG layer II layer (mp2Processor per classic-audio subchannel and stream): allocated only
-// for a pipeline with caps.max_mp2 > 0
-struct Mp2Layer {
-    int fstride = 0;              // bytes per frame slot: 2 * 24 * max_bitrate bits
-    DevBuf<int32_t> sub_d;
-    DevBuf<int16_t> br_d;
-    DevBuf<int64_t> since_d;      // [S][NMP]
-    DevBuf<Mp2SyncState> sync_d;  // [S][NMP] the synchronisers
-    DevBuf<uint8_t> part_d;       // [S][NMP][fstride] their frames in progress
-    DevBuf<int16_t> vstate_d[2];  // [S][NMP][MP2_STATE_I16] the decoders: a pass reads [cur], writes [cur ^ 1]
-    int cur = 0;
-    DevBuf<uint8_t> frames_d;     // [S * NMP][4F][fstride] the frames that completed in the run
-    DevBuf<uint8_t> present_d;    // [S * NMP][4F]
-    Event ev;                     // the last pass
-};
-// Packet-mode data layer (an mscDatagroup's assembler per packet-mode subchannel and stream):
-// allocated only while dabgpu_pipe_packet_caps' max_packet > 0
-struct PacketLayer {
-    int cap = 0, ncell = 0;       // max_group_bytes; cells per CIF the buffers hold (max_bitrate / 8)
-    DevBuf<int32_t> sub_d;
-    DevBuf<int16_t> br_d;
-    DevBuf<int64_t> since_d;      // [S][NPK]
-    DevBuf<PkState> state_d;      // [S][NPK] the assemblers
-    DevBuf<uint8_t> carry_d[2];   // [S][NPK][cap] their series in flight: a pass reads [cur], writes [cur ^ 1]
-    int cur = 0;
-    DevBuf<uint32_t> rec_d;       // [S * NPK][4F][ncell] packet records of the run
-    DevBuf<int2> take_d;          // [S * NPK][4F][ncell]
-    DevBuf<int32_t> segtab_d;     // [S * NPK][1 + 4F * ncell]
-    Event ev;                     // the last pass
-};
-
-// MOT layer (a motHandler per packet entry flagged DABGPU_SUBCH_MOT and stream): allocated
-// only while dabgpu_pipe_mot_caps' max_mot > 0
-struct MotLayer {
-    int body = 0, body_cap = 0;   // max_body_bytes, and rounded up to 16
-    size_t state_bytes = 0;       // dabgpu_mot_state_bytes(body)
-    int gslots = 0;               // DABGPU_PKT_GROUP_SLOTS(F, max_bitrate)
-    DevBuf<uint8_t> state_d;      // [S][NMOT][state_bytes] the motHandlers, updated in place
-    DevBuf<int32_t> src_d;        // [S][NMOT] the packet slot (s * NPK + j) each reads, -1: absent
-    DevBuf<int4> ops_d;           // [S * NMOT][2 * gslots] the pass's copy list
-    DevBuf<int32_t> nops_d;       // [S * NMOT]
-    Event ev;                     // the last pass
-};
-
-// PAD layer (a padHandler per DAB+ entry flagged DABGPU_SUBCH_PAD and stream): allocated only
-// while dabgpu_pipe_pad_caps' max_pad > 0
-struct PadLayer {
-    DevBuf<uint8_t> state_d;      // [S][NPAD] PadState, the padHandlers, updated in place
-    DevBuf<int32_t> src_d;        // [S][NPAD] the DAB+ slot (s * NDP + j) each reads, -1: absent
-    Event ev;                     // the last pass
-};
-
-// FIC layer (a fib_processor's database per stream): allocated only while dabgpu_pipe_fic_caps is on
-struct FicLayer {
-    DevBuf<uint8_t> db_d;         // [S] dabgpu_fic_db, updated in place
-    Event ev;                     // the last pass
-    bool on = false;
-};
-
-struct dabgpu_pipe {
-    dabgpu_ctx *c = nullptr;
-    int S = 0, F = 0, NSUB = 0, R = 0, NDP = 0, NMP = 0, NPK = 0, NMOT = 0, NPAD = 0;
-    int16_t threshold = 3;
-    int16_t method = 1;              // freqSyncMethod
-    bool scan = false;               // scanMode (No_Signal_Found after > 5 attempts)
-    // Subchannel tables, one per stream (dabgpu_pipe_set_subch): NSUB = caps.max_subch output
-    // rows and NDP = caps.max_dabplus DAB+ slots per stream, whatever the tables hold.
-    // since[s][k]: the stream's cif_count when entry k was set (it delivers from since + 16).
-    std::vector<std::vector<dabgpu_subch>> tab;
-    std::vector<std::vector<int64_t>> since;
-    int max_bitrate = 0, max_nbits = 0;
-    // uniform: every stream has the same full table (NSUB entries, since 0) -- the kernels
-    // take the shared-table path (VitJob::ent_prof null); else the per-(stream, entry)
-    // descriptor tables below and the list of active pairs (rebuild_tables)
-    bool uniform = true;
-    int n_act = 0;
-    DevBuf<int32_t> ent_prof_d, ent_start_d, act_d;
-    DevBuf<int64_t> ent_since_d;
-    std::vector<uint8_t> entry_valid;   // [S][4F][NSUB] of the last run (dabgpu_pipe_msc_entry_valid)
-    std::vector<StreamSt> st;
-    DevBuf<uint8_t> ring;            // [S][R][75][3072] RING8 bytes (soft bit + 127, dab_kernels.h)
-    DevBuf<Profile> prof_d;          // [NSUB]
-    DevBuf<Profile> ficprof_d;
-    DevBuf<uint8_t> inv_d;           // the subchannel profiles' inverse depuncturing tables
-    DevBuf<int32_t> substart_d;      // [NSUB]
-    DevBuf<dabgpu_frame> frames_d;
-    DevBuf<int32_t> si_d;
-    DevBuf<int16_t> corr_d, snr_d;
-    DevBuf<float> fc_d, fcpart_d;    // [S*F] float2, [S*F][kMaxChunks] float2
-    // the back end's per-run descriptors, one block per back-end stream (parity), uploaded
-    // with ONE copy per run (each runtime copy is a kernel of its own on the back-end
-    // stream, ~6 us, in front of the ACS): [S] int64 CIF index of each stream's first CIF
-    // slot | [S] int32 CIFs each stream delivered | [S * F] int32 FIC ring slots;
-    // h_desc: their pinned staging, BackSlot::ev_copy marks the upload done before reuse
-    DevBuf<uint8_t> desc_d;
-    PinBuf<uint8_t> h_desc;
-    size_t desc_sz = 0;
-    int64_t *cif0_dev(int par) const { return (int64_t *)(desc_d + par * desc_sz); }
-    int32_t *ncif_dev(int par) const { return (int32_t *)(desc_d + par * desc_sz + 8 * (size_t)S); }
-    int32_t *slots_dev(int par) const { return (int32_t *)(desc_d + par * desc_sz + 12 * (size_t)S); }
-    int64_t *h_cif0(int par) const { return (int64_t *)(h_desc + par * desc_sz); }
-    int32_t *h_ncif(int par) const { return (int32_t *)(h_desc + par * desc_sz + 8 * (size_t)S); }
-    int32_t *h_slots(int par) const { return (int32_t *)(h_desc + par * desc_sz + 12 * (size_t)S); }
-    int cur = 0;                     // back-end stream of the last run
-    int64_t run_idx = 0;
-    int64_t dec_fic_off = 0;         // FIC decisions: words after the MSC's
-    // pinned host staging of the front end's per-pass copies (frame descriptors in,
-    // startIndex / FreqCorr out): DMA without the pageable bounce, each pass syncs
-    // before the buffers are touched again
-    PinBuf<dabgpu_frame> h_frames;
-    PinBuf<int32_t> h_si;
-    PinBuf<float2> h_fc;
-    PinBuf<int16_t> h_snr;
-    // the back-end streams' own error words (the front end's is the context's): the
-    // Viterbi jobs of run r set berr_d[r & 1], which the back end publishes into
-    // h_berr[r & 1] (and clears) as its last step; read once back[r & 1].ev_back completed
-    DevBuf<int32_t> berr_d;
-    PinBuf<int32_t> h_berr;
-    // speculative back end (dabgpu_pipe_run): queued behind the first front pass
-    bool speculate = true;                      // env DABGPU_NO_SPECULATE=1: off (A/B)
-    Event ev_front;
-    bool ev_front_demod = false;     // ev_front marks this pass's demod (the speculative back end's gate)
-    std::vector<dabgpu_frame> last_frames;   // [S][F]
-    std::vector<dabgpu_frame_info> last_info;   // [S][F] observables of the last run
-    DabPlus dp;
-    Mp2Layer mp2;
-    PacketLayer pk;
-    MotLayer mot;
-    // the outputs of the run's dabgpu_pipe_packet call, which dabgpu_pipe_mot reads
-    const uint8_t *pk_bytes = nullptr;
-    const dabgpu_datagroup *pk_groups = nullptr;
-    const dabgpu_packet_run *pk_run = nullptr;
-    bool mot_pending = false;        // ... have not entered the MOT layer yet
-    PadLayer pad;
-    // the outputs of the run's dabgpu_pipe_dabplus call, which dabgpu_pipe_pad reads
-    const uint8_t *dp_sf = nullptr;
-    const dabgpu_superframe *dp_info = nullptr;
-    int32_t dp_sf_stride = 0;
-    bool dp_sf_compact = false;
-    bool pad_pending = false;        // ... have not entered the PAD layer yet
-    FicLayer fic;
-    // the FIC outputs of the last run, which dabgpu_pipe_fic reads
-    const uint8_t *last_fic = nullptr, *last_crc = nullptr;
-    bool last_fic_packed = false;
-    bool fic_pending = false;        // ... have not entered the FIC layer yet
-    const uint8_t *last_msc = nullptr; // MSC bits of the last run
-    bool dp_pending = false, mp2_pending = false, pk_pending = false;   // the last run's CIFs have not entered the layer yet
-    int32_t last_msc_stride = 0;
-    bool last_msc_packed = false;
-    // the iqBuffer feed (dabgpu_pipe_set_display): symbol 2's display carriers per ring slot
-    DevBuf<float2> disp_d;           // [S][R][K]
-    bool display = false;
-    int disp_token = 2;              // the display feed's symbol (ofdm-decoder.cpp:61 displayToken)
-    bool packed = false;             // MSC output 8 bits per byte (dabgpu_pipe_set_packed)
-    bool fic_packed = false;         // FIC output as FIB bytes (DABGPU_PACK_FIC)
-    int iq_fmt = DABGPU_IQ_F32;      // sample format of the streams (dabgpu_pipe_set_iq_format)
-    // fault injection (DABGPU_CTL_INJECT_BOUNDS): the next run's MSC job gets a subchannel
-    // table whose first entry points past the ring, which the Viterbi loader refuses
-    bool inject_bounds = false;
-    DevBuf<int32_t> substart_bad_d;
-    // optional per-stage kernel timing (HIP events on the stage's stream)
-    int profiling = 0;                          // 1: last run, 2: every run since enabled, 3: 2 + stages alone
-    std::vector<Event> ev_pool;
-    std::vector<std::pair<int, int>> ev_rec;   // (stage, index of start event; end = +1)
-    // the streams (of the back ends and the background null search) after every buffer above
-    BackSlot back[2];
-    AcqBg acq;
-    ~dabgpu_pipe() {                 // the front end's stream is the context's: wait for it here
-        if (c) (void)c->stream.sync();
-        for (BackSlot &b : back) (void)b.stream.sync();
-        (void)acq.stream.sync();     // a background null search still running
-    }
-};
-
-static hipError_t prof_mark(dabgpu_pipe *p, int stage, bool start) {
+hipError_t dab::prof_mark(dabgpu_pipe *p, int stage, bool start) {
     if (!p->profiling) return hipSuccess;
     hipStream_t st = (stage >= DABGPU_STAGE_FIC) ? p->back[p->cur].stream : p->c->stream;
     if (p->profiling == 3) {                    // the stage alone on the device
@@ -276,16 +55,27 @@ static int back_errors(dabgpu_pipe *p, bool wait) {
     return 0;
 }
 
-// wait for everything the pipeline has enqueued on its front-end and back-end streams
-static int sync_streams(dabgpu_pipe *p) {
-    HIPCHK(p->c->stream.sync());
-    for (BackSlot &b : p->back) HIPCHK(b.stream.sync());
+// DABGPU_CTL_INJECT_BOUNDS: the table the next run's MSC job reads its start offsets from
+int dab::inject_table(dabgpu_pipe *p) {
+    if (!p->substart_bad_d) {                       // (rebuild_tables drops it with the tables)
+        // the start offsets in use (shared, or per entry) with the first decoded entry's
+        // far past any ring (no int32 overflow in the loader)
+        std::vector<int32_t> bad;
+        if (p->uniform) {
+            for (int i = 0; i < p->NSUB; i++) bad.push_back(p->tab[0][i].startAddr * 64);
+            bad[0] = 0x40000000;
+        } else {
+            bad.assign((size_t)p->S * p->NSUB, 0);
+            bool first = true;
+            for (int s = 0; s < p->S; s++)
+                for (int k = 0; k < (int)p->tab[s].size(); k++) {
+                    bad[(size_t)s * p->NSUB + k] = first ? 0x40000000 : p->tab[s][k].startAddr * 64;
+                    first = false;
+                }
+        }
+        HIPCHK(p->substart_bad_d.put(bad));
+    }
     return 0;
-}
-
-// the streams a control call names: [first, end) -- one stream, or every stream for -1
-static std::pair<int, int> stream_range(const dabgpu_pipe *p, int stream) {
-    return stream < 0 ? std::make_pair(0, p->S) : std::make_pair(stream, stream + 1);
 }
 
 extern "C" {
@@ -305,349 +95,15 @@ static int acq_async_setup(dabgpu_pipe *p) {
     return 0;
 }
 
-// A subchannel table against the reference's definitions and the pipeline's caps
-// (dabgpu_pipe_create_caps and dabgpu_pipe_set_subch validate alike)
-static int check_table(const dabgpu_subch *sub, int n, int max_subch, int max_bitrate, int max_dabplus, int max_mp2,
-                       int max_packet, int max_mot, int max_pad) {
-    if (n < 0 || (n > 0 && !sub)) return fail(DABGPU_E_ARG, "bad subchannel table");
-    if (n > max_subch) return fail(DABGPU_E_ARG, "%d subchannels, the pipeline holds %d per stream", n, max_subch);
-    int ndp = 0, nmp = 0, npk = 0, nmot = 0, npad = 0;
-    for (int i = 0; i < n; i++) {
-        Profile P;
-        if (sub[i].flags & DABGPU_SUBCH_PAD) {
-            if (!(sub[i].flags & DABGPU_SUBCH_DABPLUS)) return fail(DABGPU_E_ARG, "subchannel %d is flagged PAD and not DAB+", i);
-            npad++;
-        }
-        if (sub[i].flags & DABGPU_SUBCH_MOT) {
-            if (!(sub[i].flags & DABGPU_SUBCH_PACKET))
-                return fail(DABGPU_E_ARG, "subchannel %d is flagged MOT and not packet mode", i);
-            nmot++;
-        }
-        if (make_profile(sub[i], P)) return fail(DABGPU_E_UNSUP, "subchannel %d protection undefined", i);
-        if (sub[i].startAddr < 0 || sub[i].startAddr + sub[i].length > 864 || P.frag > sub[i].length * 64)
-            return fail(DABGPU_E_ARG, "subchannel %d does not fit its CUs", i);
-        // packets are multiples of 24 bytes: a CIF of 3 * bitRate bytes holds bitRate / 8 cells
-        if ((sub[i].flags & DABGPU_SUBCH_PACKET) && (sub[i].bitRate < 8 || sub[i].bitRate % 8 || sub[i].bitRate > max_bitrate))
-            return fail(DABGPU_E_UNSUP, "packet-mode subchannel %d: bitRate %d is not a multiple of 8 in [8, %d]", i,
-                        sub[i].bitRate, max_bitrate);
-        if (sub[i].bitRate > max_bitrate)
-            return fail(DABGPU_E_ARG, "subchannel %d: bitRate %d above the pipeline's %d", i, sub[i].bitRate, max_bitrate);
-        if ((sub[i].flags & DABGPU_SUBCH_MP2) && (sub[i].flags & DABGPU_SUBCH_DABPLUS))
-            return fail(DABGPU_E_ARG, "subchannel %d is flagged both DAB+ and layer II", i);
-        if (sub[i].flags & DABGPU_SUBCH_MP2) nmp++;
-        if (sub[i].flags & DABGPU_SUBCH_PACKET) {
-            if (sub[i].flags & (DABGPU_SUBCH_MP2 | DABGPU_SUBCH_DABPLUS))
-                return fail(DABGPU_E_ARG, "subchannel %d is flagged packet mode and an audio layer", i);
-            npk++;
-        }
-        if (!(sub[i].flags & DABGPU_SUBCH_DABPLUS)) continue;
-        // DAB+ subchannels (mp4Processor: RSDims = bitRate / 8, mp4processor.cpp:83-84)
-        const int br = sub[i].bitRate;
-        if (br < 8 || br % 8 || br / 8 > DP_MAX_RS)
-            return fail(DABGPU_E_UNSUP, "DAB+ subchannel %d: bitRate %d is not a multiple of 8 in [8, 384]", i, br);
-        ndp++;
-    }
-    if (ndp > max_dabplus) return fail(DABGPU_E_ARG, "%d DAB+ subchannels, the pipeline holds %d per stream", ndp, max_dabplus);
-    if (nmp > max_mp2) return fail(DABGPU_E_ARG, "%d layer II subchannels, the pipeline holds %d per stream", nmp, max_mp2);
-    if (npk > max_packet)
-        return fail(DABGPU_E_ARG, "%d packet-mode subchannels, the pipeline holds %d per stream", npk, max_packet);
-    if (nmot > max_mot) return fail(DABGPU_E_ARG, "%d MOT subchannels, the pipeline holds %d per stream", nmot, max_mot);
-    if (npad > max_pad) return fail(DABGPU_E_ARG, "%d PAD subchannels, the pipeline holds %d per stream", npad, max_pad);
-    return 0;
-}
-
-static bool same_subch(const dabgpu_subch &a, const dabgpu_subch &b) {
-    return a.startAddr == b.startAddr && a.length == b.length && a.bitRate == b.bitRate && a.protLevel == b.protLevel &&
-           a.uepFlag == b.uepFlag && a.flags == b.flags;
-}
-
-// (Re)size the packet-mode layer to npk slots per stream and groups of cap bytes.  The
-// assemblers of the slots both sizes hold go on (their carried bytes cut or padded to cap),
-// every other slot is a new mscDatagroup.  The caller has waited for the streams.  The new
-// layer is built beside the old one and takes its place only when everything succeeded: on
-// an error the pipeline keeps the layer, and the assemblers, it had.
-static int packet_size(dabgpu_pipe *p, int npk, int cap) {
-    const PacketLayer &old = p->pk;
-    const int S = p->S, old_n = p->NPK, old_cap = old.cap;
-    std::vector<PkState> ost;
-    std::vector<uint8_t> oca;
-    if (old_n) {
-        ost.resize((size_t)S * old_n);
-        oca.resize((size_t)S * old_n * old_cap);
-        HIPCHK(hipMemcpy(ost.data(), old.state_d, sizeof(PkState) * ost.size(), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(oca.data(), old.carry_d[old.cur], oca.size(), hipMemcpyDeviceToHost));
-    }
-    PacketLayer k;
-    if (!npk) {
-        p->pk = std::move(k);
-        p->NPK = 0;
-        return 0;
-    }
-    k.cap = cap;
-    k.ncell = std::max(1, p->max_bitrate / 8);
-    const size_t ne = (size_t)S * npk, cells = (size_t)4 * p->F * k.ncell;
-    HIPCHK(k.ev.create(hipEventDisableTiming));
-    HIPCHK(k.sub_d.alloc(ne));
-    HIPCHK(k.br_d.alloc(ne));
-    HIPCHK(k.since_d.alloc(ne));
-    HIPCHK(k.state_d.alloc(ne));
-    HIPCHK(k.rec_d.alloc(ne * cells));
-    HIPCHK(k.take_d.alloc(ne * cells));
-    HIPCHK(k.segtab_d.alloc(ne * (1 + cells)));
-    for (auto &c : k.carry_d) HIPCHK(c.alloc(ne * cap));
-    std::vector<PkState> st(ne, PkState{0, -1, 0, 0, 0, 0, 0, 0});
-    std::vector<uint8_t> ca(ne * cap, 0);
-    for (int s = 0; s < S; s++)
-        for (int j = 0; j < std::min(old_n, npk); j++) {
-            st[(size_t)s * npk + j] = ost[(size_t)s * old_n + j];
-            memcpy(ca.data() + ((size_t)s * npk + j) * cap, oca.data() + ((size_t)s * old_n + j) * old_cap, std::min(cap, old_cap));
-        }
-    HIPCHK(hipMemcpy(k.state_d, st.data(), sizeof(PkState) * ne, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(k.carry_d[0], ca.data(), ca.size(), hipMemcpyHostToDevice));
-    p->pk = std::move(k);
-    p->NPK = npk;
-    return 0;
-}
-
-// (Re)size the MOT layer to nmot slots per stream and bodies of at most body bytes, as
-// packet_size does: the motHandlers of the slots both sizes hold go on (an entry whose body no
-// longer fits is flagged DABGPU_MOT_TOO_LARGE), every other slot is a new one; the new layer
-// takes the old one's place only when everything succeeded.
-static int mot_size(dabgpu_pipe *p, int nmot, int body) {
-    const MotLayer &old = p->mot;
-    const int S = p->S, old_n = p->NMOT;
-    std::vector<uint8_t> ost;
-    if (old_n) {
-        ost.resize((size_t)S * old_n * old.state_bytes);
-        HIPCHK(hipMemcpy(ost.data(), old.state_d, ost.size(), hipMemcpyDeviceToHost));
-    }
-    MotLayer m;
-    if (!nmot) {
-        p->mot = std::move(m);
-        p->NMOT = 0;
-        return 0;
-    }
-    m.body = body;
-    m.body_cap = (body + 15) / 16 * 16;
-    m.state_bytes = dabgpu_mot_state_bytes(body);
-    m.gslots = DABGPU_PKT_GROUP_SLOTS(p->F, p->max_bitrate);
-    const size_t ne = (size_t)S * nmot;
-    HIPCHK(m.ev.create(hipEventDisableTiming));
-    HIPCHK(m.state_d.alloc(ne * m.state_bytes));
-    HIPCHK(m.src_d.alloc(ne));
-    HIPCHK(m.ops_d.alloc(std::max<size_t>(1, ne * 2 * m.gslots)));
-    HIPCHK(m.nops_d.alloc(ne));
-    std::vector<uint8_t> st(ne * m.state_bytes, 0);
-    for (int s = 0; s < S; s++)
-        for (int j = 0; j < std::min(old_n, nmot); j++) {
-            const uint8_t *o = ost.data() + ((size_t)s * old_n + j) * old.state_bytes;
-            uint8_t *n = st.data() + ((size_t)s * nmot + j) * m.state_bytes;
-            memcpy(n, o, MOT_TABLE_BYTES);
-            auto *e = (dabgpu_mot_entry *)(n + sizeof(dabgpu_mot_head));
-            for (int k = 0; k < DABGPU_MOT_ENTRIES; k++) {
-                if (!e[k].order || (e[k].flags & DABGPU_MOT_TOO_LARGE)) continue;
-                if (e[k].bodySize > body) {
-                    e[k].flags |= DABGPU_MOT_TOO_LARGE;
-                    continue;
-                }
-                memcpy(n + MOT_TABLE_BYTES + (size_t)k * m.body_cap, o + MOT_TABLE_BYTES + (size_t)k * old.body_cap,
-                       (size_t)std::max(0, e[k].bodySize));
-            }
-        }
-    HIPCHK(hipMemcpy(m.state_d, st.data(), st.size(), hipMemcpyHostToDevice));
-    p->mot = std::move(m);
-    p->NMOT = nmot;
-    return 0;
-}
-
-// (Re)size the PAD layer to npad slots per stream, as mot_size does: the padHandlers of the
-// slots both sizes hold go on, every other slot is a new one.
-static int pad_size(dabgpu_pipe *p, int npad) {
-    const PadLayer &old = p->pad;
-    const int S = p->S, old_n = p->NPAD;
-    std::vector<uint8_t> ost;
-    if (old_n) {
-        ost.resize((size_t)S * old_n * sizeof(PadState));
-        HIPCHK(hipMemcpy(ost.data(), old.state_d, ost.size(), hipMemcpyDeviceToHost));
-    }
-    PadLayer m;
-    if (!npad) {
-        p->pad = std::move(m);
-        p->NPAD = 0;
-        return 0;
-    }
-    const size_t ne = (size_t)S * npad;
-    HIPCHK(m.ev.create(hipEventDisableTiming));
-    HIPCHK(m.state_d.alloc(ne * sizeof(PadState)));
-    HIPCHK(m.src_d.alloc(ne));
-    std::vector<uint8_t> st(ne * sizeof(PadState), 0);
-    for (int s = 0; s < S; s++)
-        for (int j = 0; j < std::min(old_n, npad); j++)
-            memcpy(st.data() + ((size_t)s * npad + j) * sizeof(PadState), ost.data() + ((size_t)s * old_n + j) * sizeof(PadState),
-                   sizeof(PadState));
-    HIPCHK(hipMemcpy(m.state_d, st.data(), st.size(), hipMemcpyHostToDevice));
-    p->pad = std::move(m);
-    p->NPAD = npad;
-    return 0;
-}
-
-// The device's descriptor tables from p->tab / p->since.  The caller has waited for the
-// pipeline's streams (in-flight kernels read the old tables): the tables are replaced.
-static int rebuild_tables(dabgpu_pipe *p) {
-    const int S = p->S, NS = p->NSUB;
-    p->uniform = true;
-    for (int s = 0; s < S && p->uniform; s++) {
-        if ((int)p->tab[s].size() != NS) p->uniform = false;
-        for (int k = 0; k < (int)p->tab[s].size() && p->uniform; k++)
-            if (p->since[s][k] != 0 || !same_subch(p->tab[s][k], p->tab[0][k])) p->uniform = false;
-    }
-    std::vector<Profile> profs;
-    std::vector<uint8_t> inv;
-    std::vector<int32_t> ss(std::max(1, NS), 0);
-    std::vector<int32_t> eprof(std::max<size_t>(1, (size_t)S * NS), -1), estart(eprof.size(), 0), act;
-    std::vector<int64_t> esince(eprof.size(), 0);
-    auto add_profile = [&](const dabgpu_subch &sc, bool dedup) {
-        Profile P;
-        (void)make_profile(sc, P);                      // validated by check_table
-        if (dedup)
-            for (size_t i = 0; i < profs.size(); i++) {
-                Profile Q = profs[i];
-                Q.inv_off = 0;
-                if (!memcmp(&Q, &P, sizeof P)) return (int32_t)i;
-            }
-        profs.push_back(P);
-        profs.back().inv_off = (int32_t)inv.size();
-        const std::vector<uint8_t> v = make_inv(P);
-        inv.insert(inv.end(), v.begin(), v.end());
-        return (int32_t)profs.size() - 1;
-    };
-    if (p->uniform) {                                   // profile k = entry k, as the kernels index it
-        for (int k = 0; k < NS; k++) {
-            add_profile(p->tab[0][k], false);
-            ss[k] = p->tab[0][k].startAddr * 64;
-        }
-        p->n_act = S * NS;
-    } else {
-        // distinct profiles (and their inverse tables) once, whatever streams use them
-        for (int s = 0; s < S; s++)
-            for (int k = 0; k < (int)p->tab[s].size(); k++) {
-                const size_t e = (size_t)s * NS + k;
-                eprof[e] = add_profile(p->tab[s][k], true);
-                estart[e] = p->tab[s][k].startAddr * 64;
-                esince[e] = p->since[s][k];
-                act.push_back((int32_t)e);
-            }
-        p->n_act = (int)act.size();
-    }
-    if (profs.empty()) profs.push_back(Profile());
-    if (inv.empty()) inv.push_back(0);
-    if (act.empty()) act.push_back(0);
-    // DAB+ slots: slot j of a stream is its j-th entry flagged DABGPU_SUBCH_DABPLUS
-    const size_t nd = std::max<size_t>(1, (size_t)S * p->NDP);
-    std::vector<int32_t> dps(nd, -1);
-    std::vector<int16_t> dpb(nd, 0);
-    std::vector<int64_t> dpc(nd, 0);
-    p->dp.max_rs = 0;
-    for (int s = 0; s < S; s++) {
-        int j = 0;
-        for (int k = 0; k < (int)p->tab[s].size(); k++) {
-            if (!(p->tab[s][k].flags & DABGPU_SUBCH_DABPLUS)) continue;
-            const size_t i = (size_t)s * p->NDP + j++;
-            dps[i] = k;
-            dpb[i] = p->tab[s][k].bitRate;
-            dpc[i] = p->since[s][k];
-            p->dp.max_rs = std::max(p->dp.max_rs, p->tab[s][k].bitRate / 8);
-        }
-    }
-    // put() replaces a table; the per-entry tables of a non-uniform set and the injected
-    // table go (an empty buffer is assigned) and are built again when needed
-    HIPCHK(p->prof_d.put(profs));
-    HIPCHK(p->inv_d.put(inv));
-    HIPCHK(p->substart_d.put(ss));
-    p->ent_prof_d = {};
-    p->ent_start_d = {};
-    p->ent_since_d = {};
-    p->act_d = {};
-    p->substart_bad_d = {};
-    if (!p->uniform) {
-        HIPCHK(p->ent_prof_d.put(eprof));
-        HIPCHK(p->ent_start_d.put(estart));
-        HIPCHK(p->ent_since_d.put(esince));
-        HIPCHK(p->act_d.put(act));
-    }
-    if (p->NMP) {                 // layer II slots: slot j of a stream is its j-th entry flagged DABGPU_SUBCH_MP2
-        const size_t nm = (size_t)S * p->NMP;
-        std::vector<int32_t> ms(nm, -1);
-        std::vector<int16_t> mb(nm, 0);
-        std::vector<int64_t> mc(nm, 0);
-        for (int s = 0; s < S; s++)
-            for (int k = 0, j = 0; k < (int)p->tab[s].size(); k++) {
-                if (!(p->tab[s][k].flags & DABGPU_SUBCH_MP2)) continue;
-                const size_t i = (size_t)s * p->NMP + j++;
-                ms[i] = k;
-                mb[i] = p->tab[s][k].bitRate;
-                mc[i] = p->since[s][k];
-            }
-        HIPCHK(hipMemcpy(p->mp2.sub_d, ms.data(), sizeof(int32_t) * nm, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(p->mp2.br_d, mb.data(), sizeof(int16_t) * nm, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(p->mp2.since_d, mc.data(), sizeof(int64_t) * nm, hipMemcpyHostToDevice));
-    }
-    if (p->NPK) {                 // packet slots: slot j of a stream is its j-th entry flagged DABGPU_SUBCH_PACKET
-        const size_t nk = (size_t)S * p->NPK;
-        std::vector<int32_t> ks(nk, -1);
-        std::vector<int16_t> kb(nk, 0);
-        std::vector<int64_t> kc(nk, 0);
-        for (int s = 0; s < S; s++)
-            for (int k = 0, j = 0; k < (int)p->tab[s].size(); k++) {
-                if (!(p->tab[s][k].flags & DABGPU_SUBCH_PACKET)) continue;
-                const size_t i = (size_t)s * p->NPK + j++;
-                ks[i] = k;
-                kb[i] = p->tab[s][k].bitRate;
-                kc[i] = p->since[s][k];
-            }
-        HIPCHK(hipMemcpy(p->pk.sub_d, ks.data(), sizeof(int32_t) * nk, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(p->pk.br_d, kb.data(), sizeof(int16_t) * nk, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(p->pk.since_d, kc.data(), sizeof(int64_t) * nk, hipMemcpyHostToDevice));
-    }
-    if (p->NMOT) {                // MOT slots: slot m of a stream is its m-th entry flagged DABGPU_SUBCH_MOT
-        std::vector<int32_t> src((size_t)S * p->NMOT, -1);
-        for (int s = 0; s < S; s++)
-            for (int k = 0, j = 0, m = 0; k < (int)p->tab[s].size(); k++) {
-                if (!(p->tab[s][k].flags & DABGPU_SUBCH_PACKET)) continue;
-                if (p->tab[s][k].flags & DABGPU_SUBCH_MOT) src[(size_t)s * p->NMOT + m++] = s * p->NPK + j;
-                j++;
-            }
-        HIPCHK(hipMemcpy(p->mot.src_d, src.data(), sizeof(int32_t) * src.size(), hipMemcpyHostToDevice));
-    }
-    if (p->NPAD) {                // PAD slots: slot m of a stream is its m-th entry flagged DABGPU_SUBCH_PAD
-        std::vector<int32_t> src((size_t)S * p->NPAD, -1);
-        for (int s = 0; s < S; s++)
-            for (int k = 0, j = 0, m = 0; k < (int)p->tab[s].size(); k++) {
-                if (!(p->tab[s][k].flags & DABGPU_SUBCH_DABPLUS)) continue;
-                if (p->tab[s][k].flags & DABGPU_SUBCH_PAD) src[(size_t)s * p->NPAD + m++] = s * p->NDP + j;
-                j++;
-            }
-        HIPCHK(hipMemcpy(p->pad.src_d, src.data(), sizeof(int32_t) * src.size(), hipMemcpyHostToDevice));
-    }
-    if (p->NDP) {
-        HIPCHK(hipMemcpy(p->dp.sub_d, dps.data(), sizeof(int32_t) * nd, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(p->dp.br_d, dpb.data(), sizeof(int16_t) * nd, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(p->dp.since_d, dpc.data(), sizeof(int64_t) * nd, hipMemcpyHostToDevice));
-    }
-    return 0;
-}
-
 int dabgpu_pipe_create(dabgpu_ctx *c, const dabgpu_pipe_cfg *cfg, dabgpu_pipe **out) {
     if (!c || !cfg || !out) return fail(DABGPU_E_ARG, "null arg");
     *out = nullptr;
     if (cfg->n_subch < 0 || (cfg->n_subch > 0 && !cfg->subch)) return fail(DABGPU_E_ARG, "bad sizes");
     // the caps of the table itself
     dabgpu_pipe_caps caps = {cfg->n_subch, 0, 0, 0};
-    for (int i = 0; i < cfg->n_subch; i++) {
-        caps.max_bitrate = std::max<int32_t>(caps.max_bitrate, cfg->subch[i].bitRate);
-        if (cfg->subch[i].flags & DABGPU_SUBCH_DABPLUS) caps.max_dabplus++;
-        if (cfg->subch[i].flags & DABGPU_SUBCH_MP2) caps.max_mp2++;
-    }
+    for (int i = 0; i < cfg->n_subch; i++) caps.max_bitrate = std::max<int32_t>(caps.max_bitrate, cfg->subch[i].bitRate);
+    caps.max_dabplus = slots::count_flag(cfg->subch, cfg->n_subch, DABGPU_SUBCH_DABPLUS);
+    caps.max_mp2 = slots::count_flag(cfg->subch, cfg->n_subch, DABGPU_SUBCH_MP2);
     return dabgpu_pipe_create_caps(c, cfg, &caps, out);
 }
 
@@ -660,15 +116,12 @@ int dabgpu_pipe_create_caps(dabgpu_ctx *c, const dabgpu_pipe_cfg *cfg, const dab
         return fail(DABGPU_E_ARG, "bad caps (at most 64 subchannels of at most 384 kbit/s)");
     if (cfg->freq_sync_method < 0 || cfg->freq_sync_method > 2)
         return fail(DABGPU_E_UNSUP, "freqSyncMethod %d (0, 1 or 2: ofdm-decoder.cpp:103-161)", cfg->freq_sync_method);
-    int npk = 0, nmot = 0, npad = 0;   // the packet-mode, MOT and PAD layers start with what the table flags (dabgpu_pipe_packet_caps)
-    for (int i = 0; i < cfg->n_subch; i++) {
-        if (cfg->subch[i].flags & DABGPU_SUBCH_PACKET) npk++;
-        if (cfg->subch[i].flags & DABGPU_SUBCH_MOT) nmot++;
-        if (cfg->subch[i].flags & DABGPU_SUBCH_PAD) npad++;
-    }
-    if (int rc = check_table(cfg->subch, cfg->n_subch, caps->max_subch, caps->max_bitrate, caps->max_dabplus, caps->max_mp2, npk,
-                             nmot, npad))
-        return rc;
+    // the packet-mode, MOT and PAD layers start with what the table flags (dabgpu_pipe_packet_caps)
+    const int npk = slots::count_flag(cfg->subch, cfg->n_subch, DABGPU_SUBCH_PACKET);
+    const int nmot = slots::count_flag(cfg->subch, cfg->n_subch, DABGPU_SUBCH_MOT);
+    const int npad = slots::count_flag(cfg->subch, cfg->n_subch, DABGPU_SUBCH_PAD);
+    const TableLimits lim{caps->max_subch, caps->max_bitrate, {caps->max_dabplus, caps->max_mp2, npk, nmot, npad}};
+    if (int rc = check_table(cfg->subch, cfg->n_subch, lim)) return rc;
     auto p = std::make_unique<dabgpu_pipe>();
     p->c = c;
     p->S = cfg->n_streams;
@@ -722,33 +175,22 @@ int dabgpu_pipe_create_caps(dabgpu_ctx *c, const dabgpu_pipe_cfg *cfg, const dab
     HIPCHK(p->ev_front.create(hipEventDisableTiming));
     if (p->NDP) {
         const size_t nd = (size_t)p->S * p->NDP;
-        HIPCHK(p->dp.sub_d.alloc(nd));
-        HIPCHK(p->dp.br_d.alloc(nd));
-        HIPCHK(p->dp.since_d.alloc(nd));
-        HIPCHK(p->dp.ring_d.alloc(nd * 120 * DP_MAX_RS));
-        HIPCHK(p->dp.state_d.alloc(nd));
+        HIPCHK(p->dp.map.alloc(nd));
+        HIPCHK(p->dp.ring_d.zalloc(nd * 120 * DP_MAX_RS));
+        HIPCHK(p->dp.state_d.zalloc(nd));
         HIPCHK(p->dp.code_d.alloc(nd * 4 * p->F));
-        HIPCHK(hipMemset(p->dp.ring_d, 0, nd * 120 * DP_MAX_RS));
-        HIPCHK(hipMemset(p->dp.state_d, 0, sizeof(DpState) * nd));
     }
     if (p->NMP) {
         Mp2Layer &m = p->mp2;
         const size_t nm = (size_t)p->S * p->NMP;
         m.fstride = 6 * std::max(p->max_bitrate, 1);
         HIPCHK(m.ev.create(hipEventDisableTiming));
-        HIPCHK(m.sub_d.alloc(nm));
-        HIPCHK(m.br_d.alloc(nm));
-        HIPCHK(m.since_d.alloc(nm));
-        HIPCHK(m.sync_d.alloc(nm));
-        HIPCHK(m.part_d.alloc(nm * m.fstride));
+        HIPCHK(m.map.alloc(nm));
+        HIPCHK(m.sync_d.zalloc(nm));
+        HIPCHK(m.part_d.zalloc(nm * m.fstride));
         HIPCHK(m.frames_d.alloc(nm * 4 * p->F * m.fstride));
         HIPCHK(m.present_d.alloc(nm * 4 * p->F));
-        HIPCHK(hipMemset(m.sync_d, 0, sizeof(Mp2SyncState) * nm));
-        HIPCHK(hipMemset(m.part_d, 0, nm * m.fstride));
-        for (auto &v : m.vstate_d) {
-            HIPCHK(v.alloc(nm * MP2_STATE_I16));
-            HIPCHK(hipMemset(v, 0, sizeof(int16_t) * nm * MP2_STATE_I16));
-        }
+        for (auto &v : m.vstate_d) HIPCHK(v.zalloc(nm * MP2_STATE_I16));
     }
     if (npk)
         if (int rc = packet_size(p.get(), npk, DABGPU_PKT_GROUP_BYTES)) return rc;
@@ -1170,8 +612,8 @@ int dabgpu_pipe_run(dabgpu_pipe *p, const void *iq, int64_t stride, const int64_
     if (int rc = acq_collect(p, false)) return rc;        // a background null search that finished
     p->last_frames.assign((size_t)S * F, dabgpu_frame());
     p->last_info.assign((size_t)S * F, dabgpu_frame_info());
-    p->last_msc = nullptr;
-    p->fic_pending = false;
+    p->feed.last_msc = nullptr;                // (a run that fails leaves no rows and no FIBs to consume)
+    p->feed.fic_pending = false;
     if (p->profiling == 1) p->ev_rec.clear();   // modes 2, 3 accumulate over runs
     p->ev_front_demod = false;
     // at most one run of overlap: run r-2's ACS, the last reader of the ring slots this
@@ -1229,16 +671,14 @@ int dabgpu_pipe_run(dabgpu_pipe *p, const void *iq, int64_t stride, const int64_
     if (int rc = finish_back(p, par)) return bail(p, par, sp, rc);
     p->run_idx++;
     p->inject_bounds = false;
-    p->last_msc = have_rows ? msc_bits : nullptr;
-    p->dp_pending = p->mp2_pending = p->pk_pending = have_rows;
-    p->mot_pending = false;                    // until this run's dabgpu_pipe_packet
-    p->pad_pending = false;                    // until this run's dabgpu_pipe_dabplus
-    p->last_fic = fic_bits;
-    p->last_crc = fic_crc;
-    p->last_fic_packed = p->fic_packed;
-    p->fic_pending = fic_bits && fic_crc;
-    p->last_msc_stride = msc_stride;
-    p->last_msc_packed = p->packed;
+    LayerFeed &f = p->feed;
+    f.last_msc = have_rows ? msc_bits : nullptr;
+    f.last_msc_stride = msc_stride;
+    f.last_msc_packed = p->packed;
+    f.last_fic = fic_bits;
+    f.last_crc = fic_crc;
+    f.last_fic_packed = p->fic_packed;
+    f.new_run(have_rows, fic_bits && fic_crc);
     publish_validity(p, done, have_rows, msc_valid);
     for (int s = 0; s < S; s++) cur[s].cif_count = p->st[s].cif_count + 4 * (int64_t)done[s];
     p->st = cur;
@@ -1281,359 +721,6 @@ int dabgpu_pipe_sync(dabgpu_pipe *p) {
     return kernel_errors(p->c);
 }
 
-int dabgpu_pipe_dabplus(dabgpu_pipe *p, uint8_t *sf_bytes, int32_t sf_stride, dabgpu_superframe *info) {
-    if (!p || !sf_bytes || !info) return fail(DABGPU_E_ARG, "null arg");
-    if (p->NDP == 0) return fail(DABGPU_E_STATE, "no DAB+ subchannel in this pipeline");
-    if (!p->last_msc || !p->dp_pending) return fail(DABGPU_E_STATE, "no dabgpu_pipe_run with MSC output to consume");
-    if (sf_stride < 110 * p->dp.max_rs) return fail(DABGPU_E_ARG, "sf_stride %d < %d", sf_stride, 110 * p->dp.max_rs);
-    dabgpu_ctx *c = p->c;
-    DpJob J;
-    memset(&J, 0, sizeof J);
-    J.msc = p->last_msc;
-    J.msc_stride = p->last_msc_stride;
-    J.packed = p->last_msc_packed ? 1 : 0;
-    J.ncif = 4 * p->F;
-    J.nsub = p->NSUB;
-    J.ndp = p->NDP;
-    J.nstreams = p->S;
-    J.cif0s = p->cif0_dev(p->cur);
-    J.ncifs = p->ncif_dev(p->cur);
-    J.dp_sub = p->dp.sub_d;
-    J.dp_br = p->dp.br_d;
-    J.dp_since = p->dp.since_d;
-    J.ring = p->dp.ring_d;
-    J.state = p->dp.state_d;
-    J.code = p->dp.code_d;
-    J.sf_out = sf_bytes;
-    J.sf_stride = sf_stride;
-    if (p->dp.compact) {
-        if (p->F > 512) return fail(DABGPU_E_UNSUP, "compact DAB+ output: at most 512 frames per run");
-        const size_t need = (size_t)p->S * 4 * p->F * p->NDP * (size_t)sf_stride;
-        if (need > p->dp.sf_sparse_d.n) {
-            // the layers that wrote the old scratch ran on this pipeline's back-end streams:
-            // wait for those (not the whole device: other pipelines, the null search)
-            for (BackSlot &b : p->back) HIPCHK(b.stream.sync());
-            p->dp.sf_sparse_d.reset();
-            HIPCHK(p->dp.sf_sparse_d.alloc(need));
-        }
-        J.sf_out = p->dp.sf_sparse_d;
-        J.sf_compact = sf_bytes;
-        J.kmax = DABGPU_SF_SLOTS(p->F);
-    }
-    J.info = info;
-    J.tabs = c->dptab;
-    // on the last run's back-end stream (after its MSC), after the previous
-    // superframe pass (the 5-CIF rings carry state from run to run)
-    hipStream_t bs = p->back[p->cur].stream;
-    HIPCHK(p->dp.ev.wait_on(bs));
-    HIPCHK(prof_mark(p, DABGPU_STAGE_DABPLUS, true));
-    HIPCHK(launch_dabplus(bs, J));
-    HIPCHK(prof_mark(p, DABGPU_STAGE_DABPLUS, false));
-    HIPCHK(p->dp.ev.record(bs));
-    // (the run after next does not wait for this: the layer reads this run's MSC output
-    // and CIF counters, which that run's back end overwrites behind it on this stream)
-    p->dp_pending = false;                     // each run's CIFs enter the superframe layer once
-    p->dp_sf = sf_bytes;
-    p->dp_info = info;
-    p->dp_sf_stride = sf_stride;
-    p->dp_sf_compact = p->dp.compact;
-    p->pad_pending = p->NPAD > 0;
-    return 0;
-}
-
-int dabgpu_pipe_pad(dabgpu_pipe *p, const uint8_t *sf_bytes, int32_t sf_stride, const dabgpu_superframe *info,
-                    dabgpu_pad_label *labels, dabgpu_datagroup *groups, uint8_t *bytes, dabgpu_pad_run *run) {
-    if (!p || !sf_bytes || !info || !labels || !groups || !bytes || !run) return fail(DABGPU_E_ARG, "null arg");
-    if (p->NPAD == 0) return fail(DABGPU_E_STATE, "no PAD subchannel in this pipeline");
-    if (!p->pad_pending) return fail(DABGPU_E_STATE, "no dabgpu_pipe_dabplus call of this run to consume");
-    if (sf_bytes != p->dp_sf || info != p->dp_info || sf_stride != p->dp_sf_stride)
-        return fail(DABGPU_E_ARG, "sf_bytes_d, sf_stride and info_d are not those of this run's dabgpu_pipe_dabplus call");
-    PadLayer &m = p->pad;
-    PadJob J;
-    memset(&J, 0, sizeof J);
-    J.n_slots = p->S * p->NPAD;
-    J.state = m.state_d;
-    J.info = info;
-    J.sf = sf_bytes;
-    J.sf_stride = sf_stride;
-    J.kmax = p->dp_sf_compact ? DABGPU_SF_SLOTS(p->F) : 0;
-    J.ncif = 4 * p->F;
-    J.ndp = p->NDP;
-    J.src = m.src_d;
-    J.labels = labels;
-    J.label_slots = DABGPU_PAD_LABEL_SLOTS(p->F);
-    J.groups = groups;
-    J.group_slots = DABGPU_PAD_GROUP_SLOTS(p->F);
-    J.bytes = bytes;
-    J.arena = DABGPU_PAD_ARENA_BYTES((int64_t)p->F);
-    J.run = run;
-    // on the run's back-end stream, behind its DAB+ layer; after the previous pass (the
-    // padHandlers are updated in place)
-    hipStream_t bs = p->back[p->cur].stream;
-    HIPCHK(m.ev.wait_on(bs));
-    HIPCHK(launch_pad(bs, J));
-    HIPCHK(m.ev.record(bs));
-    p->pad_pending = false;                    // each run's AUs enter the layer once
-    return 0;
-}
-
-int dabgpu_pipe_pad_caps(dabgpu_pipe *p, int max_pad) {
-    if (!p || max_pad < 0 || max_pad > p->NDP) return fail(DABGPU_E_ARG, "bad args (max_pad <= max_dabplus)");
-    if (max_pad && DABGPU_PAD_ARENA_BYTES((int64_t)p->F) > 0x7FFFFFFF) return fail(DABGPU_E_ARG, "an arena of 2 GiB and more");
-    for (int s = 0; s < p->S; s++) {
-        int n = 0;
-        for (const dabgpu_subch &e : p->tab[s])
-            if (e.flags & DABGPU_SUBCH_PAD) n++;
-        if (n > max_pad) return fail(DABGPU_E_ARG, "stream %d's table has %d PAD subchannels", s, n);
-    }
-    if (int rc = sync_streams(p)) return rc;
-    if (int rc = pad_size(p, max_pad)) return rc;
-    p->pad_pending = false;
-    return rebuild_tables(p);
-}
-
-int dabgpu_pipe_fic_caps(dabgpu_pipe *p, int on) {
-    if (!p) return fail(DABGPU_E_ARG, "null pipe");
-    if (int rc = sync_streams(p)) return rc;
-    p->fic_pending = false;
-    if (!on) {
-        p->fic = FicLayer();
-        return 0;
-    }
-    if (p->fic.on) return 0;                   // the databases stay
-    const size_t nb = (size_t)p->S * sizeof(dabgpu_fic_db);
-    HIPCHK(p->fic.db_d.alloc(nb));
-    HIPCHK(p->fic.ev.create(hipEventDisableTiming));
-    HIPCHK(hipMemset(p->fic.db_d, 0, nb));
-    p->fic.on = true;
-    return 0;
-}
-
-int dabgpu_pipe_fic(dabgpu_pipe *p, const uint8_t *fic_bits, const uint8_t *fic_crc, int want_flags, dabgpu_fic_event *events,
-                    dabgpu_fic_table *table, dabgpu_fic_run *run) {
-    if (!p || !fic_bits || !fic_crc || !events || !table || !run) return fail(DABGPU_E_ARG, "null arg");
-    if (!p->fic.on) return fail(DABGPU_E_STATE, "no FIC layer in this pipeline (dabgpu_pipe_fic_caps)");
-    if (!p->fic_pending) return fail(DABGPU_E_STATE, "no dabgpu_pipe_run with FIC output to consume");
-    if (fic_bits != p->last_fic || fic_crc != p->last_crc)
-        return fail(DABGPU_E_ARG, "fic_bits_d and fic_crc_d are not those of the last dabgpu_pipe_run");
-    FibJob J;
-    memset(&J, 0, sizeof J);
-    J.n_slots = p->S;
-    J.n_fibs = 12 * p->F;
-    J.db = (dabgpu_fic_db *)(uint8_t *)p->fic.db_d;
-    J.fibs = fic_bits;
-    J.bit_src = p->last_fic_packed ? 0 : 1;
-    J.stride = (int64_t)J.n_fibs * (J.bit_src ? 256 : 32);
-    J.ok = fic_crc;
-    J.want = want_flags & (DABGPU_SUBCH_MP2 | DABGPU_SUBCH_PACKET | DABGPU_SUBCH_MOT | DABGPU_SUBCH_PAD);
-    J.events = events;
-    J.event_slots = DABGPU_FIC_EVENT_SLOTS;
-    J.table = table;
-    J.run = run;
-    // on the run's back-end stream, behind its FIC decode; after the previous pass (the
-    // databases are updated in place)
-    hipStream_t bs = p->back[p->cur].stream;
-    HIPCHK(p->fic.ev.wait_on(bs));
-    HIPCHK(launch_fib(bs, J));
-    HIPCHK(p->fic.ev.record(bs));
-    p->fic_pending = false;                    // each run's FIBs enter the layer once
-    return 0;
-}
-
-int dabgpu_pipe_fic_db(dabgpu_pipe *p, int stream, dabgpu_fic_db *db_h) {
-    if (!p || !db_h || stream < 0 || stream >= p->S) return fail(DABGPU_E_ARG, "bad args");
-    if (!p->fic.on) return fail(DABGPU_E_STATE, "no FIC layer in this pipeline (dabgpu_pipe_fic_caps)");
-    if (int rc = sync_streams(p)) return rc;
-    HIPCHK(hipMemcpy(db_h, p->fic.db_d + (size_t)stream * sizeof(dabgpu_fic_db), sizeof(dabgpu_fic_db), hipMemcpyDeviceToHost));
-    return 0;
-}
-
-int dabgpu_pipe_fic_clear(dabgpu_pipe *p, int stream) {
-    if (!p || stream < -1 || stream >= p->S) return fail(DABGPU_E_ARG, "bad args");
-    if (!p->fic.on) return fail(DABGPU_E_STATE, "no FIC layer in this pipeline (dabgpu_pipe_fic_caps)");
-    if (int rc = sync_streams(p)) return rc;
-    dabgpu_fic_db *db = (dabgpu_fic_db *)(uint8_t *)p->fic.db_d;
-    HIPCHK(launch_fic_clear(p->c->stream, stream < 0 ? db : db + stream, stream < 0 ? p->S : 1));
-    HIPCHK(hipStreamSynchronize(p->c->stream));
-    return 0;
-}
-
-int dabgpu_pipe_mp2(dabgpu_pipe *p, int16_t *pcm, dabgpu_mp2_info *info) {
-    if (!p || !pcm || !info) return fail(DABGPU_E_ARG, "null arg");
-    if (p->NMP == 0) return fail(DABGPU_E_STATE, "no layer II subchannel in this pipeline");
-    if (!p->last_msc || !p->mp2_pending) return fail(DABGPU_E_STATE, "no dabgpu_pipe_run with MSC output to consume");
-    Mp2Layer &m = p->mp2;
-    Mp2SyncJob Y;
-    memset(&Y, 0, sizeof Y);
-    Y.msc = p->last_msc;
-    Y.msc_stride = p->last_msc_stride;
-    Y.packed = p->last_msc_packed ? 1 : 0;
-    Y.ncif = 4 * p->F;
-    Y.nsub = p->NSUB;
-    Y.nmp = p->NMP;
-    Y.nstreams = p->S;
-    Y.cif0s = p->cif0_dev(p->cur);
-    Y.ncifs = p->ncif_dev(p->cur);
-    Y.mp_sub = m.sub_d;
-    Y.mp_br = m.br_d;
-    Y.mp_since = m.since_d;
-    Y.state = m.sync_d;
-    Y.part = m.part_d;
-    Y.frames = m.frames_d;
-    Y.fstride = m.fstride;
-    Y.present = m.present_d;
-    Y.info = info;
-    Mp2Job J;
-    memset(&J, 0, sizeof J);
-    J.frames = m.frames_d;
-    J.stride = m.fstride;
-    J.n_chains = p->S * p->NMP;
-    J.chain_len = 4 * p->F;
-    J.present = m.present_d;
-    J.state_in = m.vstate_d[m.cur];
-    J.state_out = m.vstate_d[m.cur ^ 1];
-    J.pcm = pcm;
-    J.info = info;
-    J.cdiv = p->NMP;
-    J.idx_a = (int64_t)4 * p->F * p->NMP;
-    J.idx_b = 1;
-    J.idx_c = p->NMP;
-    if (int rc = mp2_tables(p->c, &J.tabs)) return rc;
-    // on the last run's back-end stream (after its MSC), after the previous pass (the
-    // synchronisers, the decoders and the frame slots carry over or are reused)
-    hipStream_t bs = p->back[p->cur].stream;
-    HIPCHK(m.ev.wait_on(bs));
-    HIPCHK(launch_mp2_sync(bs, Y));
-    HIPCHK(launch_mp2_decode(bs, J));
-    HIPCHK(m.ev.record(bs));
-    m.cur ^= 1;
-    p->mp2_pending = false;                    // each run's CIFs enter the layer once
-    return 0;
-}
-
-int dabgpu_pipe_packet(dabgpu_pipe *p, uint8_t *bytes, dabgpu_datagroup *groups, dabgpu_packet_run *run,
-                       dabgpu_packet_info *info) {
-    if (!p || !bytes || !groups || !run || !info) return fail(DABGPU_E_ARG, "null arg");
-    if (p->NPK == 0) return fail(DABGPU_E_STATE, "no packet-mode subchannel in this pipeline");
-    if (!p->last_msc || !p->pk_pending) return fail(DABGPU_E_STATE, "no dabgpu_pipe_run with MSC output to consume");
-    PacketLayer &k = p->pk;
-    PkJob J;
-    memset(&J, 0, sizeof J);
-    J.msc = p->last_msc;
-    J.msc_stride = p->last_msc_stride;
-    J.packed = p->last_msc_packed ? 1 : 0;
-    J.ncif = 4 * p->F;
-    J.nsub = p->NSUB;
-    J.npk = p->NPK;
-    J.nstreams = p->S;
-    J.ncell = k.ncell;
-    J.cap = k.cap;
-    J.cif0s = p->cif0_dev(p->cur);
-    J.ncifs = p->ncif_dev(p->cur);
-    J.pk_sub = k.sub_d;
-    J.pk_br = k.br_d;
-    J.pk_since = k.since_d;
-    J.state = k.state_d;
-    J.carry_in = k.carry_d[k.cur];
-    J.carry_out = k.carry_d[k.cur ^ 1];
-    J.rec = k.rec_d;
-    J.take = k.take_d;
-    J.segtab = k.segtab_d;
-    J.bytes = bytes;
-    J.arena = DABGPU_PKT_ARENA_BYTES((int64_t)p->F, p->max_bitrate, k.cap);
-    J.groups = groups;
-    J.gslots = DABGPU_PKT_GROUP_SLOTS(p->F, p->max_bitrate);
-    J.run = run;
-    J.info = info;
-    // on the last run's back-end stream (after its MSC), after the previous pass (the
-    // assemblers and the work buffers carry over or are reused)
-    hipStream_t bs = p->back[p->cur].stream;
-    HIPCHK(k.ev.wait_on(bs));
-    HIPCHK(launch_packet(bs, J));
-    HIPCHK(k.ev.record(bs));
-    k.cur ^= 1;
-    p->pk_pending = false;                     // each run's CIFs enter the layer once
-    p->pk_bytes = bytes;
-    p->pk_groups = groups;
-    p->pk_run = run;
-    p->mot_pending = p->NMOT > 0;
-    return 0;
-}
-
-int dabgpu_pipe_mot(dabgpu_pipe *p, uint8_t *bytes, dabgpu_mot_object *objects, dabgpu_mot_run *run) {
-    if (!p || !bytes || !objects || !run) return fail(DABGPU_E_ARG, "null arg");
-    if (p->NMOT == 0) return fail(DABGPU_E_STATE, "no MOT subchannel in this pipeline");
-    if (!p->mot_pending) return fail(DABGPU_E_STATE, "no dabgpu_pipe_packet call of this run to consume");
-    if ((uintptr_t)bytes & 15) return fail(DABGPU_E_ARG, "bytes_d must be 16-byte aligned");
-    MotLayer &m = p->mot;
-    MotJob J;
-    memset(&J, 0, sizeof J);
-    J.n_slots = p->S * p->NMOT;
-    J.max_body = m.body;
-    J.body_cap = m.body_cap;
-    J.state_bytes = (int64_t)m.state_bytes;
-    J.state = m.state_d;
-    J.src = m.src_d;
-    J.groups = p->pk_groups;
-    J.gslots = m.gslots;
-    J.bytes = p->pk_bytes;
-    J.arena = DABGPU_PKT_ARENA_BYTES((int64_t)p->F, p->max_bitrate, p->pk.cap);
-    J.run = p->pk_run;
-    J.objects = objects;
-    J.out = bytes;
-    J.out_arena = DABGPU_MOT_ARENA_BYTES((int64_t)p->F, p->max_bitrate, m.body);
-    J.mot_run = run;
-    J.ops = m.ops_d;
-    J.nops = m.nops_d;
-    // on the run's back-end stream, behind its packet layer; after the previous pass (the
-    // motHandlers are updated in place, the copy list is reused)
-    hipStream_t bs = p->back[p->cur].stream;
-    HIPCHK(m.ev.wait_on(bs));
-    HIPCHK(launch_mot(bs, J));
-    HIPCHK(m.ev.record(bs));
-    p->mot_pending = false;                    // each run's groups enter the layer once
-    return 0;
-}
-
-int dabgpu_pipe_mot_caps(dabgpu_pipe *p, int max_mot, int max_body_bytes) {
-    if (!p || max_mot < 0 || max_body_bytes < 0 || max_body_bytes > (1 << 24) || max_mot > p->NPK)
-        return fail(DABGPU_E_ARG, "bad args (max_mot <= max_packet, max_body_bytes <= 1 << 24)");
-    const int body = max_body_bytes ? max_body_bytes : DABGPU_MOT_BODY_BYTES;
-    if (max_mot && (DABGPU_PKT_ARENA_BYTES((int64_t)p->F, p->max_bitrate, p->pk.cap) > 0x7FFFFFFF ||
-                    DABGPU_MOT_ARENA_BYTES((int64_t)p->F, p->max_bitrate, body) > 0x7FFFFFFF))
-        return fail(DABGPU_E_ARG, "arenas of 2 GiB and more");
-    for (int s = 0; s < p->S; s++) {
-        int n = 0;
-        for (const dabgpu_subch &e : p->tab[s])
-            if (e.flags & DABGPU_SUBCH_MOT) n++;
-        if (n > max_mot) return fail(DABGPU_E_ARG, "stream %d's table has %d MOT subchannels", s, n);
-    }
-    if (int rc = sync_streams(p)) return rc;
-    if (int rc = mot_size(p, max_mot, body)) return rc;
-    p->mot_pending = false;
-    return rebuild_tables(p);
-}
-
-int dabgpu_pipe_packet_caps(dabgpu_pipe *p, int max_packet, int max_group_bytes) {
-    if (!p || max_packet < 0 || max_group_bytes < 0 || max_packet > p->NSUB) return fail(DABGPU_E_ARG, "bad args");
-    if (max_packet < p->NMOT) return fail(DABGPU_E_ARG, "the MOT layer holds %d slots (dabgpu_pipe_mot_caps first)", p->NMOT);
-    if (max_packet && p->max_bitrate < 8) return fail(DABGPU_E_ARG, "max_bitrate %d holds no packet-mode entry", p->max_bitrate);
-    const int cap = max_group_bytes ? max_group_bytes : DABGPU_PKT_GROUP_BYTES;
-    // the MOT layer indexes the packet arena in int32 (as dabgpu_pipe_mot_caps checks)
-    if (p->NMOT && DABGPU_PKT_ARENA_BYTES((int64_t)p->F, p->max_bitrate, (int64_t)cap) > 0x7FFFFFFF)
-        return fail(DABGPU_E_ARG, "a packet arena of 2 GiB and more under the MOT layer");
-    for (int s = 0; s < p->S; s++) {
-        int n = 0;
-        for (const dabgpu_subch &e : p->tab[s])
-            if (e.flags & DABGPU_SUBCH_PACKET) n++;
-        if (n > max_packet) return fail(DABGPU_E_ARG, "stream %d's table has %d packet-mode subchannels", s, n);
-    }
-    if (int rc = sync_streams(p)) return rc;
-    if (int rc = packet_size(p, max_packet, cap)) return rc;
-    p->mot_pending = false;
-    return rebuild_tables(p);
-}
-
 int dabgpu_pipe_state(dabgpu_pipe *p, int s, dabgpu_stream_state *o) {
     if (!p || !o || s < 0 || s >= p->S) return fail(DABGPU_E_ARG, "bad args");
     // a background null search that has finished is taken now (not at the next run), so
@@ -1663,29 +750,6 @@ int dabgpu_pipe_frame_info(dabgpu_pipe *p, dabgpu_frame_info *info) {
     if (!p || !info) return fail(DABGPU_E_ARG, "bad args");
     if (p->last_info.empty()) memset(info, 0, sizeof(dabgpu_frame_info) * (size_t)p->S * p->F);
     else memcpy(info, p->last_info.data(), sizeof(dabgpu_frame_info) * p->last_info.size());
-    return 0;
-}
-
-// DABGPU_CTL_INJECT_BOUNDS: the table the next run's MSC job reads its start offsets from
-static int inject_table(dabgpu_pipe *p) {
-    if (!p->substart_bad_d) {                       // (rebuild_tables drops it with the tables)
-        // the start offsets in use (shared, or per entry) with the first decoded entry's
-        // far past any ring (no int32 overflow in the loader)
-        std::vector<int32_t> bad;
-        if (p->uniform) {
-            for (int i = 0; i < p->NSUB; i++) bad.push_back(p->tab[0][i].startAddr * 64);
-            bad[0] = 0x40000000;
-        } else {
-            bad.assign((size_t)p->S * p->NSUB, 0);
-            bool first = true;
-            for (int s = 0; s < p->S; s++)
-                for (int k = 0; k < (int)p->tab[s].size(); k++) {
-                    bad[(size_t)s * p->NSUB + k] = first ? 0x40000000 : p->tab[s][k].startAddr * 64;
-                    first = false;
-                }
-        }
-        HIPCHK(p->substart_bad_d.put(bad));
-    }
     return 0;
 }
 
@@ -1739,153 +803,6 @@ int dabgpu_pipe_frame_slot(dabgpu_pipe *p, int frame, int32_t *slot) {
     *slot = p->last_frames.empty() ? -1 : p->last_frames[frame].out_slot;
     return 0;
 }
-int dabgpu_pipe_set_subch(dabgpu_pipe *p, int stream, const dabgpu_subch *sub, int32_t n) {
-    if (!p || stream < -1 || stream >= p->S) return fail(DABGPU_E_ARG, "bad args");
-    if (int rc = check_table(sub, n, p->NSUB, p->max_bitrate, p->NDP, p->NMP, p->NPK, p->NMOT, p->NPAD)) return rc;   // the table stays on error
-    // in-flight kernels read the device tables: a rare control call, so it waits for
-    // everything the pipeline has enqueued (as dabgpu_pipe_set_profiling) instead of
-    // double-buffering them
-    if (int rc = sync_streams(p)) return rc;
-    const size_t RB = 120 * DP_MAX_RS;
-    for (auto [s, end] = stream_range(p, stream); s < end; s++) {
-        const std::vector<dabgpu_subch> old = p->tab[s];
-        const std::vector<int64_t> old_since = p->since[s];
-        std::vector<int> old_slot(old.size(), -1);      // DAB+ slot of each old entry
-        for (int k = 0, j = 0; k < (int)old.size(); k++)
-            if (old[k].flags & DABGPU_SUBCH_DABPLUS) old_slot[k] = j++;
-        // an entry whose index and fields are unchanged goes on (since_cif, DAB+ ring and
-        // state kept, wherever its slot now lies); every other one starts like a new
-        // dabConcurrent / mp4Processor at the stream's current CIF
-        std::vector<uint8_t> rings, nrings;
-        std::vector<DpState> sts, nsts;
-        if (p->NDP) {
-            rings.resize(p->NDP * RB);
-            sts.resize(p->NDP);
-            HIPCHK(hipMemcpy(rings.data(), p->dp.ring_d + (size_t)s * p->NDP * RB, rings.size(), hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(sts.data(), p->dp.state_d + (size_t)s * p->NDP, sizeof(DpState) * p->NDP, hipMemcpyDeviceToHost));
-            nrings.assign(rings.size(), 0);
-            nsts.assign(p->NDP, DpState{0, 0});
-        }
-        // the layer II slots likewise: synchroniser, frame in progress and decoder of an
-        // unchanged entry move to its new slot, every other slot is a new mp2Processor
-        if (p->NMP) {
-            Mp2Layer &m = p->mp2;
-            const size_t NM = p->NMP, FS = m.fstride, o = (size_t)s * NM;
-            std::vector<Mp2SyncState> sy(NM), nsy(NM, Mp2SyncState{0, 0, 0, 0});
-            std::vector<uint8_t> pt(NM * FS), npt(NM * FS, 0);
-            std::vector<int16_t> vs(NM * MP2_STATE_I16), nvs(NM * MP2_STATE_I16, 0);
-            HIPCHK(hipMemcpy(sy.data(), m.sync_d + o, sizeof(Mp2SyncState) * NM, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(pt.data(), m.part_d + o * FS, NM * FS, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(vs.data(), m.vstate_d[m.cur] + o * MP2_STATE_I16, sizeof(int16_t) * vs.size(), hipMemcpyDeviceToHost));
-            std::vector<int> oslot(old.size(), -1);
-            for (int k = 0, j = 0; k < (int)old.size(); k++)
-                if (old[k].flags & DABGPU_SUBCH_MP2) oslot[k] = j++;
-            for (int k = 0, j = 0; k < n; k++) {
-                if (!(sub[k].flags & DABGPU_SUBCH_MP2)) continue;
-                if (k < (int)old.size() && same_subch(old[k], sub[k])) {
-                    nsy[j] = sy[oslot[k]];
-                    memcpy(npt.data() + j * FS, pt.data() + oslot[k] * FS, FS);
-                    memcpy(nvs.data() + (size_t)j * MP2_STATE_I16, vs.data() + (size_t)oslot[k] * MP2_STATE_I16,
-                           sizeof(int16_t) * MP2_STATE_I16);
-                }
-                j++;
-            }
-            HIPCHK(hipMemcpy(m.sync_d + o, nsy.data(), sizeof(Mp2SyncState) * NM, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(m.part_d + o * FS, npt.data(), NM * FS, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(m.vstate_d[m.cur] + o * MP2_STATE_I16, nvs.data(), sizeof(int16_t) * nvs.size(), hipMemcpyHostToDevice));
-        }
-        // the packet slots likewise: an unchanged entry's assembler and series in flight move
-        // to its new slot, every other slot is a new mscDatagroup
-        if (p->NPK) {
-            PacketLayer &m = p->pk;
-            const size_t NK = p->NPK, CB = m.cap, o = (size_t)s * NK;
-            std::vector<PkState> ps(NK), nps(NK, PkState{0, -1, 0, 0, 0, 0, 0, 0});
-            std::vector<uint8_t> ca(NK * CB), nca(NK * CB, 0);
-            HIPCHK(hipMemcpy(ps.data(), m.state_d + o, sizeof(PkState) * NK, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(ca.data(), m.carry_d[m.cur] + o * CB, NK * CB, hipMemcpyDeviceToHost));
-            std::vector<int> oslot(old.size(), -1);
-            for (int k = 0, j = 0; k < (int)old.size(); k++)
-                if (old[k].flags & DABGPU_SUBCH_PACKET) oslot[k] = j++;
-            for (int k = 0, j = 0; k < n; k++) {
-                if (!(sub[k].flags & DABGPU_SUBCH_PACKET)) continue;
-                if (k < (int)old.size() && same_subch(old[k], sub[k])) {
-                    nps[j] = ps[oslot[k]];
-                    memcpy(nca.data() + j * CB, ca.data() + oslot[k] * CB, CB);
-                }
-                j++;
-            }
-            HIPCHK(hipMemcpy(m.state_d + o, nps.data(), sizeof(PkState) * NK, hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(m.carry_d[m.cur] + o * CB, nca.data(), NK * CB, hipMemcpyHostToDevice));
-        }
-        // the MOT slots likewise: an unchanged entry's motHandler moves to its new slot, every
-        // other slot is a new one
-        if (p->NMOT) {
-            MotLayer &m = p->mot;
-            const size_t NM = p->NMOT, SB = m.state_bytes, o = (size_t)s * NM * SB;
-            std::vector<uint8_t> ms(NM * SB), nms(NM * SB, 0);
-            HIPCHK(hipMemcpy(ms.data(), m.state_d + o, NM * SB, hipMemcpyDeviceToHost));
-            std::vector<int> oslot(old.size(), -1);
-            for (int k = 0, j = 0; k < (int)old.size(); k++)
-                if (old[k].flags & DABGPU_SUBCH_MOT) oslot[k] = j++;
-            for (int k = 0, j = 0; k < n; k++) {
-                if (!(sub[k].flags & DABGPU_SUBCH_MOT)) continue;
-                if (k < (int)old.size() && same_subch(old[k], sub[k])) memcpy(nms.data() + j * SB, ms.data() + oslot[k] * SB, SB);
-                j++;
-            }
-            HIPCHK(hipMemcpy(m.state_d + o, nms.data(), NM * SB, hipMemcpyHostToDevice));
-        }
-        // the PAD slots likewise: an unchanged entry's padHandler moves to its new slot, every
-        // other slot is a new one
-        if (p->NPAD) {
-            const size_t NM = p->NPAD, SB = sizeof(PadState), o = (size_t)s * NM * SB;
-            std::vector<uint8_t> ms(NM * SB), nms(NM * SB, 0);
-            HIPCHK(hipMemcpy(ms.data(), p->pad.state_d + o, NM * SB, hipMemcpyDeviceToHost));
-            std::vector<int> oslot(old.size(), -1);
-            for (int k = 0, j = 0; k < (int)old.size(); k++)
-                if (old[k].flags & DABGPU_SUBCH_PAD) oslot[k] = j++;
-            for (int k = 0, j = 0; k < n; k++) {
-                if (!(sub[k].flags & DABGPU_SUBCH_PAD)) continue;
-                if (k < (int)old.size() && same_subch(old[k], sub[k])) memcpy(nms.data() + j * SB, ms.data() + oslot[k] * SB, SB);
-                j++;
-            }
-            HIPCHK(hipMemcpy(p->pad.state_d + o, nms.data(), NM * SB, hipMemcpyHostToDevice));
-        }
-        p->tab[s].assign(sub, sub + n);
-        p->since[s].assign(n, p->st[s].cif_count);
-        for (int k = 0, j = 0; k < n; k++) {
-            const bool kept = k < (int)old.size() && same_subch(old[k], sub[k]);
-            if (kept) p->since[s][k] = old_since[k];
-            if (!(sub[k].flags & DABGPU_SUBCH_DABPLUS)) continue;
-            if (kept) {
-                memcpy(nrings.data() + (size_t)j * RB, rings.data() + (size_t)old_slot[k] * RB, RB);
-                nsts[j] = sts[old_slot[k]];
-            }
-            j++;
-        }
-        if (p->NDP) {
-            HIPCHK(hipMemcpy(p->dp.ring_d + (size_t)s * p->NDP * RB, nrings.data(), nrings.size(), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(p->dp.state_d + (size_t)s * p->NDP, nsts.data(), sizeof(DpState) * p->NDP, hipMemcpyHostToDevice));
-        }
-    }
-    p->last_msc = nullptr;            // the last run's rows follow the old tables: no DAB+ layer over them now
-    p->mot_pending = false;
-    p->pad_pending = false;
-    if (int rc = rebuild_tables(p)) return rc;
-    if (p->inject_bounds) return inject_table(p);
-    return 0;
-}
-
-int dabgpu_pipe_get_subch(dabgpu_pipe *p, int stream, dabgpu_subch *sub, int32_t *n, int64_t *since_cif) {
-    if (!p || !n || stream < 0 || stream >= p->S || (!sub && !p->tab[stream].empty()))
-        return fail(DABGPU_E_ARG, "bad args");
-    *n = (int32_t)p->tab[stream].size();
-    for (int k = 0; k < *n; k++) {
-        sub[k] = p->tab[stream][k];
-        if (since_cif) since_cif[k] = p->since[stream][k];
-    }
-    return 0;
-}
-
 int dabgpu_pipe_msc_entry_valid(dabgpu_pipe *p, uint8_t *valid_h) {
     if (!p || !valid_h) return fail(DABGPU_E_ARG, "bad args");
     const size_t nb = (size_t)p->S * 4 * p->F * p->NSUB;
@@ -1940,8 +857,7 @@ int dabgpu_pipe_set_display(dabgpu_pipe *p, int on) {
     if (!p) return fail(DABGPU_E_ARG, "bad args");
     if (on && !p->disp_d) {
         HIPCHK(hipStreamSynchronize(p->c->stream));
-        HIPCHK(p->disp_d.alloc((size_t)p->S * p->R * K));
-        HIPCHK(hipMemset(p->disp_d, 0, sizeof(float2) * (size_t)p->S * p->R * K));
+        HIPCHK(p->disp_d.zalloc((size_t)p->S * p->R * K));
     }
     p->display = on != 0;
     return 0;

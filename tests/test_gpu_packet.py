@@ -351,6 +351,29 @@ def test_pipeline_tables_and_caps(ctx, tx_iq):
         p.close()
 
 
+def test_pipeline_kept_entries_change_slot(ctx, tx_iq):
+    """set_subch that takes the first packet entry's flags away and leaves the other two as they
+    are: those keep their assemblers though their slots move from 1 and 2 down to 0 and 1 -- the
+    series in flight completes (Layer.run's comparison against the carried Assemblers) and no
+    CIF of the next run is missing (status 0 throughout); the slot left over is empty"""
+    L = Layer(ctx, tx_iq[:1], _subs(TX))
+    try:
+        L.run()
+        run = L.out[-1][2][0]
+        print("before the change: state", run["state"].tolist(), "pending_bytes", run["pending_bytes"].tolist())
+        assert (run["state"][1:3] == 1).any() and (run["pending_bytes"][1:3] > 0).any()   # a kept entry has a series in flight
+        moved = [TX[0][:5] + (0,)] + TX[1:4]
+        L.pipe.set_subch(0, _subs(moved))
+        L.table(_subs(moved), keep=(1, 2))
+        assert [k for k, _ in L.slots] == [1, 2] and sorted(L.asm) == [(0, 0), (0, 1)]
+        _, ev = L.run()
+        info = L.out[-1][3][0]
+        assert ev[0, :, 1:3].all() and (info[:, :2]["status"] == 0).all()     # no gap
+        assert (info[:, 2]["status"] == -1).all()
+    finally:
+        L.close()
+
+
 def test_dropin_on_datagroup(ctx, long_iq, tmp_path):
     """ensembleDecoder::on_datagroup / on_packet_quality (a C++ program over the drop-in
     library, auto_layout on the transmitter's FIGs, 10 steps of 6 frames): the table it parses

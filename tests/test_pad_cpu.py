@@ -7,6 +7,7 @@ reference is undefined or unbounded on cases outside the golden file, and what t
 the binding export."""
 import ctypes as C
 import os
+import subprocess
 
 import numpy as np
 import pytest
@@ -27,8 +28,8 @@ def kat():
 
 @pytest.fixture(scope="module")
 def wrap():
-    if not os.path.exists(WRAP):
-        pytest.fail(f"{WRAP} not built (run __graft_entry__.build())")
+    # built here when build()'s copy is not there (as test_consumers_cpu builds its library)
+    subprocess.run(["make", "-s", "-f", os.path.join(ROOT, "tests", "cpp", "Makefile.pad"), WRAP], check=True)
     l = C.CDLL(WRAP)
     l.pw_new.restype = C.c_void_p
     l.pw_free.argtypes = [C.c_void_p]
