@@ -194,6 +194,39 @@ typedef struct {            /* a motElement (mot-data.h:33-44) */
 #define DABGPU_MOT_ARENA_BYTES(n_frames, max_bitrate, max_body_bytes) \
     DABGPU_MOT_ARENA_FOR(DABGPU_PKT_GROUP_SLOTS(n_frames, max_bitrate), max_body_bytes)
 
+#define DABGPU_SUBCH_IP      64  /* feed the packet entry's data groups to the IP layer (dabgpu_pipe_ip); only together
+                                    with DABGPU_SUBCH_PACKET, not together with DABGPU_SUBCH_MOT (one my_dataHandler
+                                    per mscDatagroup): DABGPU_E_ARG otherwise */
+/* An ip_dataHandler's carried state (ip-datahandler.cpp:100-104, show_crcErrors on).  All zero: a new one. */
+typedef struct {
+    int32_t handled;        /* handledPackets */
+    int32_t crc_errors;     /* crcErrors */
+} dabgpu_ip_state;
+/* What ip_dataHandler::add_mscDatagroup did with one group of the run; index = the group's index */
+typedef struct {
+    int32_t offset;         /* of the payload in the slot's output arena, a multiple of 16; 0 unless delivered */
+    int32_t nbytes;         /* payload length (ipLength - 4 * headerSize - 8); 0 unless delivered */
+    int16_t status;         /* DABGPU_IP_* */
+    int16_t quality;        /* what show_ipErrors emits inside this group's call (100 - crcErrors), else -1 */
+    int32_t ip_bytes;       /* ipLength, 0 when the group never got that far */
+} dabgpu_ip_result;
+#define DABGPU_IP_DELIVERED    0   /* writeDatagram: the UDP payload */
+#define DABGPU_IP_NOT_ACCEPTED 1   /* no DABGPU_DG_ACCEPTED (:54), or rule 5 */
+#define DABGPU_IP_TOO_LONG     2   /* ipLength >= the group's bytes (:80) */
+#define DABGPU_IP_NOT_V4       3   /* (:85), or rule 2 */
+#define DABGPU_IP_CHECKSUM     4   /* the header checksum (:108): counted in crcErrors */
+#define DABGPU_IP_NOT_UDP      5   /* protocol != 17 (:117) */
+#define DABGPU_IP_MALFORMED    6   /* rules 3 and 6 */
+/* One (stream, packet slot) after a run */
+typedef struct {
+    int32_t n_datagrams;    /* groups that ended DABGPU_IP_DELIVERED */
+    int32_t n_bytes;        /* their payload bytes */
+    int32_t counts[7];      /* groups by status */
+    int32_t reserved[3];
+} dabgpu_ip_run;
+/* Output arena bytes per slot: every payload lies inside its group, and each starts at a multiple of 16 */
+#define DABGPU_IP_ARENA_FOR(group_slots, arena_bytes) ((arena_bytes) + 16 * (group_slots))
+
 #define DABGPU_SUBCH_PAD     32  /* feed the DAB+ entry's good AUs to the PAD layer (dabgpu_pipe_pad); only together
                                     with DABGPU_SUBCH_DABPLUS (DABGPU_E_ARG otherwise).  PAD slot j of a stream is
                                     its j-th entry so flagged. */
@@ -529,6 +562,59 @@ int dabgpu_mot_groups(dabgpu_ctx *ctx, void *state_d, int n_slots, int max_body_
                       const dabgpu_packet_run *run_d, dabgpu_mot_object *objects_d, uint8_t *out_d,
                       int64_t out_arena_bytes, dabgpu_mot_run *mot_run_d);
 
+/* ip_dataHandler::add_mscDatagroup (ip-datahandler.cpp:40-127, show_crcErrors on) batched: n_slots
+ * independent ip_dataHandlers, each taking the groups of one (stream, packet slot) of a
+ * dabgpu_pipe_packet call, or buffers in that layout, in completion order.
+ *   state_d    [n_slots], all zero for a new ip_dataHandler, updated in place
+ *   groups_d   [n_slots][group_slots], run_d [n_slots] (n_groups is read), bytes_d
+ *              [n_slots][arena_bytes]
+ *   results_d  [n_slots][group_slots], the first run.n_groups written: one per group
+ *   out_d      [n_slots][out_arena_bytes]: the payloads, in group order, each at a multiple of 16
+ *              (DABGPU_IP_ARENA_FOR(group_slots, arena_bytes) holds whatever the groups carry);
+ *              bytes between payloads are not written
+ *   ip_run_d   [n_slots]
+ * Kept bit for bit from the reference:
+ *   - a group with the CRC flag and a bad CRC is ignored (:54); the layer skips every group
+ *     without DABGPU_DG_ACCEPTED, so empty and truncated groups go the same way;
+ *   - next (:57-74) is the packet layer's data_offset: the walk over the extension, segment and
+ *     user access fields is, step for step, that of mot-databuilder.cpp:37-95 which that field
+ *     restates -- the two do not differ anywhere;
+ *   - ipLength is bytes 2..3 after next (:79) and the datagram is taken only when ipLength <
+ *     the group's byte length, CRC bytes included (:80: msc.size () counts bits);
+ *   - ipLength bytes are copied from next; the version test is (ipVector [0] >> 4) != 4 on a
+ *     signed char (:85), which only 0x40..0x4F pass: 0xC? shifts to -4;
+ *   - the window steps before the datagram's own checksum test (:100-104): ++handledPackets >=
+ *     100 emits 100 - crcErrors and clears both counters;
+ *   - the checksum covers 2 * headerSize big-endian 16-bit words, headerSize 0..15 as it comes
+ *     (0 sums to 0 and fails), with one fold; (~sum & 0xFFFF) != 0 counts in crcErrors (:105-111);
+ *   - only protocol 17 goes on (:113-119); the payload starts at 4 * headerSize + 8 and its
+ *     length is ipSize - 4 * headerSize - 8, ipSize being the two bytes of ipLength (:124-127);
+ *     the UDP header's length, ports and checksum are not looked at.
+ * Where the reference is undefined or unbounded:
+ *   1. bytes past a group's stored end read 0: the length field of a group that ends inside it
+ *      (:79) and a datagram with next + ipLength > the group's bytes (:84).  Since next >= 2, that
+ *      is every datagram with ipLength >= nbytes - 1.  A datagram that overlaps the two CRC
+ *      bytes of a group with the CRC flag reads them complemented: check_CRC_bits inverts them in
+ *      place (:54, dab-constants.h:321-322) before the copy, while the packet layer stores the
+ *      group as it was received (tests/golden/ip_kat.npz pins this on the reference's own code);
+ *   2. ipLength == 0 is DABGPU_IP_NOT_V4 and nothing is read (ipVector [0] of an empty array);
+ *   3. header bytes past ipLength read 0 (the reference reads past its vector when 4 * headerSize
+ *      or 10 > ipLength); a negative payload length is DABGPU_IP_MALFORMED, counted after the
+ *      window and checksum steps, where the reference would have called writeDatagram with it;
+ *      length 0 is delivered as an empty datagram;
+ *   4. lengths are int32 (ipSize and headerSize are int16_t in the reference); quality is stored
+ *      as int16;
+ *   5. a group record that points outside its arena is DABGPU_IP_NOT_ACCEPTED;
+ *   6. a payload that ends beyond out_arena_bytes is DABGPU_IP_MALFORMED; it still takes its
+ *      place, rounded up to 16, in the count of offsets (with DABGPU_IP_ARENA_FOR only records
+ *      that overlap in their arena get there).
+ * DABGPU_E_ARG for a bad size: n_slots or group_slots < 0, arena sizes outside [0, 2^31).
+ * Asynchronous on the context stream. */
+int dabgpu_ip_groups(dabgpu_ctx *ctx, dabgpu_ip_state *state_d, int n_slots,
+                     const dabgpu_datagroup *groups_d, int group_slots, const uint8_t *bytes_d, int64_t arena_bytes,
+                     const dabgpu_packet_run *run_d, dabgpu_ip_result *results_d, uint8_t *out_d,
+                     int64_t out_arena_bytes, dabgpu_ip_run *ip_run_d);
+
 /* padHandler::processPAD (pad-handler.cpp) batched: n_slots independent padHandlers, each
  * taking its n_aus AUs in order, fed as mp4Processor feeds them (mp4processor.cpp:237-265).
  *   state_d   [n_slots][dabgpu_pad_state_bytes()], opaque, all zero for a new padHandler,
@@ -686,8 +772,8 @@ typedef struct {
  * Outputs per slot: events_d [n_slots][event_slots] in the order raised, each with the FIB that
  * caused it (events past event_slots are counted and not recorded; the slots a call does not
  * fill are zeroed); table_d [n_slots]:
- * fib_processor::subchannels(ids, classic_audio, packet_data, mot, pad) at the end of the call,
- * the four booleans being the bits DABGPU_SUBCH_MP2 | PACKET | MOT | PAD of want_flags; run_d
+ * fib_processor::subchannels(ids, classic_audio, packet_data, mot, pad, ip) at the end of the call,
+ * the five booleans being the bits DABGPU_SUBCH_MP2 | PACKET | MOT | PAD | IP of want_flags; run_d
  * [n_slots].
  * Where the reference is undefined:
  *   1. the overrun rule: a read at or past bit 256 of the FIB reads 0, control flow otherwise the
@@ -929,6 +1015,27 @@ int dabgpu_pipe_mot(dabgpu_pipe *p, uint8_t *bytes_d, dabgpu_mot_object *objects
  * DABGPU_MOT_TOO_LARGE).  DABGPU_E_ARG for negative values, max_mot > max_packet,
  * max_body_bytes > 1 << 24 or fewer slots than an applied table flags. */
 int dabgpu_pipe_mot_caps(dabgpu_pipe *p, int max_mot, int max_body_bytes);
+/* IP layer for the groups of the run's dabgpu_pipe_packet call (call once per run, after it):
+ * dabgpu_ip_groups for every entry flagged DABGPU_SUBCH_PACKET | DABGPU_SUBCH_IP.  The outputs are
+ * indexed by packet slot; the slot of an entry that is not flagged gets an all-zero dabgpu_ip_run
+ * and is not walked.  It reads that call's bytes_d, groups_d and run_d (keep them alive and
+ * unchanged).  The ip_dataHandlers' counters live beside the packet layer's assemblers (8 bytes
+ * per packet slot, allocated with the packet layer: there is no caps call): dabgpu_pipe_set_subch
+ * keeps those of an unchanged entry, flags included, every other entry starts at zero, and
+ * dabgpu_pipe_packet_caps keeps those of the slots both sizes hold.
+ *   bytes_d   [n_streams][max_packet][DABGPU_IP_ARENA_FOR(DABGPU_PKT_GROUP_SLOTS(n_frames,
+ *             max_bitrate), DABGPU_PKT_ARENA_BYTES(n_frames, max_bitrate, max_group_bytes))]
+ *   results_d [n_streams][max_packet][DABGPU_PKT_GROUP_SLOTS(n_frames, max_bitrate)]
+ *   run_d     [n_streams][max_packet]
+ * Runs on the run's back-end stream behind the packet layer.  DABGPU_E_STATE without a packet
+ * layer (max_packet == 0), without a dabgpu_pipe_packet call for the run, on a second call, or
+ * when no applied table flags an entry DABGPU_SUBCH_IP (nothing is launched then); DABGPU_E_ARG
+ * when the packet layer's arena is 2 GiB and more. */
+int dabgpu_pipe_ip(dabgpu_pipe *p, uint8_t *bytes_d, dabgpu_ip_result *results_d, dabgpu_ip_run *run_d);
+/* One stream's ip_dataHandler counters, by packet slot, to host memory: state_h [max_packet] (a
+ * slot whose entry is not flagged holds zeros).  Waits for everything the pipeline has enqueued.
+ * DABGPU_E_ARG for a bad stream, DABGPU_E_STATE without a packet layer. */
+int dabgpu_pipe_ip_state(dabgpu_pipe *p, int stream, dabgpu_ip_state *state_h);
 /* PAD layer for the AUs of the run's dabgpu_pipe_dabplus call (call once per run, after it):
  * dabgpu_pad_aus for every entry flagged DABGPU_SUBCH_DABPLUS | DABGPU_SUBCH_PAD, PAD slot j of
  * a stream being its j-th such entry.  sf_bytes_d, sf_stride and info_d are those of that call

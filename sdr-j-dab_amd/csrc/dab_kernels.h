@@ -304,6 +304,25 @@ struct MotJob {
     int32_t *nops;                  // [n_slots]
 };
 
+// IP layer (k_ip.hip): n_slots ip_dataHandlers over the groups of a packet-layer pass, row i for slot i
+static_assert(sizeof(dabgpu_ip_state) == 8 && sizeof(dabgpu_ip_result) == 16 && sizeof(dabgpu_ip_run) == 48,
+              "the IP records are read as bytes by the bindings");
+struct IpJob {
+    int32_t n_slots;
+    dabgpu_ip_state *state;         // [n_slots]
+    const int32_t *on;              // optional [n_slots]: 0: the slot's entry is not flagged, its run is zeroed and
+                                    //   nothing else is read or written; NULL: every slot is walked
+    const dabgpu_datagroup *groups; // [n_slots][gslots]
+    int32_t gslots;
+    const uint8_t *bytes;           // [n_slots][arena]
+    int64_t arena;                  // < 2^31
+    const dabgpu_packet_run *run;   // [n_slots]
+    dabgpu_ip_result *results;      // [n_slots][gslots]
+    uint8_t *out;                   // [n_slots][out_arena]
+    int64_t out_arena;              // < 2^31
+    dabgpu_ip_run *ip_run;          // [n_slots]
+};
+
 // PAD layer (k_pad.hip): n_slots padHandlers, each over its AUs in order
 constexpr int PAD_BUFFER = 8192;    // msc_dataGroupBuffer
 struct PadState {                   // a padHandler's carried state; all zero: a new one
@@ -355,7 +374,7 @@ struct FibJob {
     int64_t stride;
     int32_t bit_src;                // the FIBs are one bit per byte (the pipeline's unpacked FIC)
     const uint8_t *ok;              // [n_slots][n_fibs]
-    int32_t want;                   // DABGPU_SUBCH_MP2 | PACKET | MOT | PAD
+    int32_t want;                   // DABGPU_SUBCH_MP2 | PACKET | MOT | PAD | IP
     dabgpu_fic_event *events;       // [n_slots][event_slots]
     int32_t event_slots;
     dabgpu_fic_table *table;        // [n_slots]
@@ -399,6 +418,7 @@ hipError_t launch_mp2_decode(hipStream_t st, const Mp2Job &job);
 hipError_t launch_mp2_sync(hipStream_t st, const Mp2SyncJob &job);
 hipError_t launch_packet(hipStream_t st, const PkJob &job);
 hipError_t launch_mot(hipStream_t st, const MotJob &job);
+hipError_t launch_ip(hipStream_t st, const IpJob &job);
 hipError_t launch_pad(hipStream_t st, const PadJob &job);
 hipError_t launch_fib(hipStream_t st, const FibJob &job);
 hipError_t launch_fic_clear(hipStream_t st, dabgpu_fic_db *db, int n_slots);

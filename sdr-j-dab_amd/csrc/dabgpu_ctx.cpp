@@ -802,7 +802,7 @@ int dabgpu_fib_parse(dabgpu_ctx *c, dabgpu_fic_db *db, int n_slots, const uint8_
     J.fibs = fibs;
     J.stride = fib_stride;
     J.ok = ok;
-    J.want = want_flags & (DABGPU_SUBCH_MP2 | DABGPU_SUBCH_PACKET | DABGPU_SUBCH_MOT | DABGPU_SUBCH_PAD);
+    J.want = want_flags & (DABGPU_SUBCH_MP2 | DABGPU_SUBCH_PACKET | DABGPU_SUBCH_MOT | DABGPU_SUBCH_PAD | DABGPU_SUBCH_IP);
     J.events = events;
     J.event_slots = event_slots;
     J.table = table;
@@ -866,6 +866,31 @@ int dabgpu_mot_groups(dabgpu_ctx *c, void *state, int n_slots, int max_body_byte
     J.ops = (int4 *)w;
     J.nops = (int32_t *)((uint8_t *)w + ob);
     HIPCHK(launch_mot(c->stream, J));
+    return 0;
+}
+
+int dabgpu_ip_groups(dabgpu_ctx *c, dabgpu_ip_state *state, int n_slots, const dabgpu_datagroup *groups, int group_slots,
+                     const uint8_t *bytes, int64_t arena_bytes, const dabgpu_packet_run *run, dabgpu_ip_result *results,
+                     uint8_t *out, int64_t out_arena_bytes, dabgpu_ip_run *ip_run) {
+    if (!c || !state || !groups || !bytes || !run || !results || !out || !ip_run || n_slots < 0 || group_slots < 0)
+        return fail(DABGPU_E_ARG, "bad args");
+    if (arena_bytes < 0 || arena_bytes > 0x7FFFFFFF || out_arena_bytes < 0 || out_arena_bytes > 0x7FFFFFFF)
+        return fail(DABGPU_E_ARG, "arena sizes %lld / %lld", (long long)arena_bytes, (long long)out_arena_bytes);
+    if (!n_slots) return 0;
+    IpJob J;
+    memset(&J, 0, sizeof J);
+    J.n_slots = n_slots;
+    J.state = state;
+    J.groups = groups;
+    J.gslots = group_slots;
+    J.bytes = bytes;
+    J.arena = arena_bytes;
+    J.run = run;
+    J.results = results;
+    J.out = out;
+    J.out_arena = out_arena_bytes;
+    J.ip_run = ip_run;
+    HIPCHK(launch_ip(c->stream, J));
     return 0;
 }
 

@@ -65,7 +65,9 @@ std::vector<SlotBuf> state_bufs(dabgpu_pipe *p, int kind) {
                 {p->mp2.part_d.ptr, (size_t)p->mp2.fstride, nullptr},
                 {p->mp2.vstate_d[p->mp2.cur].ptr, sizeof(int16_t) * MP2_STATE_I16, nullptr}};
     case slots::PACKET:
-        return {{p->pk.state_d.ptr, sizeof(PkState), &kFreshPk}, {p->pk.carry_d[p->pk.cur].ptr, (size_t)p->pk.cap, nullptr}};
+        return {{p->pk.state_d.ptr, sizeof(PkState), &kFreshPk},
+                {p->pk.carry_d[p->pk.cur].ptr, (size_t)p->pk.cap, nullptr},
+                {p->pk.ip_state_d.ptr, sizeof(dabgpu_ip_state), nullptr}};
     case slots::MOT: return {{p->mot.state_d.ptr, p->mot.state_bytes, nullptr}};
     default: return {{p->pad.state_d.ptr, sizeof(PadState), nullptr}};
     }
@@ -168,6 +170,10 @@ int check_table(const dabgpu_subch *sub, int n, const TableLimits &lim) {
             return fail(DABGPU_E_ARG, "subchannel %d is flagged PAD and not DAB+", i);
         if ((fl & DABGPU_SUBCH_MOT) && !(fl & DABGPU_SUBCH_PACKET))
             return fail(DABGPU_E_ARG, "subchannel %d is flagged MOT and not packet mode", i);
+        if ((fl & DABGPU_SUBCH_IP) && !(fl & DABGPU_SUBCH_PACKET))
+            return fail(DABGPU_E_ARG, "subchannel %d is flagged IP and not packet mode", i);
+        if ((fl & DABGPU_SUBCH_IP) && (fl & DABGPU_SUBCH_MOT))
+            return fail(DABGPU_E_ARG, "subchannel %d is flagged both IP and MOT", i);
         if (make_profile(sub[i], P)) return fail(DABGPU_E_UNSUP, "subchannel %d protection undefined", i);
         if (sub[i].startAddr < 0 || sub[i].startAddr + sub[i].length > 864 || P.frag > sub[i].length * 64)
             return fail(DABGPU_E_ARG, "subchannel %d does not fit its CUs", i);
@@ -212,12 +218,18 @@ int packet_size(dabgpu_pipe *p, int npk, int cap) {
         HIPCHK(k.rec_d.alloc(ne * cells));
         HIPCHK(k.take_d.alloc(ne * cells));
         HIPCHK(k.segtab_d.alloc(ne * (1 + cells)));
+        HIPCHK(k.ip_ev.create(hipEventDisableTiming));
+        HIPCHK(k.ip_state_d.alloc(ne));
+        HIPCHK(k.ip_on_d.alloc(ne));
         for (auto &c : k.carry_d) HIPCHK(c.alloc(ne * cap));
         if (int rc = resize_buf(p->S, {old.state_d.ptr, sizeof(PkState), nullptr}, p->NPK,
                                 {k.state_d.ptr, sizeof(PkState), &kFreshPk}, npk))
             return rc;
         if (int rc = resize_buf(p->S, {old.carry_d[old.cur].ptr, (size_t)old.cap, nullptr}, p->NPK,
                                 {k.carry_d[0].ptr, (size_t)cap, nullptr}, npk))
+            return rc;
+        if (int rc = resize_buf(p->S, {old.ip_state_d.ptr, sizeof(dabgpu_ip_state), nullptr}, p->NPK,
+                                {k.ip_state_d.ptr, sizeof(dabgpu_ip_state), nullptr}, npk))
             return rc;
     }
     p->pk = std::move(k);
@@ -360,6 +372,20 @@ int rebuild_tables(dabgpu_pipe *p) {
     const SlotMap *const maps[] = {&p->dp.map, &p->mp2.map, &p->pk.map};     // slots::DABPLUS, MP2, PACKET
     for (int kind = slots::DABPLUS; kind <= slots::PACKET; kind++)
         if (int rc = put_slot_map(p, kind, *maps[kind])) return rc;
+    // which packet slots the IP layer walks
+    p->pk.n_ip = 0;
+    if (p->NPK) {
+        std::vector<int32_t> on((size_t)S * p->NPK, 0);
+        for (int s = 0; s < S; s++) {
+            const std::vector<int> slot = slots::slot_of_entry(p->tab[s].data(), (int)p->tab[s].size(), DABGPU_SUBCH_PACKET);
+            for (size_t k = 0; k < slot.size(); k++)
+                if (slot[k] >= 0 && slot[k] < p->NPK && (p->tab[s][k].flags & DABGPU_SUBCH_IP)) {
+                    on[(size_t)s * p->NPK + slot[k]] = 1;
+                    p->pk.n_ip++;
+                }
+        }
+        HIPCHK(hipMemcpy(p->pk.ip_on_d, on.data(), sizeof(int32_t) * on.size(), hipMemcpyHostToDevice));
+    }
     int32_t *const srcs[] = {p->mot.src_d, p->pad.src_d};                    // slots::MOT, PAD
     for (int kind = slots::MOT; kind <= slots::PAD; kind++)
         if (int rc = put_child_src(p, kind, srcs[kind - slots::MOT])) return rc;
@@ -524,7 +550,7 @@ int dabgpu_pipe_fic(dabgpu_pipe *p, const uint8_t *fic_bits, const uint8_t *fic_
     J.bit_src = p->feed.last_fic_packed ? 0 : 1;
     J.stride = (int64_t)J.n_fibs * (J.bit_src ? 256 : 32);
     J.ok = fic_crc;
-    J.want = want_flags & (DABGPU_SUBCH_MP2 | DABGPU_SUBCH_PACKET | DABGPU_SUBCH_MOT | DABGPU_SUBCH_PAD);
+    J.want = want_flags & (DABGPU_SUBCH_MP2 | DABGPU_SUBCH_PACKET | DABGPU_SUBCH_MOT | DABGPU_SUBCH_PAD | DABGPU_SUBCH_IP);
     J.events = events;
     J.event_slots = DABGPU_FIC_EVENT_SLOTS;
     J.table = table;
@@ -630,6 +656,42 @@ int dabgpu_pipe_packet(dabgpu_pipe *p, uint8_t *bytes, dabgpu_datagroup *groups,
     f.pk_groups = groups;
     f.pk_run = run;
     f.pending[slots::MOT] = p->NMOT > 0;
+    f.ip_pending = true;
+    return 0;
+}
+
+int dabgpu_pipe_ip(dabgpu_pipe *p, uint8_t *bytes, dabgpu_ip_result *results, dabgpu_ip_run *run) {
+    if (!p || !bytes || !results || !run) return fail(DABGPU_E_ARG, "null arg");
+    if (p->NPK == 0) return fail(DABGPU_E_STATE, "no packet-mode subchannel in this pipeline");
+    if (!p->feed.ip_pending) return fail(DABGPU_E_STATE, "no dabgpu_pipe_packet call of this run to consume");
+    PacketLayer &k = p->pk;
+    if (k.n_ip == 0) return fail(DABGPU_E_STATE, "no subchannel is flagged IP");
+    IpJob J;
+    memset(&J, 0, sizeof J);
+    J.n_slots = p->S * p->NPK;
+    J.state = k.ip_state_d;
+    J.on = k.ip_on_d;
+    J.groups = p->feed.pk_groups;
+    J.gslots = DABGPU_PKT_GROUP_SLOTS(p->F, p->max_bitrate);
+    J.bytes = p->feed.pk_bytes;
+    J.arena = DABGPU_PKT_ARENA_BYTES((int64_t)p->F, p->max_bitrate, k.cap);
+    J.run = p->feed.pk_run;
+    J.results = results;
+    J.out = bytes;
+    J.out_arena = DABGPU_IP_ARENA_FOR((int64_t)J.gslots, J.arena);
+    J.ip_run = run;
+    if (J.out_arena > 0x7FFFFFFF) return fail(DABGPU_E_ARG, "a packet arena of 2 GiB and more under the IP layer");
+    // behind the run's packet layer (the counters are updated in place)
+    if (int rc = layer_pass(p, k.ip_ev, [&](hipStream_t bs) { return launch_ip(bs, J); })) return rc;
+    p->feed.ip_pending = false;                // each run's groups enter the layer once
+    return 0;
+}
+
+int dabgpu_pipe_ip_state(dabgpu_pipe *p, int stream, dabgpu_ip_state *state_h) {
+    if (!p || !state_h || stream < 0 || stream >= p->S) return fail(DABGPU_E_ARG, "bad args");
+    if (p->NPK == 0) return fail(DABGPU_E_STATE, "no packet-mode subchannel in this pipeline");
+    if (int rc = sync_streams(p)) return rc;
+    HIPCHK(hipMemcpy(state_h, p->pk.ip_state_d + (size_t)stream * p->NPK, sizeof(dabgpu_ip_state) * p->NPK, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -689,6 +751,7 @@ int dabgpu_pipe_packet_caps(dabgpu_pipe *p, int max_packet, int max_group_bytes)
     if (int rc = sync_streams(p)) return rc;
     if (int rc = packet_size(p, max_packet, cap)) return rc;
     p->feed.pending[slots::MOT] = false;
+    p->feed.ip_pending = false;
     return rebuild_tables(p);
 }
 

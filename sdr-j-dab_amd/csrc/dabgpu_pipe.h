@@ -88,6 +88,11 @@ struct PacketLayer {
     dab::DevBuf<int2> take_d;          // [S * NPK][4F][ncell]
     dab::DevBuf<int32_t> segtab_d;     // [S * NPK][1 + 4F * ncell]
     dab::Event ev;                     // the last pass
+    // the IP layer over the packet slots (an ip_dataHandler per entry flagged DABGPU_SUBCH_IP and stream)
+    dab::DevBuf<dabgpu_ip_state> ip_state_d;   // [S][NPK] their counters, updated in place
+    dab::DevBuf<int32_t> ip_on_d;      // [S][NPK] 1: the slot's entry is flagged DABGPU_SUBCH_IP
+    int n_ip = 0;                      // entries so flagged in the applied tables
+    dab::Event ip_ev;                  // the last IP pass
 };
 // MOT layer (a motHandler per packet entry flagged DABGPU_SUBCH_MOT and stream): allocated
 // only while dabgpu_pipe_mot_caps' max_mot > 0
@@ -124,6 +129,7 @@ struct LayerFeed {
     // per slot kind: DAB+, layer II, packet -- the last run's CIFs have not entered the layer yet;
     // MOT, PAD -- nor the outputs below of the run's packet / dabplus call
     bool pending[slots::NKIND] = {};
+    bool ip_pending = false;             // the outputs of the run's packet call have not entered the IP layer yet
     const uint8_t *pk_bytes = nullptr;   // the run's dabgpu_pipe_packet call
     const dabgpu_datagroup *pk_groups = nullptr;
     const dabgpu_packet_run *pk_run = nullptr;
@@ -139,6 +145,7 @@ struct LayerFeed {
         pending[slots::DABPLUS] = pending[slots::MP2] = pending[slots::PACKET] = have_rows;
         pending[slots::MOT] = false;     // until this run's dabgpu_pipe_packet
         pending[slots::PAD] = false;     // until this run's dabgpu_pipe_dabplus
+        ip_pending = false;
         fic_pending = have_fic;
     }
     // the last run's rows follow the old tables: no layer over them now (the FIC's does not read tables)
@@ -146,6 +153,7 @@ struct LayerFeed {
         last_msc = nullptr;
         pending[slots::MOT] = false;
         pending[slots::PAD] = false;
+        ip_pending = false;
     }
 };
 

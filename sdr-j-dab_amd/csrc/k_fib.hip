@@ -379,7 +379,7 @@ __global__ __launch_bounds__(64) void k_fib_walk(FibJob J) {
         if (s.inUse) {
             const int pos = __popcll(mask & ((1ull << lane) - 1ull));
             const bool classic = J.want & DABGPU_SUBCH_MP2, packet = J.want & DABGPU_SUBCH_PACKET, mot = J.want & DABGPU_SUBCH_MOT,
-                       pad = J.want & DABGPU_SUBCH_PAD;
+                       pad = J.want & DABGPU_SUBCH_PAD, ip = J.want & DABGPU_SUBCH_IP;
             int flags = 0;
             for (int k = 0; k < 64; k++) {
                 const dabgpu_fic_component c = S.components[k];
@@ -390,11 +390,14 @@ __global__ __launch_bounds__(64) void k_fib_walk(FibJob J) {
                 } else if (c.TMid == 3 && c.DSCTy != 0 && !(c.DSCTy == 5 && c.DGflag)) {
                     if (packet) flags |= DABGPU_SUBCH_PACKET;
                     if (mot && c.DSCTy == 60) flags |= DABGPU_SUBCH_PACKET | DABGPU_SUBCH_MOT;
+                    if (ip && c.DSCTy == 59) flags |= DABGPU_SUBCH_PACKET | DABGPU_SUBCH_IP;
                 }
             }
             if ((flags & DABGPU_SUBCH_DABPLUS) && pad) flags |= DABGPU_SUBCH_PAD;
             if (flags & DABGPU_SUBCH_DABPLUS) flags &= ~DABGPU_SUBCH_MP2;                           // (one layer per entry,
-            if (flags & (DABGPU_SUBCH_DABPLUS | DABGPU_SUBCH_MP2)) flags &= ~(DABGPU_SUBCH_PACKET | DABGPU_SUBCH_MOT);   // the audio layers first)
+            if (flags & (DABGPU_SUBCH_DABPLUS | DABGPU_SUBCH_MP2))
+                flags &= ~(DABGPU_SUBCH_PACKET | DABGPU_SUBCH_MOT | DABGPU_SUBCH_IP);                // the audio layers first,
+            if (flags & DABGPU_SUBCH_MOT) flags &= ~DABGPU_SUBCH_IP;                                 // MOT before IP)
             dabgpu_subch e;
             e.startAddr = s.StartAddr;
             e.length = s.Length;

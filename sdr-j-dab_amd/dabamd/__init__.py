@@ -121,6 +121,48 @@ def mot_groups(ctx: "Context", groups: np.ndarray, data: np.ndarray, run: np.nda
             b.free()
 
 
+SUBCH_IP = 64       # Subch.flags, with SUBCH_PACKET and without SUBCH_MOT: feed the entry's groups to the IP layer (Pipeline.ip)
+IP_DELIVERED, IP_NOT_ACCEPTED, IP_TOO_LONG, IP_NOT_V4, IP_CHECKSUM, IP_NOT_UDP, IP_MALFORMED = range(7)   # dabgpu_ip_result.status
+IP_STATE_DTYPE = np.dtype([("handled", "<i4"), ("crc_errors", "<i4")])                                    # dabgpu_ip_state
+IP_RESULT_DTYPE = np.dtype([("offset", "<i4"), ("nbytes", "<i4"), ("status", "<i2"), ("quality", "<i2"),
+                            ("ip_bytes", "<i4")])                                                         # dabgpu_ip_result
+IP_RUN_DTYPE = np.dtype([("n_datagrams", "<i4"), ("n_bytes", "<i4"), ("counts", "<i4", (7,)), ("reserved", "<i4", (3,))])
+
+
+def ip_arena_bytes(group_slots: int, arena_bytes: int) -> int:
+    """DABGPU_IP_ARENA_FOR"""
+    return arena_bytes + 16 * group_slots
+
+
+def ip_groups(ctx: "Context", groups: np.ndarray, data: np.ndarray, run: np.ndarray,
+              state: Optional[np.ndarray] = None, out_arena_bytes: Optional[int] = None):
+    """ip_dataHandler::add_mscDatagroup per slot (dabgpu_ip_groups; ip-datahandler.cpp:40-127):
+    groups [n_slots, group_slots] DATAGROUP_DTYPE, data [n_slots, arena] uint8 and run [n_slots]
+    PACKET_RUN_DTYPE as Pipeline.packet() returns them for one stream; state [n_slots]
+    IP_STATE_DTYPE carried from an earlier call (None: new ip_dataHandlers).  Returns (results
+    [n_slots, group_slots] IP_RESULT_DTYPE -- the first run.n_groups of a row --, bytes [n_slots,
+    out_arena] uint8, ip_run [n_slots] IP_RUN_DTYPE, state)."""
+    groups = np.ascontiguousarray(groups, dtype=DATAGROUP_DTYPE)
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    run = np.ascontiguousarray(run, dtype=PACKET_RUN_DTYPE)
+    n, gs = groups.shape
+    assert data.shape[0] == n and run.shape == (n,)
+    st = np.zeros(n, IP_STATE_DTYPE) if state is None else np.ascontiguousarray(state, dtype=IP_STATE_DTYPE).reshape(n)
+    oa = ip_arena_bytes(gs, data.shape[1]) if out_arena_bytes is None else int(out_arena_bytes)
+    dg, db, dr, ds = ctx.put(groups.view(np.uint8)), ctx.put(data), ctx.put(run.view(np.uint8)), ctx.put(st.view(np.uint8))
+    do = ctx.buf(max(16, n * gs * IP_RESULT_DTYPE.itemsize)).zero()
+    dby, dir_ = ctx.buf(max(16, n * max(oa, 0))).zero(), ctx.buf(max(16, n * IP_RUN_DTYPE.itemsize)).zero()
+    try:
+        _chk(lib().dabgpu_ip_groups(ctx.h, ds.ptr, n, dg.ptr, gs, db.ptr, data.shape[1], dr.ptr, do.ptr, dby.ptr, oa, dir_.ptr),
+             "dabgpu_ip_groups")
+        ctx.sync()
+        return (_records(do, IP_RESULT_DTYPE, (n, gs)), dby.download(np.uint8, (n, max(oa, 0))),
+                _records(dir_, IP_RUN_DTYPE, (n,)), _records(ds, IP_STATE_DTYPE, (n,)))
+    finally:
+        for b in (dg, db, dr, ds, do, dby, dir_):
+            b.free()
+
+
 SUBCH_PAD = 32      # Subch.flags, with SUBCH_DABPLUS: feed the entry's good AUs to the PAD layer (Pipeline.pad)
 PAD_LABEL_BYTES, PAD_LABEL_PIECES, PAD_LABEL_TRUNCATED = 256, 64, 1
 PAD_LABEL_DTYPE = np.dtype([("cif", "<i4"), ("au", "<i4"), ("charset", "<i4"), ("nbytes", "<i4"), ("n_pieces", "<i4"),
@@ -359,6 +401,9 @@ def lib() -> C.CDLL:
             "dabgpu_pipe_fic_db": ([vp, i32, vp], i32),
             "dabgpu_pipe_fic_clear": ([vp, i32], i32),
             "dabgpu_pipe_mot": ([vp, vp, vp, vp], i32),
+            "dabgpu_ip_groups": ([vp, vp, i32, vp, i32, vp, i64, vp, vp, vp, i64, vp], i32),
+            "dabgpu_pipe_ip": ([vp, vp, vp, vp], i32),
+            "dabgpu_pipe_ip_state": ([vp, i32, vp], i32),
             "dabgpu_pipe_pad": ([vp, vp, i32, vp, vp, vp, vp, vp], i32),
             "dabgpu_pipe_pad_caps": ([vp, i32], i32),
             "dabgpu_pipe_mot_caps": ([vp, i32, i32], i32),
@@ -987,6 +1032,7 @@ class Pipeline:
             self._mp2 = [(ctx.buf(nrec * 1152 * 4).zero(), ctx.buf(nrec * MP2_INFO_DTYPE.itemsize)) for _ in range(2)]
 
         self._pkt = []
+        self._ip = []
         self.max_packet = sum(1 for s in self.subch if s.flags & SUBCH_PACKET)
         self.max_group_bytes = PKT_GROUP_BYTES
         if max_packet is not None or max_group_bytes is not None:
@@ -1118,11 +1164,42 @@ class Pipeline:
         return (self.motb_d.download(np.uint8, (S, NM, mot_arena_bytes(gs, self.max_body_bytes))),
                 _records(self.moto_d, MOT_OBJECT_DTYPE, (S, NM, gs)), _records(self.motr_d, MOT_RUN_DTYPE, (S, NM)))
 
+    def ip(self, download: bool = True):
+        """IP layer over the groups of this run's packet() (dabgpu_pipe_ip; ip-datahandler.cpp:
+        40-127), for the entries flagged SUBCH_PACKET | SUBCH_IP.  Returns (bytes [S, max_packet,
+        arena] uint8, results [S, max_packet, slots] IP_RESULT_DTYPE -- the first n_groups of a row
+        of this run's packet() are this run's --, run [S, max_packet] IP_RUN_DTYPE), indexed by
+        packet slot; the slot of an entry that is not flagged has an all-zero run."""
+        if not self._pkt:                # max_packet == 0: the library refuses (DABGPU_E_STATE) before it writes
+            _chk(lib().dabgpu_pipe_ip(self.h, self.fic_d.ptr, self.fic_d.ptr, self.fic_d.ptr), "dabgpu_pipe_ip")
+            raise DabError("dabgpu_pipe_ip accepted a pipeline without packet slots")
+        if not self._ip:
+            ne, gs = self.S * self.max_packet, pkt_group_slots(self.F, self.max_bitrate)
+            oa = ip_arena_bytes(gs, pkt_arena_bytes(self.F, self.max_bitrate, self.max_group_bytes))
+            self._ip = [(self.ctx.buf(ne * oa), self.ctx.buf(ne * gs * IP_RESULT_DTYPE.itemsize),
+                         self.ctx.buf(ne * IP_RUN_DTYPE.itemsize)) for _ in range(2)]
+        self.ipb_d, self.ipo_d, self.ipr_d = self._ip[(self._run - 1) & 1]
+        _chk(lib().dabgpu_pipe_ip(self.h, self.ipb_d.ptr, self.ipo_d.ptr, self.ipr_d.ptr), "dabgpu_pipe_ip")
+        if not download:
+            return None
+        self.sync()
+        S, NP, gs = self.S, self.max_packet, pkt_group_slots(self.F, self.max_bitrate)
+        oa = ip_arena_bytes(gs, pkt_arena_bytes(self.F, self.max_bitrate, self.max_group_bytes))
+        return (self.ipb_d.download(np.uint8, (S, NP, oa)), _records(self.ipo_d, IP_RESULT_DTYPE, (S, NP, gs)),
+                _records(self.ipr_d, IP_RUN_DTYPE, (S, NP)))
+
+    def ip_state(self, stream: int) -> np.ndarray:
+        """one stream's ip_dataHandler counters by packet slot, [max_packet] IP_STATE_DTYPE (dabgpu_pipe_ip_state)"""
+        st = np.zeros(max(1, self.max_packet), IP_STATE_DTYPE)
+        _chk(lib().dabgpu_pipe_ip_state(self.h, int(stream), _p(st)), "dabgpu_pipe_ip_state")
+        return st[:self.max_packet]
+
     def _packet_bufs(self) -> None:
-        for o in self._pkt:
+        for o in self._pkt + self._ip:
             for b in o:
                 b.free()
         self._pkt = []
+        self._ip = []                    # (allocated by the first ip() call)
         if self.max_packet:
             ne = self.S * self.max_packet
             self._pkt = [(self.ctx.buf(ne * pkt_arena_bytes(self.F, self.max_bitrate, self.max_group_bytes)),
@@ -1358,7 +1435,7 @@ class Pipeline:
 
     def close(self) -> None:
         if self.h:
-            for o in self._outs + self._sf + self._mp2 + self._pkt + self._mot + self._pad + self._fic:
+            for o in self._outs + self._sf + self._mp2 + self._pkt + self._ip + self._mot + self._pad + self._fic:
                 for b in o:
                     b.free()
             lib().dabgpu_pipe_destroy(self.h)

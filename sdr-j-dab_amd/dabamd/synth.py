@@ -16,7 +16,7 @@ class SynthSubch(C.Structure):
                 ("protLevel", C.c_int16), ("uep", C.c_int16), ("dabplus", C.c_int16), ("content", C.c_int16)]
 
 
-MP2, PACKET, AU_MIX, MOT, PAD = 2, 3, 4, 5, 6   # SynthSubch.content (dabsynth.h DABSYNTH_MP2 / _PACKET / _AU_MIX / _MOT / _PAD)
+MP2, PACKET, AU_MIX, MOT, PAD, IP = 2, 3, 4, 5, 6, 7   # SynthSubch.content (dabsynth.h DABSYNTH_MP2 / _PACKET / _AU_MIX / _MOT / _PAD / _IP)
 
 
 class SynthCfg(C.Structure):
@@ -41,6 +41,7 @@ def lib() -> C.CDLL:
         _lib.dabsynth_conv_encode.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         _lib.dabsynth_puncture_msc.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib.dabsynth_rs_encode.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.dabsynth_ip_carousel.argtypes = [C.c_uint64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     return _lib
 
 
@@ -52,7 +53,8 @@ class Ensemble:
     """Synthetic ensemble generator.  subch: tuples (startAddr, length, bitRate,
     protLevel, uep, dabplus[, content]) -- uep=1 for UEP (uepFlag 0 in the reference);
     content MP2 / PACKET for MPEG layer II frames / packet-mode data groups; MOT for
-    packet-mode data groups that carry a MOT slide carousel; AU_MIX
+    packet-mode data groups that carry a MOT slide carousel, IP for ones that carry IPv4/UDP
+    datagrams (DSCTy 59); AU_MIX
     on a DAB+ subchannel cycles its superframes through the 4 (dacRate, SBR) layouts."""
 
     def __init__(self, n_frames: int, subch: Sequence[tuple] = (), pre_offset: int = 50000,
@@ -128,6 +130,16 @@ class Ensemble:
         for p, q, m in self.stream_pieces(period):
             iq[2 * p:2 * (p + m)] = period_iq[2 * q:2 * (q + m)]
         return iq
+
+
+def ip_carousel(seed: int, sub: int) -> list:
+    """the data groups an IP subchannel `sub` of an ensemble made with `seed` sends round and round"""
+    data, lens = np.zeros(1 << 16, np.uint8), np.zeros(256, np.int32)
+    n = lib().dabsynth_ip_carousel(seed, sub, _p(data), data.size, _p(lens), lens.size)
+    if n < 0:
+        raise DabError("dabsynth_ip_carousel failed")
+    ends = np.cumsum(lens[:n])
+    return [data[e - l:e].tobytes() for e, l in zip(ends.tolist(), lens[:n].tolist())]
 
 
 def conv_encode(bits: np.ndarray) -> np.ndarray:

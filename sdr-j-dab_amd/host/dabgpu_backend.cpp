@@ -202,12 +202,17 @@ void dabConcurrent::setFiles(FILE *mp2, FILE *mp4) {                // dab-concu
 
 mscDatagroup::mscDatagroup(uint8_t DSCTy, int16_t packetAddress, int16_t fragmentSize, int16_t bitRate,
                            int16_t uepFlag, int16_t protLevel, uint8_t DGflag, int16_t FEC_scheme,
-                           packetAssembler::datagroup_cb cb, motAssembler::object_cb mot)
+                           packetAssembler::datagroup_cb cb, motAssembler::object_cb mot, ipAssembler::datagram_cb datagram,
+                           ipAssembler::quality_cb ip_quality)
     : dabConcurrent(DAB, fragmentSize, bitRate, uepFlag, protLevel, nullptr),
       mot_(DSCTy == 60 ? new motAssembler(std::move(mot)) : nullptr),                  // msc-datagroup.cpp:82-84
+      ip_(DSCTy == 59 ? new ipAssembler(std::move(datagram), std::move(ip_quality)) : nullptr),   // msc-datagroup.cpp:78-80
       pa_(DSCTy, DGflag, mot_ ? packetAssembler::datagroup_cb([m = mot_.get(), cb](const std::vector<uint8_t> &bits) {
               if (cb) cb(bits);
               m->add_mscDatagroup(bits);                                               // :285, :304
+          }) : ip_ ? packetAssembler::datagroup_cb([h = ip_.get(), cb](const std::vector<uint8_t> &bits) {
+              if (cb) cb(bits);
+              h->add_mscDatagroup(bits);
           }) : std::move(cb)) {
     (void)packetAddress;                           // the reference follows the first address it sees
     (void)FEC_scheme;
@@ -262,7 +267,7 @@ void mscHandler::process_mscBlock(int16_t *fbits, int16_t blkno) { // msc-handle
         } else {
             dabHandler_.reset(new mscDatagroup((uint8_t)np_.DSCTy, np_.packetAddress, (int16_t)(np_.length * 64),
                                                np_.bitRate, np_.uepFlag, np_.protLevel, (uint8_t)np_.DGflag,
-                                               np_.FEC_scheme, out_.datagroup, out_.mot));
+                                               np_.FEC_scheme, out_.datagroup, out_.mot, out_.datagram, out_.ip_quality));
             startAddr_ = np_.startAddr;
             Length_ = np_.length;
         }

@@ -517,7 +517,7 @@ bool ensembleDecoder::step() {
     const bool gpu_fic = cfg_.auto_layout && cfg_.fic_on_gpu;
     if (gpu_fic) {                 // behind the run's FIC decode, on its back-end stream
         const int want = (pcm_cb_ && nmp_ > 0 ? DABGPU_SUBCH_MP2 : 0) | (dg_cb_ && npk_ > 0 ? DABGPU_SUBCH_PACKET : 0) |
-                         (mot_cb_ && nmot_ > 0 ? DABGPU_SUBCH_MOT : 0) |
+                         (mot_cb_ && nmot_ > 0 ? DABGPU_SUBCH_MOT : 0) | (ip_cb_ && npk_ > 0 ? DABGPU_SUBCH_IP : 0) |
                          ((label_cb_ || pad_dg_cb_ || pad_obj_cb_) && npad_ > 0 ? DABGPU_SUBCH_PAD : 0);
         chk(dabgpu_pipe_fic(pipe_, (const uint8_t *)fic_.get(), (const uint8_t *)crc_.get(), want, (dabgpu_fic_event *)fce_.get(),
                             (dabgpu_fic_table *)fct_.get(), (dabgpu_fic_run *)fcr_.get()), "dabgpu_pipe_fic");
@@ -767,6 +767,61 @@ bool ensembleDecoder::step() {
             }
         }
     }
+    bool any_ip = false;
+    for (int s = 0; s < S; s++)
+        for (const dabgpu_subch &e : tab_[s]) any_ip |= (e.flags & DABGPU_SUBCH_PACKET) && (e.flags & DABGPU_SUBCH_IP);
+    if (NS && npk_ && any_ip && (ip_cb_ || ipq_cb_)) {
+        const size_t ne = (size_t)S * npk_;
+        if (!ipr_.size()) {                          // on first use; npk_, pk_slots_ and pk_arena_ are the constructor's for good
+            ip_arena_ = DABGPU_IP_ARENA_FOR(pk_slots_, pk_arena_);
+            ipb_.resize(ne * ip_arena_);
+            ipo_.resize(std::max<size_t>(1, ne * pk_slots_) * sizeof(dabgpu_ip_result));
+            ipr_.resize(ne * sizeof(dabgpu_ip_run));
+        }
+        chk(dabgpu_pipe_ip(pipe_, (uint8_t *)ipb_.get(), (dabgpu_ip_result *)ipo_.get(), (dabgpu_ip_run *)ipr_.get()), "dabgpu_pipe_ip");
+        chk(dabgpu_pipe_sync(pipe_), "dabgpu_pipe_sync");
+        // as for the groups: the run records, then per flagged (stream, slot) what the run delivered
+        std::vector<dabgpu_packet_run> prun(ne);
+        std::vector<dabgpu_ip_run> run(ne);
+        pkr_.download(prun.data(), prun.size() * sizeof(dabgpu_packet_run));
+        ipr_.download(run.data(), run.size() * sizeof(dabgpu_ip_run));
+        std::vector<dabgpu_ip_result> results;
+        std::vector<dabgpu_datagroup> groups;
+        std::vector<uint8_t> bytes;
+        for (int s = 0; s < S; s++) {
+            std::vector<int> slot;                   // packet slot j of a stream is its j-th flagged entry
+            for (int k = 0; k < (int)tab_[s].size(); k++)
+                if (tab_[s][k].flags & DABGPU_SUBCH_PACKET) slot.push_back(k);
+            for (int j = 0; j < (int)slot.size() && j < npk_; j++) {
+                const size_t e = (size_t)s * npk_ + j;
+                const int ng = std::min<int>(prun[e].n_groups, (int)pk_slots_);
+                if (!(tab_[s][slot[j]].flags & DABGPU_SUBCH_IP) || ng <= 0) continue;
+                // nothing reached process_ipVector: neither a datagram nor a show_ipErrors value to deliver
+                const int32_t *c = run[e].counts;
+                if (c[DABGPU_IP_DELIVERED] + c[DABGPU_IP_CHECKSUM] + c[DABGPU_IP_NOT_UDP] + c[DABGPU_IP_MALFORMED] == 0) continue;
+                results.resize(ng);
+                groups.resize(ng);
+                chk(dabgpu_memcpy_d2h(thread_context(), results.data(), (const dabgpu_ip_result *)ipo_.get() + e * pk_slots_,
+                                      results.size() * sizeof(dabgpu_ip_result)), "dabgpu_memcpy_d2h");
+                if (run[e].n_datagrams > 0)          // (the groups only for their CIFs)
+                    chk(dabgpu_memcpy_d2h(thread_context(), groups.data(), (const dabgpu_datagroup *)pkg_.get() + e * pk_slots_,
+                                          groups.size() * sizeof(dabgpu_datagroup)), "dabgpu_memcpy_d2h");
+                size_t used = 0;
+                for (const dabgpu_ip_result &r : results)
+                    if (r.status == DABGPU_IP_DELIVERED) used = std::max(used, (size_t)r.offset + r.nbytes);
+                bytes.resize(std::max<size_t>(1, used));
+                if (used)
+                    chk(dabgpu_memcpy_d2h(thread_context(), bytes.data(), (const uint8_t *)ipb_.get() + e * ip_arena_, used),
+                        "dabgpu_memcpy_d2h");
+                for (int g = 0; g < ng; g++) {
+                    const dabgpu_ip_result &r = results[g];
+                    if (r.quality >= 0 && ipq_cb_) ipq_cb_(s, slot[j], r.quality);
+                    if (r.status == DABGPU_IP_DELIVERED && ip_cb_)
+                        ip_cb_(s, slot[j], 4 * frames_done_[s] + groups[g].cif, bytes.data() + r.offset, r.nbytes);
+                }
+            }
+        }
+    }
     for (int s = 0; s < S; s++) {
         dabgpu_stream_state st;
         chk(dabgpu_pipe_state(pipe_, s, &st), "dabgpu_pipe_state");
@@ -781,7 +836,8 @@ bool ensembleDecoder::step() {
         } else {
             for (const fib_subch &e : fibs_[s].subchannels(nullptr, pcm_cb_ != nullptr && nmp_ > 0, dg_cb_ != nullptr && npk_ > 0,
                                                            mot_cb_ != nullptr && nmot_ > 0,
-                                                           (label_cb_ || pad_dg_cb_ || pad_obj_cb_) && npad_ > 0))
+                                                           (label_cb_ || pad_dg_cb_ || pad_obj_cb_) && npad_ > 0,
+                                                           ip_cb_ != nullptr && npk_ > 0))
                 now.push_back({e.startAddr, e.length, e.bitRate, e.protLevel, e.uepFlag, e.flags});
         }
         auto same = [](const std::vector<dabgpu_subch> &x, const std::vector<dabgpu_subch> &y) {

@@ -262,15 +262,21 @@ class mscDatagroup : public dabConcurrent {
 public:
     mscDatagroup(uint8_t DSCTy, int16_t packetAddress, int16_t fragmentSize, int16_t bitRate, int16_t uepFlag,
                  int16_t protLevel, uint8_t DGflag, int16_t FEC_scheme, packetAssembler::datagroup_cb cb,
-                 motAssembler::object_cb mot = nullptr);
+                 motAssembler::object_cb mot = nullptr, ipAssembler::datagram_cb datagram = nullptr,
+                 ipAssembler::quality_cb ip_quality = nullptr);
     int32_t process(int16_t *v, int16_t cnt) override;
     const packetAssembler &assembler() const { return pa_; }
     // DSCTy 60 (my_dataHandler = new mot_databuilder, msc-datagroup.cpp:82-84): every data group
     // also goes through the host motAssembler, whose slides and files go to the mot callback
     // (nullptr for any other DSCTy)
     const motAssembler *mot() const { return mot_.get(); }
+    // DSCTy 59 (my_dataHandler = new ip_dataHandler): every data group also goes through the host
+    // ipAssembler, whose UDP payloads go to the datagram callback (where the reference sends them
+    // to port 8888) and whose show_ipErrors values go to ip_quality (nullptr for any other DSCTy)
+    const ipAssembler *ip() const { return ip_.get(); }
 private:
     std::unique_ptr<motAssembler> mot_;        // before pa_, whose callback feeds it
+    std::unique_ptr<ipAssembler> ip_;          // likewise
     packetAssembler pa_;
 };
 
@@ -290,6 +296,8 @@ public:
         mp4Processor::au_cb aac;               // AAC access units (DAB+)
         packetAssembler::datagroup_cb datagroup;
         motAssembler::object_cb mot;           // slides and files of a DSCTy 60 data channel (the_picture, fopen)
+        ipAssembler::datagram_cb datagram;     // UDP payloads of a DSCTy 59 data channel (writeDatagram)
+        ipAssembler::quality_cb ip_quality;    // ... and its show_ipErrors values
     };
     mscHandler(DabParams *p, outputs out, uint8_t concurrent = 1);
     void process_mscBlock(int16_t *fbits, int16_t blkno);
@@ -565,6 +573,17 @@ public:
     using mot_object_cb = std::function<void(int stream, int64_t cif, int subch, const dabgpu_mot_object &o,
                                              const uint8_t *body)>;
     void on_mot_object(mot_object_cb f) { mot_cb_ = std::move(f); }
+    // UDP payloads of the packet-mode entries also flagged DABGPU_SUBCH_IP (dabgpu_pipe_ip, after the
+    // step's dabgpu_pipe_packet), where ip_dataHandler emits writeDatagram (ip-datahandler.cpp:
+    // 124-127), and the numbers it emits with show_ipErrors every 100 datagrams: in group order,
+    // a group's quality before its datagram, after the step's on_datagroup calls; cif is the CIF of
+    // the group that held the datagram.  With auto_layout, sub-channels with a DSCTy 59 packet-mode
+    // component are flagged DABGPU_SUBCH_PACKET | DABGPU_SUBCH_IP when on_datagram is set before the
+    // table is applied (config::max_packet says how many).
+    using datagram_cb = std::function<void(int stream, int subch, int64_t cif, const uint8_t *bytes, int n)>;
+    using ip_quality_cb = std::function<void(int stream, int subch, int value)>;
+    void on_datagram(datagram_cb f) { ip_cb_ = std::move(f); }
+    void on_ip_quality(ip_quality_cb f) { ipq_cb_ = std::move(f); }
     // DAB+ PAD of the entries flagged DABGPU_SUBCH_DABPLUS | DABGPU_SUBCH_PAD (dabgpu_pipe_pad after
     // the step's dabgpu_pipe_dabplus): the dynamic label where padHandler emits showLabel (the
     // record holds the bytes, pieces and charSet the reference hands to toQStringUsingCharset:
@@ -619,6 +638,10 @@ private:
     int nmot_ = 0;
     size_t mot_arena_ = 0;
     mot_object_cb mot_cb_;
+    devbuf ipb_, ipo_, ipr_;                          // the IP layer's arenas, result records, run records (first use)
+    size_t ip_arena_ = 0;
+    datagram_cb ip_cb_;
+    ip_quality_cb ipq_cb_;
     devbuf pdl_, pdg_, pdb_, pdr_;                    // the PAD layer's label and group records, arenas, run records
     devbuf pms_, pmr_, pmo_, pmb_, pmm_;              // on_pad_object: MOT states, packet-run and object records, bodies, runs
     int npad_ = 0, pad_slots_ = 0;

@@ -393,7 +393,7 @@ int fib_processor::bind(int8_t tmid, int32_t sid, int16_t compnr) {
 }
 
 std::vector<fib_subch> fib_processor::subchannels(std::vector<int> *ids, bool classic_audio, bool packet_data, bool mot,
-                                                  bool pad) const {
+                                                  bool pad, bool ip) const {
     std::vector<fib_subch> v;
     if (ids) ids->clear();
     for (int id = 0; id < 64; id++) {
@@ -412,10 +412,12 @@ std::vector<fib_subch> fib_processor::subchannels(std::vector<int> *ids, bool cl
             if (c.inUse && c.TMid == 3 && c.DSCTy != 0 && c.subchannelId == id && !(c.DSCTy == 5 && c.DGflag)) {
                 if (packet_data) e.flags |= 8;                          // DABGPU_SUBCH_PACKET
                 if (mot && c.DSCTy == 60) e.flags |= 8 | 16;            // ... | DABGPU_SUBCH_MOT
+                if (ip && c.DSCTy == 59) e.flags |= 8 | 64;             // ... | DABGPU_SUBCH_IP
             }
         if ((e.flags & 1) && pad) e.flags |= 32;                        // DABGPU_SUBCH_PAD
         if (e.flags & 1) e.flags &= ~4;                                 // (one layer per entry,
-        if (e.flags & 5) e.flags &= ~(8 | 16);                          //  the audio layers first)
+        if (e.flags & 5) e.flags &= ~(8 | 16 | 64);                     //  the audio layers first,
+        if (e.flags & 16) e.flags &= ~64;                               //  MOT before IP)
         v.push_back(e);
         if (ids) ids->push_back(id);
     }

@@ -150,9 +150,12 @@ public:
     // mot: flag DABGPU_SUBCH_PACKET | DABGPU_SUBCH_MOT (8 | 16) where such a component has DSCTy
     // 60 (MOT: what mscDatagroup hands to mot_databuilder, msc-datagroup.cpp:82-84), whether
     // packet_data is set or not.
+    // ip: flag DABGPU_SUBCH_PACKET | DABGPU_SUBCH_IP (8 | 64) where such a component has DSCTy 59
+    // (embedded IP: what mscDatagroup hands to ip_dataHandler), whether packet_data is set or not.
     std::vector<fib_subch> subchannels(std::vector<int> *ids = nullptr, bool classic_audio = false,
                                        bool packet_data = false, bool mot = false,
-                                       bool pad = false) const;   // pad: DAB+ entries also get DABGPU_SUBCH_PAD (32)
+                                       bool pad = false,          // pad: DAB+ entries also get DABGPU_SUBCH_PAD (32)
+                                       bool ip = false) const;
 
     // to and from the public record; import_db rebuilds the UTF-8 labels with label_text.
     // export_db writes everything but db->table.

@@ -312,6 +312,79 @@ void motAssembler::processSegment(element *h, const uint8_t *segment, int32_t n,
     if (cb_) cb_(o);
 }
 
+// ---- ipAssembler: ip_dataHandler (ip-datahandler.cpp:40-127) -----------------------------------
+ipAssembler::ipAssembler(datagram_cb on_datagram, quality_cb on_quality)
+    : onDatagram_(std::move(on_datagram)), onQuality_(std::move(on_quality)) {}
+
+ipAssembler::result ipAssembler::add_mscDatagroup(const std::vector<uint8_t> &bits) {
+    const int32_t nb = (int32_t)(bits.size() / 8);
+    std::vector<uint8_t> g((size_t)nb);
+    for (int32_t i = 0; i < nb; i++) {
+        uint32_t b = 0;
+        for (int k = 0; k < 8; k++) b = (b << 1) | (bits[(size_t)8 * i + k] & 1u);
+        g[(size_t)i] = (uint8_t)b;
+    }
+    return add_group(g.data(), nb);
+}
+
+ipAssembler::result ipAssembler::add_group(const uint8_t *group, int32_t nbytes) {
+    const result r = handle(group, nbytes);
+    counts_[r.status]++;
+    return r;
+}
+
+ipAssembler::result ipAssembler::handle(const uint8_t *g, int32_t nb) {
+    if (nb <= 0) return {NOT_ACCEPTED, -1, 0};
+    const bool ext = g[0] & 0x80, crcf = g[0] & 0x40, seg = g[0] & 0x20, ua = g[0] & 0x10;
+    if (crcf) {                                                           // check_CRC_bits (:54), in int32
+        if (nb < 2) return {NOT_ACCEPTED, -1, 0};
+        uint32_t reg = 0xFFFF;
+        for (int32_t i = 0; i < nb; i++) {
+            const uint32_t byte = i >= nb - 2 ? g[i] ^ 0xFFu : g[i];
+            for (int k = 7; k >= 0; k--) {
+                const uint32_t top = (reg >> 15) & 1u;
+                reg = (reg << 1) & 0xFFFFu;
+                if (top ^ ((byte >> k) & 1u)) reg ^= 0x1021u;
+            }
+        }
+        if (reg != 0) return {NOT_ACCEPTED, -1, 0};
+    }
+    // rule 1: bytes past the end read 0; the CRC field reads as check_CRC_bits has left it, inverted
+    const int32_t crc0 = crcf ? nb - 2 : nb;
+    auto B = [&](int64_t i) -> uint32_t { return i < 0 || i >= nb ? 0u : i >= crc0 ? g[i] ^ 0xFFu : g[i]; };
+    int64_t next = 2 + (ext ? 2 : 0);                                     // (:57-74)
+    if (seg) next += 2;
+    // (a length indicator inside the CRC field leaves next + 2 past the end whichever way it is
+    // read: ipLength is 0 then; it is read as stored, as the packet layer's data_offset does)
+    if (ua) next += 1 + (int64_t)(next < nb ? g[next] & 0xFu : 0u);
+    const int32_t ipLength = (int32_t)((B(next + 2) << 8) | B(next + 3));  // (:79)
+    if (!(ipLength < nb)) return {TOO_LONG, -1, ipLength};                // (:80)
+    auto D = [&](int32_t i) -> uint32_t { return i < ipLength ? B(next + i) : 0u; };   // ipVector; rule 3
+    if (ipLength == 0 || (int8_t)D(0) >> 4 != 4) return {NOT_V4, -1, ipLength};        // rule 2; (:85) a signed char
+    const int32_t headerSize = (int32_t)(D(0) & 0xFu);
+    int quality = -1;
+    if (++handledPackets_ >= 100) {                                       // (:100-104)
+        quality = (int16_t)(100 - crcErrors_);
+        crcErrors_ = 0;
+        handledPackets_ = 0;
+        if (onQuality_) onQuality_(quality);
+    }
+    uint32_t checkSum = 0;
+    for (int32_t i = 0; i < 2 * headerSize; i++) checkSum += (D(2 * i) << 8) | D(2 * i + 1);
+    checkSum = (checkSum >> 16) + (checkSum & 0xFFFFu);                   // one fold (:107)
+    if ((~checkSum & 0xFFFFu) != 0) {
+        crcErrors_++;
+        return {CHECKSUM, quality, ipLength};
+    }
+    if (D(9) != 17) return {NOT_UDP, quality, ipLength};                  // (:113-119)
+    const int32_t n = ipLength - 4 * headerSize - 8;                      // (:124-127)
+    if (n < 0) return {MALFORMED, quality, ipLength};
+    std::vector<uint8_t> payload((size_t)n);
+    for (int32_t i = 0; i < n; i++) payload[(size_t)i] = (uint8_t)D(4 * headerSize + 8 + i);
+    if (onDatagram_) onDatagram_(payload.data(), n);
+    return {DELIVERED, quality, ipLength};
+}
+
 // ---- padAssembler: padHandler (pad-handler.cpp) ------------------------------------------------
 padAssembler::padAssembler(label_cb on_label, datagroup_cb on_group)
     : onLabel_(std::move(on_label)), onGroup_(std::move(on_group)), buffer_(8192, 0) {}

@@ -1,10 +1,10 @@
 // msc_consumers.h -- what the reference does with the decoded MSC bits of a
 // subchannel, minus the codecs: the plug-in interfaces (dabVirtual, dabProcessor),
 // the MPEG-1/2 layer II frame synchroniser of mp2Processor (mp2processor.cpp:572-629),
-// the packet-mode data-group assembly of mscDatagroup (msc-datagroup.cpp:221-339) and
-// motHandler's header mode (mot-data.cpp:679-728).
+// the packet-mode data-group assembly of mscDatagroup (msc-datagroup.cpp:221-339),
+// motHandler's header mode (mot-data.cpp:679-728) and ip_dataHandler (ip-datahandler.cpp).
 // Host code (a few bit operations per decoded bit, after the GPU's Viterbi): no Qt,
-// no kjmp2 / faad / IP handlers -- complete frames, data groups and MOT objects go to
+// no kjmp2 / faad / sockets -- complete frames, data groups, MOT objects and UDP payloads go to
 // callbacks instead.  Same state machines and quirks as the reference.
 #pragma once
 #include <atomic>
@@ -143,6 +143,41 @@ private:
     int32_t ordernumber_ = 1;
     bool oldSlide_ = false;
     int32_t objects_ = 0, malformed_ = 0, badSegments_ = 0, otherTypes_ = 0;
+};
+
+// ip_dataHandler (ip-datahandler.cpp:40-127, show_crcErrors on): MSC data groups in, the UDP payload
+// of every IPv4 datagram with a good header checksum out through a callback where the reference
+// emits writeDatagram, and the number show_ipErrors emits every 100 datagrams through another.  The
+// same function, byte for byte, as the GPU's IP layer (dabgpu_ip_groups in include/dabgpu.h, whose
+// rules 1-5 for what the reference leaves undefined hold here too: bytes past a group read 0 and a
+// datagram over the group's own CRC bytes reads them complemented, ipLength 0 is no IPv4, header
+// bytes past ipLength read 0 and a negative payload length is counted as malformed, lengths are
+// int32; there is no arena here, so rule 6 has no counterpart).
+class ipAssembler {
+public:
+    enum { DELIVERED = 0, NOT_ACCEPTED, TOO_LONG, NOT_V4, CHECKSUM, NOT_UDP, MALFORMED, NSTATUS };
+    struct result {
+        int status;                     // what became of the group
+        int quality;                    // what show_ipErrors emitted inside the call, else -1
+        int32_t ip_bytes;               // ipLength, 0 when the group never got that far
+    };
+    using datagram_cb = std::function<void(const uint8_t *payload, int32_t nbytes)>;
+    using quality_cb = std::function<void(int value)>;
+    explicit ipAssembler(datagram_cb on_datagram, quality_cb on_quality = nullptr);
+    // one MSC data group, one bit per byte, as packetAssembler delivers it
+    result add_mscDatagroup(const std::vector<uint8_t> &bits);
+    // ... as bytes, its CRC field as received
+    result add_group(const uint8_t *group, int32_t nbytes);
+    int32_t handledPackets() const { return handledPackets_; }
+    int32_t crcErrors() const { return crcErrors_; }
+    void setCounters(int32_t handledPackets, int32_t crcErrors) { handledPackets_ = handledPackets; crcErrors_ = crcErrors; }
+    int32_t count(int status) const { return counts_[status]; }
+private:
+    result handle(const uint8_t *group, int32_t nbytes);
+    datagram_cb onDatagram_;
+    quality_cb onQuality_;
+    int32_t handledPackets_ = 0, crcErrors_ = 0;
+    int32_t counts_[NSTATUS] = {};
 };
 
 // padHandler (pad-handler.cpp) for one DAB+ stream: the PAD of every good AU whose first

@@ -450,6 +450,44 @@ void make_pad_programme(uint64_t seed, int sub, std::vector<std::vector<uint8_t>
             out.push_back(xpad({{13, 7}}, {std::vector<uint8_t>(G.begin() + pos, G.begin() + std::min(n, pos + 48))}));
     }
 }
+// DABSYNTH_IP: 44 MSC data groups sent round and round, group k holding one IPv4 datagram with a
+// UDP header and 8..199 seeded data bytes: a good header checksum unless k % 7 == 6 (corrupted),
+// protocol 17 unless k % 11 == 10 (6), a header of 6..8 words (options) when k % 5 == 3 and of 5
+// otherwise, the group with the CRC flag unless k % 3 == 0; every datagram lies inside its group.
+constexpr int IP_CAROUSEL = 44;
+void make_ip_carousel(uint64_t seed, int sub, std::vector<std::vector<uint8_t>> &out) {
+    Rng rng(seed ^ (0x495034ull << 20) ^ (uint64_t)sub);
+    for (int k = 0; k < IP_CAROUSEL; k++) {
+        const int hs = k % 5 == 3 ? 6 + (int)(rng.next() % 3) : 5, nd = 8 + (int)(rng.next() % 192);
+        const int total = 4 * hs + 8 + nd;
+        std::vector<uint8_t> d((size_t)total, 0);
+        d[0] = (uint8_t)(0x40 | hs);
+        d[2] = (uint8_t)(total >> 8), d[3] = (uint8_t)(total & 0xFF);
+        d[4] = (uint8_t)(k >> 8), d[5] = (uint8_t)k;
+        d[8] = 64, d[9] = k % 11 == 10 ? 6 : 17;
+        const uint8_t addr[8] = {10, 0, (uint8_t)sub, 1, 239, 1, 2, (uint8_t)k};
+        std::memcpy(&d[12], addr, 8);
+        for (int i = 20; i < 4 * hs; i++) d[i] = (uint8_t)rng.next();
+        uint32_t sum = 0;
+        for (int i = 0; i < 2 * hs; i++) sum += (uint32_t)((d[2 * i] << 8) | d[2 * i + 1]);
+        while (sum >> 16) sum = (sum >> 16) + (sum & 0xFFFF);
+        const uint16_t c = (uint16_t)~sum;
+        d[10] = (uint8_t)(c >> 8), d[11] = (uint8_t)(c & 0xFF);
+        if (k % 7 == 6) d[11] ^= 0x5A;
+        uint8_t *u = &d[4 * hs];
+        u[0] = 0x22, u[1] = 0xB8, u[2] = 0x22, u[3] = 0xB8, u[4] = (uint8_t)((8 + nd) >> 8), u[5] = (uint8_t)((8 + nd) & 0xFF);
+        for (int i = 0; i < nd; i++) u[8 + i] = (uint8_t)rng.next();
+        const bool crcf = k % 3 != 0;
+        std::vector<uint8_t> g = {(uint8_t)(crcf ? 0x40 : 0x00), 0};
+        g.insert(g.end(), d.begin(), d.end());
+        if (crcf) {
+            const uint16_t gc = (uint16_t)~crc_ccitt(g.data(), (int)g.size());
+            g.push_back((uint8_t)(gc >> 8));
+            g.push_back((uint8_t)(gc & 0xFF));
+        }
+        out.push_back(g);
+    }
+}
 void make_packet_cif(Rng &rng, PacketState &st, int bitRate, int addr, uint8_t *info) {
     const int nbytes = 3 * bitRate;
     std::vector<uint8_t> out(nbytes, 0);
@@ -589,13 +627,13 @@ static void make_fig_fib(const dabsynth_cfg *cfg, int64_t n, uint8_t *fib) {
         }
         w.put(0, 3), w.put(6, 5), w.put(0, 3), w.put(2, 5);
         w.put(0xC000 + i, 16), w.put(0, 1), w.put(0, 3), w.put(1, 4);
-        if (!sc.dabplus && (sc.content == DABSYNTH_PACKET || sc.content == DABSYNTH_MOT)) {
+        if (!sc.dabplus && (sc.content == DABSYNTH_PACKET || sc.content == DABSYNTH_MOT || sc.content == DABSYNTH_IP)) {
             // packet-mode component (TMid 3, SCId 0x400 + i), then FIG 0/3: SCId -> DG flag 0,
-            // DSCTy 60 (MOT), sub-channel i, packet address 0x100 + i
+            // DSCTy 60 (MOT) or 59 (embedded IP, DABSYNTH_IP), sub-channel i, packet address 0x100 + i
             w.put(3, 2), w.put(0x400 + i, 12), w.put(1, 1), w.put(0, 1);
             w.put(0, 3), w.put(6, 5), w.put(0, 3), w.put(3, 5);
             w.put(0x400 + i, 12), w.put(0, 3), w.put(0, 1), w.put(0, 1), w.put(0, 1);
-            w.put(60, 6), w.put(i, 6), w.put(0x100 + i, 10);
+            w.put(sc.content == DABSYNTH_IP ? 59 : 60, 6), w.put(i, 6), w.put(0x100 + i, 10);
         } else {
             w.put(0, 2), w.put(sc.dabplus ? 63 : 0, 6), w.put(i, 6), w.put(1, 1), w.put(0, 1);
         }
@@ -618,6 +656,19 @@ void dabsynth_make_fib(uint64_t *st, uint8_t *fib) {
 }
 
 void dabsynth_rs_encode(const uint8_t *data, uint8_t *cw) { rs_encode(data, cw); }
+
+int dabsynth_ip_carousel(uint64_t seed, int sub, uint8_t *bytes, int max_bytes, int32_t *lens, int max_groups) {
+    std::vector<std::vector<uint8_t>> groups;
+    make_ip_carousel(seed, sub, groups);
+    int pos = 0;
+    for (size_t k = 0; k < groups.size(); k++) {
+        if ((int)k >= max_groups || pos + (int)groups[k].size() > max_bytes) return -1;
+        std::memcpy(bytes + pos, groups[k].data(), groups[k].size());
+        lens[k] = (int32_t)groups[k].size();
+        pos += (int)groups[k].size();
+    }
+    return (int)groups.size();
+}
 
 int64_t dabsynth_stream_len(const dabsynth_cfg *cfg) {
     return (int64_t)(TF - cfg->pre_offset) + (int64_t)cfg->n_frames * TF + TNULL;
@@ -647,8 +698,10 @@ static int gen_core(const dabsynth_cfg *cfg, uint64_t seed, int P, float *iq, ui
         const dabsynth_subch &sc = cfg->subch[s];
         int nb = 24 * sc.bitRate;
         if (cyc && sc.dabplus && NC % 5) return -3;      // superframes must tile the period
-        if (cyc && !sc.dabplus && (sc.content == DABSYNTH_PACKET || sc.content == DABSYNTH_MOT)) return -4;   // groups do not wrap (dabsynth.h)
+        if (cyc && !sc.dabplus && (sc.content == DABSYNTH_PACKET || sc.content == DABSYNTH_MOT || sc.content == DABSYNTH_IP))
+            return -4;                                   // groups do not wrap (dabsynth.h)
         if (!sc.dabplus && sc.content == DABSYNTH_MOT) make_mot_carousel(seed, s, pst[s].carousel);
+        if (!sc.dabplus && sc.content == DABSYNTH_IP) make_ip_carousel(seed, s, pst[s].carousel);
         PadProgramme prog;
         if (sc.dabplus && sc.content == DABSYNTH_PAD) make_pad_programme(seed, s, prog.pads);
         frag_len[s] = sc.length * 64;
@@ -713,7 +766,7 @@ static int gen_core(const dabsynth_cfg *cfg, uint64_t seed, int P, float *iq, ui
                 }
             } else if (sc.content == DABSYNTH_MP2) {
                 make_mp2_frame(rng, sc.bitRate, info.data());
-            } else if (sc.content == DABSYNTH_PACKET || sc.content == DABSYNTH_MOT) {
+            } else if (sc.content == DABSYNTH_PACKET || sc.content == DABSYNTH_MOT || sc.content == DABSYNTH_IP) {
                 make_packet_cif(rng, pst[s], sc.bitRate, 0x100 + s, info.data());
             } else {
                 for (int i = 0; i < nb; i++) info[i] = rng.bit();

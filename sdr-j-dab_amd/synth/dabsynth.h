@@ -37,6 +37,11 @@ typedef struct {
                             header mode (four objects, transport ids 0x1000 + 16 * subchannel + k:
                             header groups, 100-byte body segments, every object sent twice, the
                             last with header and body in one segment);
+                            DABSYNTH_IP: the same, announced as DSCTy 59, the groups being 44 seeded
+                            IPv4/UDP datagrams sent round and round, one a group (8..199 data bytes;
+                            every seventh with a corrupted header checksum, every eleventh with
+                            protocol 6, every fifth with 4..12 option bytes, two in three groups with
+                            the CRC flag), each inside its group;
                             with dabplus: 0 every superframe dacRate 0 / SBR 0 (4 AUs),
                             DABSYNTH_AU_MIX the superframes cycle through the four (dacRate, SBR)
                             layouts of mp4processor.cpp:163-195 (4, 2, 6, 3 AUs); DABSYNTH_PAD: layout
@@ -52,6 +57,7 @@ typedef struct {
 #define DABSYNTH_AU_MIX 4
 #define DABSYNTH_MOT 5
 #define DABSYNTH_PAD 6
+#define DABSYNTH_IP 7
 
 typedef struct {
     int32_t n_frames;    /* frames after the pre-roll */
@@ -93,7 +99,7 @@ int dabsynth_generate_many(const dabsynth_cfg *cfg, uint64_t seed0, int n_ens, i
  * at TF - pre_offset) is iq_stream[p] = iq[(p - (TF - pre_offset)) mod (P * TF)].
  * Truth: fic_bits [P][4][768] by frame; msc_bits [4P][n_subch][24*max_bitRate] by
  * receiver CIF n mod 4P (receiver CIF n decodes encoder CIF (n - 15) mod 4P).
- * DABSYNTH_PACKET subchannels are refused (-4): a data group in flight and the packet
+ * DABSYNTH_PACKET, DABSYNTH_MOT and DABSYNTH_IP subchannels are refused (-4): a data group in flight and the packet
  * continuity counter would not wrap at the seam. */
 int dabsynth_generate_period(const dabsynth_cfg *cfg, uint64_t seed, int period, float *iq,
                              uint8_t *fic_bits, uint8_t *msc_bits);
@@ -107,6 +113,10 @@ int  dabsynth_puncture_msc(int uep, int bitRate, int protLevel, const uint8_t *m
 void dabsynth_puncture_fic(const uint8_t *mother /*[3096]*/, uint8_t *out /*[2304]*/);
 void dabsynth_make_fib(uint64_t *rng_state, uint8_t *fib /*[256]*/);
 void dabsynth_rs_encode(const uint8_t *data /*[110]*/, uint8_t *cw /*[120]*/);
+/* the data groups a DABSYNTH_IP subchannel `sub` of an ensemble made with `seed` sends round and
+ * round: back to back into bytes, their lengths into lens; returns their number, -1 when they do
+ * not fit */
+int dabsynth_ip_carousel(uint64_t seed, int sub, uint8_t *bytes, int max_bytes, int32_t *lens, int max_groups);
 
 #ifdef __cplusplus
 }
