@@ -230,6 +230,9 @@ typedef struct {
 #define DABGPU_SUBCH_PAD     32  /* feed the DAB+ entry's good AUs to the PAD layer (dabgpu_pipe_pad); only together
                                     with DABGPU_SUBCH_DABPLUS (DABGPU_E_ARG otherwise).  PAD slot j of a stream is
                                     its j-th entry so flagged. */
+#define DABGPU_SUBCH_AUDIO   128 /* feed the layer II entry's decoded frames to the audio output layer
+                                    (dabgpu_pipe_audio); only together with DABGPU_SUBCH_MP2 (DABGPU_E_ARG
+                                    otherwise).  Audio slot j of a stream is its j-th entry so flagged. */
 /* One showLabel emission of padHandler::dynamicLabel (pad-handler.cpp:231-267).  text holds the
  * bytes the reference passed to toQStringUsingCharset, piece after piece, since the last clear,
  * unconverted; charset is charSet at the emission; piece_len keeps the boundaries of those
@@ -283,6 +286,9 @@ typedef struct {
 /* a decoder's carried state (the last 15 V vectors of both channels), opaque */
 #define DABGPU_MP2_STATE_BYTES 3840
 
+/* an audioSink's carried state (the last input pairs of its three interpolators), opaque */
+#define DABGPU_AUDIO_STATE_BYTES 32
+
 /* One CIF of one DAB+ subchannel through mp4Processor::addtoFrame
  * (mp4processor.cpp:107-145) and, when five blocks are buffered and the fire
  * code holds, processSuperframe (:146-292). */
@@ -322,12 +328,16 @@ typedef struct {
  *   DABGPU_TABLE_OSC     float2[2048000] oscillatorTable (ofdm-processor.cpp:79-81)
  *   DABGPU_TABLE_NCO     double2[384] the factor tables the kernels rebuild
  *                        oscillatorTable from (128 e^{2pi i a/128}, 125 e^{2pi i b/16000},
- *                        128 e^{2pi i c/2048000}, 3 zero) */
+ *                        128 e^{2pi i c/2048000}, 3 zero)
+ *   DABGPU_TABLE_AUDIO_FIR float[3][5] the kernels of audioSink's LowPassFIR (5, 16000, 48000),
+ *                        (5, 24000, 48000) and (5, 32000, 96000), in this order
+ *                        (fir-filters.cpp:35-69) */
 #define DABGPU_TABLE_PRS    1
 #define DABGPU_TABLE_MAPPER 2
 #define DABGPU_TABLE_REFARG 3
 #define DABGPU_TABLE_OSC    4
 #define DABGPU_TABLE_NCO    5
+#define DABGPU_TABLE_AUDIO_FIR 6
 int dabgpu_host_table(int which, void *out_h, size_t bytes);
 /* The depuncturing profile the decoder uses for a subchannel (deconvolve.cpp:142-366;
  * uep_deconvolve's unknown-profile fallback to table row 1, :148-151): decoded bits,
@@ -506,6 +516,30 @@ int dabgpu_rs_decode(dabgpu_ctx *ctx, const uint8_t *in_d, int n, uint8_t *out_d
  * Asynchronous on the context stream. */
 int dabgpu_mp2_decode(dabgpu_ctx *ctx, const uint8_t *frames_d, int64_t frame_stride, int n_chains, int chain_len,
                       void *state_d, int16_t *pcm_d, int32_t *ret_d);
+
+/* audioSink::audioOut batched (audiosink.cpp:235-360 over LowPassFIR::Pass, fir-filters.cpp:78-92;
+ * the counterpart of dabgpu_mp2_decode): n_chains independent sinks, each taking chain_len calls
+ * audioOut (V, amount, rate) in order.  What a call delivers is what it puts into _O_Buffer when
+ * that never fills: one 48 kHz float stereo signal.
+ *   pcm_d      int16 (left, right) pairs: call j of chain i reads amounts_h[i*chain_len + j] pairs
+ *              from pcm_d + (i*chain_len + j) * pcm_stride * 2 (pcm_stride in pairs)
+ *   rates_h    int32 [n_chains][chain_len] (host): 16000, 24000 and 32000 go through their
+ *              interpolator (x3, x2, x3 and every second result), every other rate is scaled only
+ *              (the reference's default: label); 0 is "no call" and leaves all state as it was
+ *   amounts_h  int32 [n_chains][chain_len] (host), each in 0 .. max_amount; an odd amount at
+ *              32000 is DABGPU_E_ARG (the reference then puts one float it never wrote)
+ *   state_d    DABGPU_AUDIO_STATE_BYTES per chain, 4-byte aligned, opaque, all-zero for a new sink,
+ *              updated in place; a call at one rate leaves the other rates' filters as they were
+ *   samples_d  float [n_chains][chain_len][max_amount*3][2] (8-byte aligned); rows of calls that
+ *              deliver nothing are left untouched
+ *   n_out_d    int32 [n_chains][chain_len]: pairs written (amount, 2*amount, 3*amount or
+ *              3*amount/2; 0 for rate 0)
+ * Each sample is (float)((double)(float)V / 32767.0); every product and sum of a filter is rounded
+ * to fp32 on its own, in the reference's order (no fma).  Not modelled: the sink's back-pressure
+ * (amount cut to the ring's room) and dumpFile.  Asynchronous on the context stream (rates_h and
+ * amounts_h are read before the call returns). */
+int dabgpu_audio_out(dabgpu_ctx *ctx, const int16_t *pcm_d, int64_t pcm_stride, int n_chains, int chain_len, int max_amount,
+                     const int32_t *rates_h, const int32_t *amounts_h, void *state_d, float *samples_d, int32_t *n_out_d);
 
 /* motHandler::process_mscGroup in header mode (mot-data.cpp:679-728) batched: n_slots
  * independent motHandlers, each taking the groups of one (stream, packet slot) of a
@@ -879,7 +913,8 @@ int dabgpu_pipe_create_caps(dabgpu_ctx *ctx, const dabgpu_pipe_cfg *cfg, const d
  * packet-mode entries than dabgpu_pipe_packet_caps allows, more MOT entries than
  * dabgpu_pipe_mot_caps allows, an entry flagged DABGPU_SUBCH_MOT without DABGPU_SUBCH_PACKET, more
  * PAD entries than dabgpu_pipe_pad_caps allows, an entry flagged DABGPU_SUBCH_PAD without
- * DABGPU_SUBCH_DABPLUS or an entry flagged for two layers;
+ * DABGPU_SUBCH_DABPLUS, more audio output entries than dabgpu_pipe_audio_caps allows, an entry
+ * flagged DABGPU_SUBCH_AUDIO without DABGPU_SUBCH_MP2 or an entry flagged for two layers;
  * DABGPU_E_UNSUP for a packet-mode bitRate that is no multiple of 8; on any error the table
  * is unchanged.  (A packet-mode entry that is not unchanged is a new mscDatagroup, and a new
  * motHandler when it is flagged DABGPU_SUBCH_MOT; an unchanged one keeps both.)
@@ -952,6 +987,25 @@ int dabgpu_pipe_dabplus(dabgpu_pipe *p, uint8_t *sf_bytes_d, int32_t sf_stride, 
  * DAB+ layer it reads msc_bits_d back: not for a run whose msc_bits_d is host memory.
  * DABGPU_E_STATE for a pipeline with max_mp2 == 0 or without a run to consume. */
 int dabgpu_pipe_mp2(dabgpu_pipe *p, int16_t *pcm_d, dabgpu_mp2_info *info_d);
+/* Audio output layer for the frames of the run's dabgpu_pipe_mp2 call (call once per run, after
+ * it): for every entry flagged DABGPU_SUBCH_MP2 | DABGPU_SUBCH_AUDIO, audio slot j of a stream
+ * being its j-th such entry, every frame with info.status == 2 goes through audioSink::audioOut
+ * (pcm, 1152, info.sample_rate) in CIF order (mp2processor.cpp:584-588; see dabgpu_audio_out for
+ * the arithmetic).  pcm_d and info_d are those of that call (DABGPU_E_ARG otherwise); they are read
+ * and never written.  The sinks are carried across runs; dabgpu_pipe_set_subch keeps the one of an
+ * unchanged entry and gives every other entry a new one, together with its mp2Processor.
+ * Outputs (device):
+ *   samples_d float [n_streams][4*n_frames][max_audio][2304][2], written where n_out > 0
+ *   n_out_d   int32 [n_streams][4*n_frames][max_audio]: 0, 1152 (a 48 kHz frame) or 2304 (24 kHz)
+ * Runs on the run's back-end stream behind the layer II layer.  DABGPU_E_STATE without a layer
+ * (max_audio == 0), without a dabgpu_pipe_mp2 call for the run, or on a second call. */
+int dabgpu_pipe_audio(dabgpu_pipe *p, const int16_t *pcm_d, const dabgpu_mp2_info *info_d, float *samples_d, int32_t *n_out_d);
+/* Size the audio output layer: max_audio slots per stream (<= max_mp2), as dabgpu_pipe_pad_caps
+ * sizes the PAD layer.  Both create calls start with the number of flagged entries of their
+ * table; with max_audio == 0 nothing is allocated or launched.  Between runs; waits for
+ * everything enqueued.  The sinks of the slots both sizes hold are kept.  DABGPU_E_ARG for a
+ * negative value, max_audio > max_mp2 or fewer slots than an applied table flags. */
+int dabgpu_pipe_audio_caps(dabgpu_pipe *p, int max_audio);
 /* Packet-mode data layer for the CIFs of the last dabgpu_pipe_run (call once per run, after
  * it, in any order with dabgpu_pipe_dabplus / dabgpu_pipe_mp2): for every entry flagged
  * DABGPU_SUBCH_PACKET, mscDatagroup::handlePackets + handlePacket (msc-datagroup.cpp:221-319,

@@ -381,6 +381,30 @@ struct FibJob {
     dabgpu_fic_run *run;            // [n_slots]
 };
 
+// audio output layer (k_audio.hip)
+struct AudioState {                 // an audioSink's interpolators, zero for a new sink
+    uint32_t hist[3][2];            // per filter (16000, 24000, 32000): its last and last-but-one input pair, int16 (left | right << 16)
+    uint32_t reserved[2];
+};
+static_assert(sizeof(AudioState) == DABGPU_AUDIO_STATE_BYTES, "dabgpu.h");
+// n_chains sinks, chain_len calls each.  Chain c = (s, a) = (c / cdiv, c % cdiv); its call j
+//   reads amount pairs at pcm + (s * in_a + j * in_c + m) * in_pairs * 2, m = src ? src[c] - s * in_c : 0
+//   (src[c] < 0: the chain has no calls), and its rate and amount from rates / amounts[c * chain_len + j],
+//   or, with info, from info[s * in_a + j * in_c + m]: status 2 -> (sample_rate, fixed_amount), else no call;
+//   writes row r = s * out_a + j * out_c + a of samples ([out_pairs][2] floats each) and of n_out.
+struct AudioJob {
+    const int16_t *pcm;
+    int64_t in_pairs, in_a, in_c;
+    int32_t n_chains, chain_len, cdiv, fixed_amount;
+    const int32_t *src;             // optional [n_chains]
+    const int32_t *rates, *amounts; // [n_chains][chain_len], or
+    const dabgpu_mp2_info *info;
+    AudioState *state;              // [n_chains], updated in place by the second launch
+    const float *coef;              // [3][5] (DABGPU_TABLE_AUDIO_FIR), device
+    float *samples;
+    int32_t *n_out;
+    int64_t out_pairs, out_a, out_c;
+};
 
 // iq: samples in format fmt (DABGPU_IQ_*); frame descriptors count samples
 hipError_t launch_prs_sync(hipStream_t st, const void *iq, int fmt, const dabgpu_frame *fr, int n, const OfdmTables &T,
@@ -420,6 +444,7 @@ hipError_t launch_packet(hipStream_t st, const PkJob &job);
 hipError_t launch_mot(hipStream_t st, const MotJob &job);
 hipError_t launch_ip(hipStream_t st, const IpJob &job);
 hipError_t launch_pad(hipStream_t st, const PadJob &job);
+hipError_t launch_audio(hipStream_t st, const AudioJob &job);
 hipError_t launch_fib(hipStream_t st, const FibJob &job);
 hipError_t launch_fic_clear(hipStream_t st, dabgpu_fic_db *db, int n_slots);
 

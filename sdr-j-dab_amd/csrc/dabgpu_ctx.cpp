@@ -9,6 +9,7 @@
 #include <memory>
 #include <algorithm>
 #include "dabgpu_internal.h"
+#include "../host/audio_fir.h"
 #include "stage_layout.h"
 #include "dab_tables.h"
 
@@ -304,6 +305,21 @@ std::vector<uint8_t> dab::make_inv(const Profile &P) {
     return inv;
 }
 
+// audioSink's three interpolation kernels (host/audio_fir.h)
+const std::vector<float> &dab::audio_host_fir() {
+    static const std::vector<float> tab = [] {
+        std::vector<float> k(15);
+        dabgpu::audio_fir_kernels(k.data());
+        return k;
+    }();
+    return tab;
+}
+int dab::audio_tables(dabgpu_ctx *c, const float **out) {
+    if (!c->audiotab) HIPCHK(c->audiotab.put(audio_host_fir()));
+    *out = c->audiotab.ptr;
+    return 0;
+}
+
 // ----------------------------------------------------------------- context
 int dab::scratch(dabgpu_ctx *c, int slot, size_t bytes, void **p) {
     DevBuf<uint8_t> &b = c->scratch[slot];
@@ -383,6 +399,7 @@ int dabgpu_host_table(int which, void *out, size_t bytes) {
     case DABGPU_TABLE_REFARG: src = t.refarg.data(); n = t.refarg.size() * sizeof(float); break;
     case DABGPU_TABLE_NCO: src = t.nco.data(); n = t.nco.size() * sizeof(double2); break;
     case DABGPU_TABLE_OSC: src = t.osc.data(); n = t.osc.size() * sizeof(float2); break;
+    case DABGPU_TABLE_AUDIO_FIR: src = audio_host_fir().data(); n = audio_host_fir().size() * sizeof(float); break;
     default: return fail(DABGPU_E_ARG, "unknown table %d", which);
     }
     if (!out || bytes < n) return fail(DABGPU_E_ARG, "table %d needs %zu bytes", which, n);
@@ -747,6 +764,50 @@ int dabgpu_mp2_decode(dabgpu_ctx *c, const uint8_t *frames, int64_t frame_stride
     J.idx_c = 1;
     if (int rc = mp2_tables(c, &J.tabs)) return rc;
     HIPCHK(launch_mp2_decode(c->stream, J));
+    return 0;
+}
+
+int dabgpu_audio_out(dabgpu_ctx *c, const int16_t *pcm, int64_t pcm_stride, int n_chains, int chain_len, int max_amount,
+                     const int32_t *rates, const int32_t *amounts, void *state, float *samples, int32_t *n_out) {
+    if (!c || !pcm || !rates || !amounts || !state || !samples || !n_out || n_chains < 0 || chain_len < 0 || max_amount < 0)
+        return fail(DABGPU_E_ARG, "bad args");
+    if (pcm_stride < max_amount) return fail(DABGPU_E_ARG, "pcm_stride %lld < max_amount %d", (long long)pcm_stride, max_amount);
+    if (max_amount > 0x7FFFFFFF / 3) return fail(DABGPU_E_ARG, "max_amount %d", max_amount);
+    if (((uintptr_t)pcm & 3) || ((uintptr_t)state & 3) || ((uintptr_t)samples & 7))
+        return fail(DABGPU_E_ARG, "pcm_d and state_d must be 4-byte aligned, samples_d 8-byte aligned");
+    const int64_t ncall = (int64_t)n_chains * chain_len;
+    if (ncall > 0x7FFFFFFF) return fail(DABGPU_E_ARG, "%lld calls in one batch", (long long)ncall);
+    for (int64_t i = 0; i < ncall; i++) {
+        if (rates[i] == 0) continue;
+        if (amounts[i] < 0 || amounts[i] > max_amount)
+            return fail(DABGPU_E_ARG, "call %lld: amount %d outside 0 .. %d", (long long)i, amounts[i], max_amount);
+        if (rates[i] == 32000 && (amounts[i] & 1))
+            return fail(DABGPU_E_ARG, "call %lld: odd amount %d at 32000 Hz", (long long)i, amounts[i]);
+    }
+    if (!ncall) return 0;
+    void *desc = nullptr;
+    if (int rc = scratch(c, SC_AUDIO, 2 * sizeof(int32_t) * (size_t)ncall, &desc)) return rc;
+    HIPCHK(hipMemcpyAsync(desc, rates, sizeof(int32_t) * ncall, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync((int32_t *)desc + ncall, amounts, sizeof(int32_t) * ncall, hipMemcpyHostToDevice, c->stream));
+    AudioJob J;
+    memset(&J, 0, sizeof J);
+    J.pcm = pcm;
+    J.in_pairs = pcm_stride;
+    J.in_a = chain_len;
+    J.in_c = 1;
+    J.n_chains = n_chains;
+    J.chain_len = chain_len;
+    J.cdiv = 1;
+    J.rates = (const int32_t *)desc;
+    J.amounts = (const int32_t *)desc + ncall;
+    J.state = (AudioState *)state;
+    J.samples = samples;
+    J.n_out = n_out;
+    J.out_pairs = 3 * (int64_t)max_amount;
+    J.out_a = chain_len;
+    J.out_c = 1;
+    if (int rc = audio_tables(c, &J.coef)) return rc;
+    HIPCHK(launch_audio(c->stream, J));
     return 0;
 }
 

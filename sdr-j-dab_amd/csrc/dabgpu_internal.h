@@ -120,10 +120,11 @@ struct dabgpu_ctx {
     dab::DevBuf<uint8_t> dptab;    // DAB+ tables (HostTables::dptab)
     dab::DevBuf<uint8_t> fic_inv;  // the FIC profile's inverse depuncturing table (make_inv)
     dab::DevBuf<uint8_t> mp2tab;   // layer II tables (Mp2Tabs, mp2_host_tables)
+    dab::DevBuf<float> audiotab;   // audioSink's filter kernels (audio_host_fir)
     dab::DevBuf<int32_t> err;      // device error word (KERR_* bits)
     dab::PinBuf<int32_t> h_err;    // its pinned host copy (read after every synchronising pass)
     dab::OfdmTables T{};
-    dab::DevBuf<uint8_t> scratch[9];   // growable scratch (dab::scratch)
+    dab::DevBuf<uint8_t> scratch[10];   // growable scratch (dab::scratch)
     dab::Stream stream;
     ~dabgpu_ctx() {
         (void)hipSetDevice(device);
@@ -144,7 +145,8 @@ int fail(int code, const char *fmt, ...);
                         hipGetErrorString(e_), __FILE__, __LINE__);                                \
     } while (0)
 
-enum { SC_DEC = 0, SC_PROF = 1, SC_I32 = 2, SC_FRAMES = 3, SC_FC = 4, SC_MISC = 5, SC_ACQ = 6, SC_MP2 = 7, SC_MOT = 8 };
+enum { SC_DEC = 0, SC_PROF = 1, SC_I32 = 2, SC_FRAMES = 3, SC_FC = 4, SC_MISC = 5, SC_ACQ = 6, SC_MP2 = 7, SC_MOT = 8,
+       SC_AUDIO = 9 };
 int scratch(dabgpu_ctx *c, int slot, size_t bytes, void **p);
 // read (and clear) the device error word; call after a stream synchronisation
 int kernel_errors(dabgpu_ctx *c);
@@ -160,5 +162,7 @@ Profile fic_profile();                                   // fic-handler.cpp:254-
 std::vector<uint8_t> make_inv(const Profile &P);         // inverse depuncturing table
 std::vector<uint8_t> mp2_host_tables();                  // an Mp2Tabs (k_mp2.hip)
 int mp2_tables(dabgpu_ctx *c, const Mp2Tabs **out);      // the context's device copy, made at first use
+const std::vector<float> &audio_host_fir();              // DABGPU_TABLE_AUDIO_FIR, float[3][5]
+int audio_tables(dabgpu_ctx *c, const float **out);      // the context's device copy, made at first use
 
 }  // namespace dab

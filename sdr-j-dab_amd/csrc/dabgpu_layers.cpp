@@ -69,6 +69,7 @@ std::vector<SlotBuf> state_bufs(dabgpu_pipe *p, int kind) {
                 {p->pk.carry_d[p->pk.cur].ptr, (size_t)p->pk.cap, nullptr},
                 {p->pk.ip_state_d.ptr, sizeof(dabgpu_ip_state), nullptr}};
     case slots::MOT: return {{p->mot.state_d.ptr, p->mot.state_bytes, nullptr}};
+    case slots::AUDIO: return {{p->audio.state_d.ptr, sizeof(AudioState), nullptr}};
     default: return {{p->pad.state_d.ptr, sizeof(PadState), nullptr}};
     }
 }
@@ -120,7 +121,8 @@ int layer_ready(const dabgpu_pipe *p, int kind) {
     if (kKinds[kind].parent < 0) {
         if (!p->feed.last_msc || !p->feed.pending[kind]) return fail(DABGPU_E_STATE, "no dabgpu_pipe_run with MSC output to consume");
     } else if (!p->feed.pending[kind]) {
-        return fail(DABGPU_E_STATE, "no dabgpu_pipe_%s call of this run to consume", kind == slots::MOT ? "packet" : "dabplus");
+        return fail(DABGPU_E_STATE, "no dabgpu_pipe_%s call of this run to consume",
+                    kind == slots::MOT ? "packet" : kind == slots::AUDIO ? "mp2" : "dabplus");
     }
     return 0;
 }
@@ -168,6 +170,8 @@ int check_table(const dabgpu_subch *sub, int n, const TableLimits &lim) {
         const int fl = sub[i].flags, br = sub[i].bitRate;
         if ((fl & DABGPU_SUBCH_PAD) && !(fl & DABGPU_SUBCH_DABPLUS))
             return fail(DABGPU_E_ARG, "subchannel %d is flagged PAD and not DAB+", i);
+        if ((fl & DABGPU_SUBCH_AUDIO) && !(fl & DABGPU_SUBCH_MP2))
+            return fail(DABGPU_E_ARG, "subchannel %d is flagged audio output and not layer II", i);
         if ((fl & DABGPU_SUBCH_MOT) && !(fl & DABGPU_SUBCH_PACKET))
             return fail(DABGPU_E_ARG, "subchannel %d is flagged MOT and not packet mode", i);
         if ((fl & DABGPU_SUBCH_IP) && !(fl & DABGPU_SUBCH_PACKET))
@@ -191,7 +195,7 @@ int check_table(const dabgpu_subch *sub, int n, const TableLimits &lim) {
         if ((fl & DABGPU_SUBCH_DABPLUS) && (br < 8 || br % 8 || br / 8 > DP_MAX_RS))
             return fail(DABGPU_E_UNSUP, "DAB+ subchannel %d: bitRate %d is not a multiple of 8 in [8, 384]", i, br);
     }
-    for (int kind = 0; kind < slots::NKIND; kind++) {
+    for (int kind = 0; kind < slots::NSLOTKIND; kind++) {
         const int c = slots::count_flag(sub, n, kKinds[kind].flag);
         if (c > lim.max_slots[kind])
             return fail(DABGPU_E_ARG, "%d %s subchannels, the pipeline holds %d per stream", c, kKinds[kind].name,
@@ -296,6 +300,24 @@ int pad_size(dabgpu_pipe *p, int npad) {
     return 0;
 }
 
+// (Re)size the audio output layer to naudio slots per stream, as pad_size does: the sinks of the
+// slots both sizes hold go on, every other slot is a new one.
+int audio_size(dabgpu_pipe *p, int naudio) {
+    AudioLayer m;
+    if (naudio) {
+        const size_t ne = (size_t)p->S * naudio;
+        HIPCHK(m.ev.create(hipEventDisableTiming));
+        HIPCHK(m.state_d.alloc(ne));
+        HIPCHK(m.src_d.alloc(ne));
+        if (int rc = resize_buf(p->S, {p->audio.state_d.ptr, sizeof(AudioState), nullptr}, p->NAUDIO,
+                                {m.state_d.ptr, sizeof(AudioState), nullptr}, naudio))
+            return rc;
+    }
+    p->audio = std::move(m);
+    p->NAUDIO = naudio;
+    return 0;
+}
+
 // The device's descriptor tables from p->tab / p->since.  The caller has waited for the
 // pipeline's streams (in-flight kernels read the old tables): the tables are replaced.
 int rebuild_tables(dabgpu_pipe *p) {
@@ -386,8 +408,8 @@ int rebuild_tables(dabgpu_pipe *p) {
         }
         HIPCHK(hipMemcpy(p->pk.ip_on_d, on.data(), sizeof(int32_t) * on.size(), hipMemcpyHostToDevice));
     }
-    int32_t *const srcs[] = {p->mot.src_d, p->pad.src_d};                    // slots::MOT, PAD
-    for (int kind = slots::MOT; kind <= slots::PAD; kind++)
+    int32_t *const srcs[] = {p->mot.src_d, p->pad.src_d, p->audio.src_d};    // slots::MOT, PAD, AUDIO
+    for (int kind = slots::MOT; kind <= slots::AUDIO; kind++)
         if (int rc = put_child_src(p, kind, srcs[kind - slots::MOT])) return rc;
     return 0;
 }
@@ -406,10 +428,10 @@ int dabgpu_pipe_set_subch(dabgpu_pipe *p, int stream, const dabgpu_subch *sub, i
     for (auto [s, end] = stream_range(p, stream); s < end; s++) {
         // an entry whose index and fields are unchanged goes on (since_cif and its state in every
         // layer kept, wherever its slots now lie); every other one starts like a new dabConcurrent
-        // and new handlers (mp4Processor, mp2Processor, mscDatagroup, motHandler, padHandler) at
+        // and new handlers (mp4Processor, mp2Processor, mscDatagroup, motHandler, padHandler, audioSink) at
         // the stream's current CIF
         const std::vector<dabgpu_subch> &old = p->tab[s];
-        for (int kind = 0; kind < slots::NKIND; kind++) {
+        for (int kind = 0; kind < slots::NSLOTKIND; kind++) {
             if (!p->nslot(kind)) continue;
             const std::vector<int> plan = slots::carry_plan(old.data(), (int)old.size(), sub, n, kKinds[kind].flag, p->nslot(kind));
             for (const SlotBuf &b : state_bufs(p, kind))
@@ -618,8 +640,54 @@ int dabgpu_pipe_mp2(dabgpu_pipe *p, int16_t *pcm, dabgpu_mp2_info *info) {
         }))
         return rc;
     m.cur ^= 1;
-    p->feed.pending[slots::MP2] = false;       // each run's CIFs enter the layer once
+    LayerFeed &f = p->feed;
+    f.pending[slots::MP2] = false;             // each run's CIFs enter the layer once
+    f.mp2_pcm = pcm;
+    f.mp2_info = info;
+    f.pending[slots::AUDIO] = p->NAUDIO > 0;
     return 0;
+}
+
+int dabgpu_pipe_audio(dabgpu_pipe *p, const int16_t *pcm, const dabgpu_mp2_info *info, float *samples, int32_t *n_out) {
+    if (!p || !pcm || !info || !samples || !n_out) return fail(DABGPU_E_ARG, "null arg");
+    if (int rc = layer_ready(p, slots::AUDIO)) return rc;
+    if (pcm != p->feed.mp2_pcm || info != p->feed.mp2_info)
+        return fail(DABGPU_E_ARG, "pcm_d and info_d are not those of this run's dabgpu_pipe_mp2 call");
+    if (((uintptr_t)pcm & 3) || ((uintptr_t)samples & 7))
+        return fail(DABGPU_E_ARG, "pcm_d must be 4-byte aligned, samples_d 8-byte aligned");
+    AudioLayer &m = p->audio;
+    AudioJob J;
+    memset(&J, 0, sizeof J);
+    J.pcm = pcm;
+    J.in_pairs = 1152;
+    J.in_a = (int64_t)4 * p->F * p->NMP;
+    J.in_c = p->NMP;
+    J.n_chains = p->S * p->NAUDIO;
+    J.chain_len = 4 * p->F;
+    J.cdiv = p->NAUDIO;
+    J.fixed_amount = 1152;
+    J.src = m.src_d;
+    J.info = info;
+    J.state = m.state_d;
+    J.samples = samples;
+    J.n_out = n_out;
+    J.out_pairs = 2304;
+    J.out_a = (int64_t)4 * p->F * p->NAUDIO;
+    J.out_c = p->NAUDIO;
+    if (int rc = audio_tables(p->c, &J.coef)) return rc;
+    // behind the run's layer II layer (the sinks are updated in place, by the pass's second launch)
+    if (int rc = layer_pass(p, m.ev, [&](hipStream_t bs) { return launch_audio(bs, J); })) return rc;
+    p->feed.pending[slots::AUDIO] = false;     // each run's frames enter the layer once
+    return 0;
+}
+
+int dabgpu_pipe_audio_caps(dabgpu_pipe *p, int max_audio) {
+    if (!p || max_audio < 0 || max_audio > p->NMP) return fail(DABGPU_E_ARG, "bad args (max_audio <= max_mp2)");
+    if (int rc = tables_fit(p, slots::AUDIO, max_audio)) return rc;
+    if (int rc = sync_streams(p)) return rc;
+    if (int rc = audio_size(p, max_audio)) return rc;
+    p->feed.pending[slots::AUDIO] = false;
+    return rebuild_tables(p);
 }
 
 int dabgpu_pipe_packet(dabgpu_pipe *p, uint8_t *bytes, dabgpu_datagroup *groups, dabgpu_packet_run *run,

@@ -116,11 +116,12 @@ int dabgpu_pipe_create_caps(dabgpu_ctx *c, const dabgpu_pipe_cfg *cfg, const dab
         return fail(DABGPU_E_ARG, "bad caps (at most 64 subchannels of at most 384 kbit/s)");
     if (cfg->freq_sync_method < 0 || cfg->freq_sync_method > 2)
         return fail(DABGPU_E_UNSUP, "freqSyncMethod %d (0, 1 or 2: ofdm-decoder.cpp:103-161)", cfg->freq_sync_method);
-    // the packet-mode, MOT and PAD layers start with what the table flags (dabgpu_pipe_packet_caps)
+    // the packet-mode, MOT, PAD and audio output layers start with what the table flags (dabgpu_pipe_packet_caps)
     const int npk = slots::count_flag(cfg->subch, cfg->n_subch, DABGPU_SUBCH_PACKET);
     const int nmot = slots::count_flag(cfg->subch, cfg->n_subch, DABGPU_SUBCH_MOT);
     const int npad = slots::count_flag(cfg->subch, cfg->n_subch, DABGPU_SUBCH_PAD);
-    const TableLimits lim{caps->max_subch, caps->max_bitrate, {caps->max_dabplus, caps->max_mp2, npk, nmot, npad}};
+    const int naudio = slots::count_flag(cfg->subch, cfg->n_subch, DABGPU_SUBCH_AUDIO);
+    const TableLimits lim{caps->max_subch, caps->max_bitrate, {caps->max_dabplus, caps->max_mp2, npk, nmot, npad, naudio}};
     if (int rc = check_table(cfg->subch, cfg->n_subch, lim)) return rc;
     auto p = std::make_unique<dabgpu_pipe>();
     p->c = c;
@@ -198,6 +199,8 @@ int dabgpu_pipe_create_caps(dabgpu_ctx *c, const dabgpu_pipe_cfg *cfg, const dab
         if (int rc = mot_size(p.get(), nmot, DABGPU_MOT_BODY_BYTES)) return rc;
     if (npad)
         if (int rc = pad_size(p.get(), npad)) return rc;
+    if (naudio)
+        if (int rc = audio_size(p.get(), naudio)) return rc;
     if (int rc = rebuild_tables(p.get())) return rc;
     // the default re-acquisition mode: a stream that loses sync is searched in the
     // background (DABGPU_CTL_ACQ_ASYNC; DABGPU_CTL_ACQ_SYNC restores the in-run search)

@@ -113,6 +113,13 @@ struct PadLayer {
     dab::DevBuf<int32_t> src_d;        // [S][NPAD] the DAB+ slot (s * NDP + j) each reads, -1: absent
     dab::Event ev;                     // the last pass
 };
+// Audio output layer (an audioSink per layer II entry flagged DABGPU_SUBCH_AUDIO and stream):
+// allocated only while dabgpu_pipe_audio_caps' max_audio > 0
+struct AudioLayer {
+    dab::DevBuf<dab::AudioState> state_d;   // [S][NAUDIO] the sinks' interpolators, updated in place
+    dab::DevBuf<int32_t> src_d;        // [S][NAUDIO] the MP2 slot (s * NMP + j) each reads, -1: absent
+    dab::Event ev;                     // the last pass
+};
 // FIC layer (a fib_processor's database per stream): allocated only while dabgpu_pipe_fic_caps is on
 struct FicLayer {
     dab::DevBuf<uint8_t> db_d;         // [S] dabgpu_fic_db, updated in place
@@ -127,8 +134,8 @@ struct LayerFeed {
     int32_t last_msc_stride = 0;
     bool last_msc_packed = false;
     // per slot kind: DAB+, layer II, packet -- the last run's CIFs have not entered the layer yet;
-    // MOT, PAD -- nor the outputs below of the run's packet / dabplus call
-    bool pending[slots::NKIND] = {};
+    // MOT, PAD, audio output -- nor the outputs below of the run's packet / dabplus / mp2 call
+    bool pending[slots::NSLOTKIND] = {};
     bool ip_pending = false;             // the outputs of the run's packet call have not entered the IP layer yet
     const uint8_t *pk_bytes = nullptr;   // the run's dabgpu_pipe_packet call
     const dabgpu_datagroup *pk_groups = nullptr;
@@ -137,6 +144,8 @@ struct LayerFeed {
     const dabgpu_superframe *dp_info = nullptr;
     int32_t dp_sf_stride = 0;
     bool dp_sf_compact = false;
+    const int16_t *mp2_pcm = nullptr;    // the run's dabgpu_pipe_mp2 call
+    const dabgpu_mp2_info *mp2_info = nullptr;
     const uint8_t *last_fic = nullptr, *last_crc = nullptr;   // the FIC outputs of the last run
     bool last_fic_packed = false;
     bool fic_pending = false;            // ... have not entered the FIC layer yet
@@ -145,6 +154,7 @@ struct LayerFeed {
         pending[slots::DABPLUS] = pending[slots::MP2] = pending[slots::PACKET] = have_rows;
         pending[slots::MOT] = false;     // until this run's dabgpu_pipe_packet
         pending[slots::PAD] = false;     // until this run's dabgpu_pipe_dabplus
+        pending[slots::AUDIO] = false;   // until this run's dabgpu_pipe_mp2
         ip_pending = false;
         fic_pending = have_fic;
     }
@@ -153,6 +163,7 @@ struct LayerFeed {
         last_msc = nullptr;
         pending[slots::MOT] = false;
         pending[slots::PAD] = false;
+        pending[slots::AUDIO] = false;
         ip_pending = false;
     }
 };
@@ -160,13 +171,13 @@ struct LayerFeed {
 // what check_table holds a table against: the pipeline's caps and the slots its layers hold now
 struct TableLimits {
     int max_subch, max_bitrate;
-    int max_slots[slots::NKIND];
+    int max_slots[slots::NSLOTKIND];
 };
 
 struct dabgpu_pipe {
     dabgpu_ctx *c = nullptr;
-    int S = 0, F = 0, NSUB = 0, R = 0, NDP = 0, NMP = 0, NPK = 0, NMOT = 0, NPAD = 0;
-    TableLimits limits() const { return {NSUB, max_bitrate, {NDP, NMP, NPK, NMOT, NPAD}}; }
+    int S = 0, F = 0, NSUB = 0, R = 0, NDP = 0, NMP = 0, NPK = 0, NMOT = 0, NPAD = 0, NAUDIO = 0;
+    TableLimits limits() const { return {NSUB, max_bitrate, {NDP, NMP, NPK, NMOT, NPAD, NAUDIO}}; }
     int nslot(int kind) const { return limits().max_slots[kind]; }   // slots per stream of a slots::kKinds kind
     int16_t threshold = 3;
     int16_t method = 1;              // freqSyncMethod
@@ -235,6 +246,7 @@ struct dabgpu_pipe {
     PacketLayer pk;
     MotLayer mot;
     PadLayer pad;
+    AudioLayer audio;
     FicLayer fic;
     LayerFeed feed;
     // the iqBuffer feed (dabgpu_pipe_set_display): symbol 2's display carriers per ring slot
@@ -283,6 +295,7 @@ int check_table(const dabgpu_subch *sub, int n, const TableLimits &lim);
 int packet_size(dabgpu_pipe *p, int npk, int cap);
 int mot_size(dabgpu_pipe *p, int nmot, int body);
 int pad_size(dabgpu_pipe *p, int npad);
+int audio_size(dabgpu_pipe *p, int naudio);
 int rebuild_tables(dabgpu_pipe *p);
 
 }  // namespace dab

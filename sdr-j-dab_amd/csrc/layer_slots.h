@@ -9,17 +9,20 @@
 namespace slots {
 
 // The slot kinds.  parent >= 0: the kind's src_d row names slots of the parent kind (a MOT slot
-// reads a packet slot, a PAD slot a DAB+ slot).  name: as the error texts spell it.
+// reads a packet slot, a PAD slot a DAB+ slot, an audio output slot a layer II slot).  name: as the
+// error texts spell it.  NKIND counts the kinds up to PAD; NSLOTKIND counts them all.
 enum { DABPLUS = 0, MP2, PACKET, MOT, PAD, NKIND };
+enum { AUDIO = NKIND, NSLOTKIND };
 struct Kind {
     int flag, parent;
     const char *name;
 };
-constexpr Kind kKinds[NKIND] = {{DABGPU_SUBCH_DABPLUS, -1, "DAB+"},
+constexpr Kind kKinds[NSLOTKIND] = {{DABGPU_SUBCH_DABPLUS, -1, "DAB+"},
                                 {DABGPU_SUBCH_MP2, -1, "layer II"},
                                 {DABGPU_SUBCH_PACKET, -1, "packet-mode"},
                                 {DABGPU_SUBCH_MOT, PACKET, "MOT"},
-                                {DABGPU_SUBCH_PAD, DABPLUS, "PAD"}};
+                                {DABGPU_SUBCH_PAD, DABPLUS, "PAD"},
+                                {DABGPU_SUBCH_AUDIO, MP2, "audio output"}};
 
 inline bool same_subch(const dabgpu_subch &a, const dabgpu_subch &b) {
     return a.startAddr == b.startAddr && a.length == b.length && a.bitRate == b.bitRate && a.protLevel == b.protLevel &&

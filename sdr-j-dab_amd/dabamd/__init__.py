@@ -37,6 +37,9 @@ class Subch(C.Structure):
 SUBCH_DABPLUS = 1   # Subch.flags: feed the DAB+ superframe layer
 SUBCH_RAW = 2       # Subch.flags (msc_deconvolve): no energy dispersal
 SUBCH_MP2 = 4       # Subch.flags: feed the MPEG layer II layer (Pipeline.mp2)
+SUBCH_AUDIO = 128   # Subch.flags, with SUBCH_MP2: feed the audio output layer (Pipeline.audio)
+AUDIO_STATE_BYTES = 32   # DABGPU_AUDIO_STATE_BYTES
+TABLE_AUDIO_FIR = 6      # DABGPU_TABLE_AUDIO_FIR: float32 [3, 5]
 MP2_STATE_BYTES = 3840   # DABGPU_MP2_STATE_BYTES: a layer II decoder's carried state
 MP2_INFO_DTYPE = np.dtype([("status", "<i4"), ("sample_rate", "<i4"), ("frame_bytes", "<i4")])   # dabgpu_mp2_info
 SUBCH_PACKET = 8    # Subch.flags: feed the packet-mode data layer (Pipeline.packet)
@@ -387,6 +390,9 @@ def lib() -> C.CDLL:
             "dabgpu_pipe_dabplus": ([vp, vp, C.c_int32, vp], i32),
             "dabgpu_mp2_decode": ([vp, vp, i64, i32, i32, vp, vp, vp], i32),
             "dabgpu_pipe_mp2": ([vp, vp, vp], i32),
+            "dabgpu_audio_out": ([vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp], i32),
+            "dabgpu_pipe_audio": ([vp, vp, vp, vp, vp], i32),
+            "dabgpu_pipe_audio_caps": ([vp, i32], i32),
             "dabgpu_pipe_packet": ([vp, vp, vp, vp, vp], i32),
             "dabgpu_pipe_packet_caps": ([vp, i32, i32], i32),
             "dabgpu_mot_state_bytes": ([i32], sz),
@@ -462,7 +468,7 @@ def host_table(which: int) -> np.ndarray:
     """the product's host-built tables (dabgpu_host_table; no device needed)"""
     shape, dt = {TABLE_PRS: ((2048, 2), np.float32), TABLE_MAPPER: (1536, np.int16),
                  TABLE_REFARG: (18, np.float32), TABLE_OSC: ((2048000, 2), np.float32),
-                 TABLE_NCO: ((384, 2), np.float64)}[which]
+                 TABLE_NCO: ((384, 2), np.float64), TABLE_AUDIO_FIR: ((3, 5), np.float32)}[which]
     out = np.zeros(shape, dt)
     _chk(lib().dabgpu_host_table(which, _p(out), out.nbytes), "dabgpu_host_table")
     return out
@@ -820,6 +826,34 @@ class Context:
         finally:
             din.free(); ds.free(); dp.free(); dr.free()
 
+    def audio_out(self, pcm: np.ndarray, rates, amounts, state: Optional[np.ndarray] = None, fill: Optional[float] = None):
+        """audioSink::audioOut per call (audiosink.cpp:235-360): pcm [n_chains, chain_len, max_amount, 2]
+        int16, rates and amounts [n_chains, chain_len] (rate 0: no call), chain_len consecutive calls
+        to each sink in order; state [n_chains, AUDIO_STATE_BYTES] bytes carried from an earlier call
+        (None: new sinks).  Returns (samples [n_chains, chain_len, 3 * max_amount, 2] float32 -- the
+        first n_out pairs of a row are the call's, the rest keeps `fill` (None: zeros) --, n_out
+        [n_chains, chain_len] int32, state)."""
+        pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+        nc, cl, ma, two = pcm.shape
+        if two != 2:
+            raise DabError("audio_out: pcm is [n_chains, chain_len, max_amount, 2]")
+        ra = np.ascontiguousarray(rates, dtype=np.int32).reshape(nc, cl)
+        am = np.ascontiguousarray(amounts, dtype=np.int32).reshape(nc, cl)
+        st = np.zeros((nc, AUDIO_STATE_BYTES), np.uint8) if state is None else \
+            np.ascontiguousarray(state, dtype=np.uint8).reshape(nc, AUDIO_STATE_BYTES)
+        n = nc * cl
+        din, ds = self.put(pcm if pcm.size else np.zeros(2, np.int16)), self.put(st if st.size else np.zeros(32, np.uint8))
+        out = np.zeros((nc, cl, 3 * ma, 2), np.float32) if fill is None else np.full((nc, cl, 3 * ma, 2), fill, np.float32)
+        do, dn = self.put(out if out.size else np.zeros(2, np.float32)), self.buf(max(4, 4 * n))
+        try:
+            _chk(lib().dabgpu_audio_out(self.h, din.ptr, ma, nc, cl, ma, _p(ra), _p(am), ds.ptr, do.ptr, dn.ptr),
+                 "dabgpu_audio_out")
+            self.sync()
+            return (do.download(np.float32, (nc, cl, 3 * ma, 2)), dn.download(np.int32, (nc, cl)),
+                    ds.download(np.uint8, (nc, AUDIO_STATE_BYTES)))
+        finally:
+            din.free(); ds.free(); do.free(); dn.free()
+
     def prs_sync(self, iq: DevBuf, frames: Sequence[Frame], level: int = 3):
         """phaseReference::findIndex (phasereference.cpp:60-88) per frame window."""
         n = len(frames)
@@ -1050,6 +1084,43 @@ class Pipeline:
         self.max_pad = sum(1 for s in self.subch if s.flags & SUBCH_PAD)
         self._pad_bufs()
         self._fic = []                   # the FIC layer's outputs, while fic_caps is on
+        self._audio = []
+        self.max_audio = sum(1 for s in self.subch if s.flags & SUBCH_AUDIO)
+        self._audio_bufs()
+
+    def _audio_bufs(self) -> None:
+        for o in self._audio:
+            for b in o:
+                b.free()
+        self._audio = []
+        if self.max_audio:
+            nrec = self.S * 4 * self.F * self.max_audio
+            self._audio = [(self.ctx.buf(nrec * 2304 * 8).zero(), self.ctx.buf(nrec * 4)) for _ in range(2)]
+
+    def audio_caps(self, max_audio: int) -> None:
+        """size the audio output layer between runs (dabgpu_pipe_audio_caps): max_audio slots per
+        stream (<= max_mp2); the existing slots keep their sinks"""
+        _chk(lib().dabgpu_pipe_audio_caps(self.h, int(max_audio)), "dabgpu_pipe_audio_caps")
+        self.max_audio = int(max_audio)
+        self._audio_bufs()
+
+    def audio(self, download: bool = True):
+        """Audio output layer over the frames of this run's mp2() (dabgpu_pipe_audio; audiosink.cpp:
+        235-360).  Returns (samples [S, 4F, max_audio, 2304, 2] float32, the first n_out pairs of a
+        row valid, n_out [S, 4F, max_audio] int32: 0, 1152 or 2304)."""
+        if not self._audio or not hasattr(self, "pcm_d"):
+            # max_audio == 0, or no mp2() yet: there are no buffers to hand to the library, which would refuse as well
+            e = DabError("dabgpu_pipe_audio: no audio output subchannel in this pipeline" if not self._audio else
+                         "dabgpu_pipe_audio: no dabgpu_pipe_mp2 call of this run to consume")
+            e.code = -6                  # DABGPU_E_STATE
+            raise e
+        self.aus_d, self.aun_d = self._audio[(self._run - 1) & 1]
+        _chk(lib().dabgpu_pipe_audio(self.h, self.pcm_d.ptr, self.mp2i_d.ptr, self.aus_d.ptr, self.aun_d.ptr), "dabgpu_pipe_audio")
+        if not download:
+            return None
+        self.sync()
+        shape = (self.S, 4 * self.F, self.max_audio)
+        return self.aus_d.download(np.float32, shape + (2304, 2)), self.aun_d.download(np.int32, shape)
 
     def _pad_bufs(self) -> None:
         for o in self._pad:
@@ -1435,7 +1506,7 @@ class Pipeline:
 
     def close(self) -> None:
         if self.h:
-            for o in self._outs + self._sf + self._mp2 + self._pkt + self._ip + self._mot + self._pad + self._fic:
+            for o in self._outs + self._sf + self._mp2 + self._pkt + self._ip + self._mot + self._pad + self._fic + self._audio:
                 for b in o:
                     b.free()
             lib().dabgpu_pipe_destroy(self.h)

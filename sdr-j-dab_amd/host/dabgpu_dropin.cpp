@@ -295,6 +295,12 @@ ensembleDecoder::ensembleDecoder(const config &cfg) : cfg_(cfg) {
         mp2i_.resize(SF * 4 * nmp_ * sizeof(dabgpu_mp2_info));
     }
     for (const dabgpu_subch &sc : cfg.subch)
+        if (sc.flags & DABGPU_SUBCH_AUDIO) naudio_++;
+    if (cfg.max_audio) {
+        naudio_ = cfg.max_audio;
+        chk(dabgpu_pipe_audio_caps(pipe_, naudio_), "dabgpu_pipe_audio_caps");
+    }
+    for (const dabgpu_subch &sc : cfg.subch)
         if (sc.flags & DABGPU_SUBCH_PACKET) npk_++;
     pk_cap_ = cfg.max_group_bytes ? cfg.max_group_bytes : DABGPU_PKT_GROUP_BYTES;
     if (cfg.max_packet || cfg.max_group_bytes) {
@@ -516,7 +522,7 @@ bool ensembleDecoder::step() {
     const bool ok = rc == DABGPU_OK;
     const bool gpu_fic = cfg_.auto_layout && cfg_.fic_on_gpu;
     if (gpu_fic) {                 // behind the run's FIC decode, on its back-end stream
-        const int want = (pcm_cb_ && nmp_ > 0 ? DABGPU_SUBCH_MP2 : 0) | (dg_cb_ && npk_ > 0 ? DABGPU_SUBCH_PACKET : 0) |
+        const int want = ((pcm_cb_ || (audio_cb_ && naudio_ > 0)) && nmp_ > 0 ? DABGPU_SUBCH_MP2 : 0) | (dg_cb_ && npk_ > 0 ? DABGPU_SUBCH_PACKET : 0) |
                          (mot_cb_ && nmot_ > 0 ? DABGPU_SUBCH_MOT : 0) | (ip_cb_ && npk_ > 0 ? DABGPU_SUBCH_IP : 0) |
                          ((label_cb_ || pad_dg_cb_ || pad_obj_cb_) && npad_ > 0 ? DABGPU_SUBCH_PAD : 0);
         chk(dabgpu_pipe_fic(pipe_, (const uint8_t *)fic_.get(), (const uint8_t *)crc_.get(), want, (dabgpu_fic_event *)fce_.get(),
@@ -701,6 +707,40 @@ bool ensembleDecoder::step() {
                     }
             }
         }
+        bool flagged = false;                        // (an unset callback or no flagged entry: nothing is launched)
+        for (int s = 0; s < S && audio_cb_ && naudio_; s++)
+            for (const dabgpu_subch &e : tab_[s]) flagged |= (e.flags & DABGPU_SUBCH_AUDIO) != 0;
+        if (flagged) {
+            const size_t rows = (size_t)S * 4 * F * naudio_;
+            if (!aus_.get()) {
+                aus_.resize(rows * 2304 * 2 * sizeof(float));
+                aun_.resize(rows * sizeof(int32_t));
+            }
+            chk(dabgpu_pipe_audio(pipe_, (const int16_t *)pcm_.get(), (const dabgpu_mp2_info *)mp2i_.get(), (float *)aus_.get(),
+                                  (int32_t *)aun_.get()), "dabgpu_pipe_audio");
+            chk(dabgpu_pipe_sync(pipe_), "dabgpu_pipe_sync");
+            std::vector<int32_t> n_out(rows);
+            aun_.download(n_out.data(), rows * sizeof(int32_t));
+            // one download per stream that delivered, its rows as they lie (the on_pcm path's bulk copy)
+            const size_t per_stream = (size_t)4 * F * naudio_ * 2304 * 2;
+            std::vector<float> samples(per_stream);
+            for (int s = 0; s < S; s++) {
+                std::vector<int> slot;               // audio slot j of a stream is its j-th flagged entry
+                for (int k = 0; k < (int)tab_[s].size(); k++)
+                    if (tab_[s][k].flags & DABGPU_SUBCH_AUDIO) slot.push_back(k);
+                bool any = false;
+                for (size_t r = (size_t)s * 4 * F * naudio_; r < (size_t)(s + 1) * 4 * F * naudio_; r++) any |= n_out[r] > 0;
+                if (!any || slot.empty()) continue;
+                chk(dabgpu_memcpy_d2h(thread_context(), samples.data(), (const float *)aus_.get() + s * per_stream,
+                                      per_stream * sizeof(float)), "dabgpu_memcpy_d2h");
+                for (int c = 0; c < 4 * F; c++)
+                    for (int j = 0; j < (int)slot.size() && j < naudio_; j++) {
+                        const size_t r = ((size_t)s * 4 * F + c) * naudio_ + j;
+                        if (n_out[r] <= 0 || n_out[r] > 2304) continue;
+                        audio_cb_(s, 4 * frames_done_[s] + c, slot[j], samples.data() + ((size_t)c * naudio_ + j) * 2304 * 2, n_out[r]);
+                    }
+            }
+        }
     }
     if (NS && npk_) {
         chk(dabgpu_pipe_packet(pipe_, (uint8_t *)pkb_.get(), (dabgpu_datagroup *)pkg_.get(), (dabgpu_packet_run *)pkr_.get(),
@@ -834,12 +874,19 @@ bool ensembleDecoder::step() {
             const dabgpu_fic_table &t = fic_tab_[s];
             now.assign(t.sub, t.sub + std::max(0, std::min(t.n, 64)));
         } else {
-            for (const fib_subch &e : fibs_[s].subchannels(nullptr, pcm_cb_ != nullptr && nmp_ > 0, dg_cb_ != nullptr && npk_ > 0,
+            for (const fib_subch &e : fibs_[s].subchannels(nullptr, (pcm_cb_ || (audio_cb_ && naudio_ > 0)) && nmp_ > 0,
+                                                           dg_cb_ != nullptr && npk_ > 0,
                                                            mot_cb_ != nullptr && nmot_ > 0,
                                                            (label_cb_ || pad_dg_cb_ || pad_obj_cb_) && npad_ > 0,
                                                            ip_cb_ != nullptr && npk_ > 0))
                 now.push_back({e.startAddr, e.length, e.bitRate, e.protLevel, e.uepFlag, e.flags});
         }
+        // on_audio: the layer II entries also feed the audio output layer, as far as its slots go
+        for (int k = 0, j = 0; k < (int)now.size() && audio_cb_ && j < naudio_; k++)
+            if (now[k].flags & DABGPU_SUBCH_MP2) {
+                now[k].flags |= DABGPU_SUBCH_AUDIO;
+                j++;
+            }
         auto same = [](const std::vector<dabgpu_subch> &x, const std::vector<dabgpu_subch> &y) {
             return x.size() == y.size() && (x.empty() || !std::memcmp(x.data(), y.data(), x.size() * sizeof(dabgpu_subch)));
         };

@@ -500,6 +500,9 @@ public:
         // may hold (0: what subch needs)
         int max_subch = 0, max_bitrate = 0, max_dabplus = 0;
         int max_mp2 = 0;                     // layer II (DABGPU_SUBCH_MP2) entries likewise
+        // dabgpu_pipe_audio_caps: layer II entries also flagged DABGPU_SUBCH_AUDIO a stream's table
+        // may hold (0: what subch flags; at most max_mp2)
+        int max_audio = 0;
         // dabgpu_pipe_packet_caps: packet-mode (DABGPU_SUBCH_PACKET) entries a stream's table may
         // hold (0: what subch flags) and the largest data group (0: DABGPU_PKT_GROUP_BYTES)
         int max_packet = 0, max_group_bytes = 0;
@@ -550,6 +553,16 @@ public:
     // has ASCTy 0 are flagged when this callback is set before the table is applied.
     using pcm_cb = std::function<void(int stream, int64_t cif, int subch, const int16_t *pcm, int n_samples, int rate)>;
     void on_pcm(pcm_cb f) { pcm_cb_ = std::move(f); }
+    // The same audio as audioSink::audioOut puts it into _O_Buffer (audiosink.cpp:235-360): 48 kHz
+    // float stereo pairs, 24 kHz frames interpolated by the reference's LowPassFIR (dabgpu_pipe_audio
+    // after the step's dabgpu_pipe_mp2), for the entries flagged DABGPU_SUBCH_MP2 |
+    // DABGPU_SUBCH_AUDIO: one call per accepted frame (n_pairs 1152 or 2304), after the step's on_pcm
+    // calls; a caller concatenates an entry's calls to its signal.  With auto_layout, sub-channels
+    // whose audio component has ASCTy 0 are flagged DABGPU_SUBCH_MP2 | DABGPU_SUBCH_AUDIO when this
+    // callback is set before the table is applied (config::max_mp2 and max_audio say how many).
+    // With the callback unset nothing is flagged, allocated or launched.
+    using audio_cb = std::function<void(int stream, int64_t cif, int subch, const float *samples, int n_pairs)>;
+    void on_audio(audio_cb f) { audio_cb_ = std::move(f); }
     // MSC data groups of the packet-mode entries (DABGPU_SUBCH_PACKET, dabgpu_pipe_packet), where
     // my_dataHandler->add_mscDatagroup stands in the reference (msc-datagroup.cpp:285, :304):
     // one call per completed group, accepted or not, as bytes (the reference passes one bit per
@@ -633,6 +646,9 @@ private:
     dabgpu_pipe *pipe_ = nullptr;
     devbuf iq_, fic_, crc_, msc_, sf_, sfi_, pcm_, mp2i_, pkb_, pkg_, pkr_, pki_;
     int nmp_ = 0, npk_ = 0, pk_cap_ = 0;
+    devbuf aus_, aun_;                                // the audio output layer's samples and pair counts (first use)
+    int naudio_ = 0;
+    audio_cb audio_cb_;
     size_t pk_slots_ = 0, pk_arena_ = 0;
     devbuf mob_, moo_, mor_;                          // the MOT layer's arenas, object records, run records
     int nmot_ = 0;

@@ -1,7 +1,9 @@
 // msc_consumers.cpp -- see msc_consumers.h.
 #include "msc_consumers.h"
+#include "audio_fir.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 namespace dabgpu {
@@ -601,6 +603,59 @@ void padAssembler::build_MSC_segment(int32_t length) {
     g.data.assign(buffer_.begin() + index, buffer_.begin() + index + g.data_nbytes);
     c_.groups++;
     if (onGroup_) onGroup_(g);
+}
+
+// ---- audioResampler -------------------------------------------------------------
+// (this file is built with contraction off: a fused multiply-add would round once where the
+// reference rounds twice)
+const float *audioResampler::kernels() {
+    static const struct table {
+        float k[15];
+        table() { audio_fir_kernels(k); }
+    } t;
+    return t.k;
+}
+
+audioResampler::audioResampler() {
+    for (int r = 0; r < 3; r++) f_[r].k = kernels() + 5 * r;
+}
+
+// LowPassFIR::Pass (DSPCOMPLEX) (fir-filters.cpp:78-92): the newest sample times k[0] first; each
+// term the complex product with (k[i], 0) as the compiler spells it out
+audioResampler::pair audioResampler::fir::pass(pair z) {
+    pair tmp{0.0f, 0.0f};
+    buf[ip] = z;
+    for (int i = 0; i < 5; i++) {
+        const pair &b = buf[ip - i < 0 ? ip - i + 5 : ip - i];
+        const float re = b.re * k[i] - b.im * 0.0f, im = b.re * 0.0f + b.im * k[i];
+        tmp.re += re;
+        tmp.im += im;
+    }
+    ip = (ip + 1) % 5;
+    return tmp;
+}
+
+bool audioResampler::audioOut(const int16_t *V, int32_t amount, int32_t rate, std::vector<float> &out) {
+    if (amount < 0) return false;
+    const int r = rate == 16000 ? 0 : rate == 24000 ? 1 : rate == 32000 ? 2 : -1;
+    if (r == 2 && (amount & 1)) return false;
+    const int zeros = r == 1 ? 1 : 2;           // zero pairs after each input pair
+    int32_t n = 0;                              // Pass results of this call
+    for (int32_t i = 0; i < amount; i++) {
+        const pair z{(float)((float)V[2 * i] / 32767.0), (float)((float)V[2 * i + 1] / 32767.0)};
+        if (r < 0) {                            // audioOut_48000, the default: label
+            out.push_back(z.re);
+            out.push_back(z.im);
+            continue;
+        }
+        for (int j = 0; j <= zeros; j++, n++) {
+            const pair y = f_[r].pass(j == 0 ? z : pair{0.0f, 0.0f});
+            if (r == 2 && (n & 1)) continue;    // audioOut_32000 keeps buffer_1 [2 * i]
+            out.push_back(y.re);
+            out.push_back(y.im);
+        }
+    }
+    return true;
 }
 
 }  // namespace dabgpu

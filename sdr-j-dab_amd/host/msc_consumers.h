@@ -2,7 +2,8 @@
 // subchannel, minus the codecs: the plug-in interfaces (dabVirtual, dabProcessor),
 // the MPEG-1/2 layer II frame synchroniser of mp2Processor (mp2processor.cpp:572-629),
 // the packet-mode data-group assembly of mscDatagroup (msc-datagroup.cpp:221-339),
-// motHandler's header mode (mot-data.cpp:679-728) and ip_dataHandler (ip-datahandler.cpp).
+// motHandler's header mode (mot-data.cpp:679-728), ip_dataHandler (ip-datahandler.cpp) and
+// audioSink's conversion to 48 kHz floats (audiosink.cpp:235-360).
 // Host code (a few bit operations per decoded bit, after the GPU's Viterbi): no Qt,
 // no kjmp2 / faad / sockets -- complete frames, data groups, MOT objects and UDP payloads go to
 // callbacks instead.  Same state machines and quirks as the reference.
@@ -68,6 +69,32 @@ private:
     std::vector<uint8_t> MP2frame_;
     int16_t MP2Header_OK_ = 0, MP2headerCount_ = 0, MP2bitCount_ = 0;
     int32_t frames_ = 0;
+};
+
+// audioSink::audioOut (audiosink.cpp:235-360) minus the device: int16 stereo PCM at 16, 24, 32 or
+// 48 kHz in, the 48 kHz float pairs it puts into _O_Buffer out (appended to `out`).  16, 24 and
+// 32 kHz go through LowPassFIR (5, ...)::Pass (fir-filters.cpp:78-92) over the zero-stuffed input,
+// 32 kHz keeping every second result of a call; every other rate is scaled only.  The same
+// function, bit for bit, as the GPU's audio output layer (dabgpu_audio_out in include/dabgpu.h):
+// every product and sum is rounded to float on its own.  The three filters live as long as the
+// object; a call at one rate leaves the others as they were.  Not modelled: the ring's
+// back-pressure and dumpFile.  An odd amount at 32000 (the reference then puts a float it never
+// wrote) and a negative amount deliver nothing and return false.
+class audioResampler {
+public:
+    audioResampler();
+    bool audioOut(const int16_t *V, int32_t amount, int32_t rate, std::vector<float> &out);
+    // the kernels of f_16000, f_24000 and f_32000 (fir-filters.cpp:35-69), 5 taps each
+    static const float *kernels();
+private:
+    struct pair { float re, im; };
+    struct fir {                                // LowPassFIR's Buffer and ip
+        pair buf[5] = {};
+        int ip = 0;
+        const float *k = nullptr;
+        pair pass(pair z);
+    };
+    fir f_[3];                                  // 16000, 24000, 32000
 };
 
 // mscDatagroup's packet handling (msc-datagroup.cpp:221-339): the decoded bits of a CIF
