@@ -530,17 +530,17 @@ public:
                                      const uint8_t *bytes, int nbytes)>;
     explicit ensembleDecoder(const config &cfg);
     ~ensembleDecoder();
-    void on_fib(fib_cb f) { fib_cb_ = std::move(f); }
-    void on_msc(msc_cb f) { msc_cb_ = std::move(f); }
-    void on_superframe(sf_cb f) { sf_cb_ = std::move(f); }
+    void on_fib(fib_cb f) { fic_.on_fib = std::move(f); }
+    void on_msc(msc_cb f) { msc_.on_msc = std::move(f); }
+    void on_superframe(sf_cb f) { dabplus_.on_superframe = std::move(f); }
     // With auto_layout: the signals nameofEnsemble (FIG 1/0, once until clearEnsemble) and
     // addtoEnsemble (FIG 1/1, once per service) of each stream's fib_processor, from the host's
     // parse or, with fic_on_gpu, from the device's events: frame is the frame whose FIB carried
     // the label, the text UTF-8 (fib_processor::label_text), 16 characters as transmitted.
     using ensemble_name_cb = std::function<void(int stream, int64_t frame, uint32_t EId, const std::string &name)>;
     using service_name_cb = std::function<void(int stream, int64_t frame, const std::string &label)>;
-    void on_ensemble_name(ensemble_name_cb f) { ens_name_cb_ = std::move(f); }
-    void on_service_name(service_name_cb f) { svc_name_cb_ = std::move(f); }
+    void on_ensemble_name(ensemble_name_cb f) { fic_.on_ensemble_name = std::move(f); }
+    void on_service_name(service_name_cb f) { fic_.on_service_name = std::move(f); }
     // With auto_layout: the stream's service database as a fib_processor -- the host's own, or
     // with fic_on_gpu one loaded from the device's record (dabgpu_pipe_fic_db, import_db) -- to ask
     // kindofService / dataforAudioService / dataforDataService / serviceLabels.
@@ -552,7 +552,7 @@ public:
     // in which the frame completed.  With auto_layout, sub-channels whose audio component
     // has ASCTy 0 are flagged when this callback is set before the table is applied.
     using pcm_cb = std::function<void(int stream, int64_t cif, int subch, const int16_t *pcm, int n_samples, int rate)>;
-    void on_pcm(pcm_cb f) { pcm_cb_ = std::move(f); }
+    void on_pcm(pcm_cb f) { mp2_.on_pcm = std::move(f); }
     // The same audio as audioSink::audioOut puts it into _O_Buffer (audiosink.cpp:235-360): 48 kHz
     // float stereo pairs, 24 kHz frames interpolated by the reference's LowPassFIR (dabgpu_pipe_audio
     // after the step's dabgpu_pipe_mp2), for the entries flagged DABGPU_SUBCH_MP2 |
@@ -562,7 +562,7 @@ public:
     // callback is set before the table is applied (config::max_mp2 and max_audio say how many).
     // With the callback unset nothing is flagged, allocated or launched.
     using audio_cb = std::function<void(int stream, int64_t cif, int subch, const float *samples, int n_pairs)>;
-    void on_audio(audio_cb f) { audio_cb_ = std::move(f); }
+    void on_audio(audio_cb f) { audio_.on_audio = std::move(f); }
     // MSC data groups of the packet-mode entries (DABGPU_SUBCH_PACKET, dabgpu_pipe_packet), where
     // my_dataHandler->add_mscDatagroup stands in the reference (msc-datagroup.cpp:285, :304):
     // one call per completed group, accepted or not, as bytes (the reference passes one bit per
@@ -572,10 +572,10 @@ public:
     // set before the table is applied.
     using datagroup_cb = std::function<void(int stream, int64_t cif, int subch, const dabgpu_datagroup &g,
                                             const uint8_t *bytes, int nbytes)>;
-    void on_datagroup(datagroup_cb f) { dg_cb_ = std::move(f); }
+    void on_datagroup(datagroup_cb f) { packet_.on_datagroup = std::move(f); }
     // show_mscErrors (msc-datagroup.cpp:250-254): 100 - crcErrors / 5 per 500 handled packets
     using packet_quality_cb = std::function<void(int stream, int64_t cif, int subch, int value)>;
-    void on_packet_quality(packet_quality_cb f) { pq_cb_ = std::move(f); }
+    void on_packet_quality(packet_quality_cb f) { packet_.on_quality = std::move(f); }
     // MOT objects of the packet-mode entries also flagged DABGPU_SUBCH_MOT (dabgpu_pipe_mot, after
     // the step's dabgpu_pipe_packet), where motHandler emits the_picture or fopens (mot-data.cpp:
     // 315-346): one call per completed object in completion order, after the step's on_datagroup
@@ -585,7 +585,7 @@ public:
     // is set before the table is applied (config::max_packet and max_mot say how many).
     using mot_object_cb = std::function<void(int stream, int64_t cif, int subch, const dabgpu_mot_object &o,
                                              const uint8_t *body)>;
-    void on_mot_object(mot_object_cb f) { mot_cb_ = std::move(f); }
+    void on_mot_object(mot_object_cb f) { mot_.on_object = std::move(f); }
     // UDP payloads of the packet-mode entries also flagged DABGPU_SUBCH_IP (dabgpu_pipe_ip, after the
     // step's dabgpu_pipe_packet), where ip_dataHandler emits writeDatagram (ip-datahandler.cpp:
     // 124-127), and the numbers it emits with show_ipErrors every 100 datagrams: in group order,
@@ -595,8 +595,8 @@ public:
     // table is applied (config::max_packet says how many).
     using datagram_cb = std::function<void(int stream, int subch, int64_t cif, const uint8_t *bytes, int n)>;
     using ip_quality_cb = std::function<void(int stream, int subch, int value)>;
-    void on_datagram(datagram_cb f) { ip_cb_ = std::move(f); }
-    void on_ip_quality(ip_quality_cb f) { ipq_cb_ = std::move(f); }
+    void on_datagram(datagram_cb f) { ip_.on_datagram = std::move(f); }
+    void on_ip_quality(ip_quality_cb f) { ip_.on_quality = std::move(f); }
     // DAB+ PAD of the entries flagged DABGPU_SUBCH_DABPLUS | DABGPU_SUBCH_PAD (dabgpu_pipe_pad after
     // the step's dabgpu_pipe_dabplus): the dynamic label where padHandler emits showLabel (the
     // record holds the bytes, pieces and charSet the reference hands to toQStringUsingCharset:
@@ -613,9 +613,9 @@ public:
                                                 const uint8_t *bytes, int nbytes)>;
     using pad_object_cb = std::function<void(int stream, int64_t cif, int subch, const dabgpu_mot_object &o,
                                              const uint8_t *body)>;
-    void on_dynamic_label(dynamic_label_cb f) { label_cb_ = std::move(f); }
-    void on_pad_datagroup(pad_datagroup_cb f) { pad_dg_cb_ = std::move(f); }
-    void on_pad_object(pad_object_cb f) { pad_obj_cb_ = std::move(f); }
+    void on_dynamic_label(dynamic_label_cb f) { pad_.on_label = std::move(f); }
+    void on_pad_datagroup(pad_datagroup_cb f) { pad_.on_datagroup = std::move(f); }
+    void on_pad_object(pad_object_cb f) { pad_mot_.on_object = std::move(f); }
     // samples[s] -> n[s] cf32 samples of stream s (copied to HBM)
     void load(const std::vector<const DSPCOMPLEX *> &samples, const std::vector<int64_t> &n);
     // the streams as recorded: format DABGPU_IQ_S16 (.sdr PCM16 I/Q pairs) or DABGPU_IQ_U8
@@ -642,47 +642,140 @@ public:
     // the stream's table (dabgpu_pipe_get_subch); since_cif (optional) per entry
     std::vector<dabgpu_subch> get_subch(int stream, std::vector<int64_t> *since_cif = nullptr) const;
 private:
+    // (the implementation: ensemble_decoder.cpp)
+    // a typed device array: devbuf in counts of T
+    template <class T> class devarr {
+    public:
+        void resize(size_t n) { b_.resize(n * sizeof(T)); }
+        T *get() const { return static_cast<T *>(b_.get()); }
+        size_t size() const { return b_.size() / sizeof(T); }
+        void upload(const std::vector<T> &h) { b_.upload(h.data(), h.size() * sizeof(T)); }
+        // elements [first, first + count) into h (h keeps at least one element, so h.data() stands)
+        void download(std::vector<T> &h, size_t first, size_t count) const;
+    private:
+        devbuf b_;
+    };
+    // what a layer leaves per element e = stream * slots of the layer + slot: up to `slots` records and
+    // their bytes, packed into an arena of `arena` bytes
+    template <class T> struct slot_store {
+        devarr<T> records;
+        devarr<uint8_t> bytes;
+        size_t slots = 0, arena = 0;
+        void resize(size_t elements, size_t slots_each, size_t arena_each) {
+            slots = slots_each;
+            arena = arena_each;
+            bytes.resize(elements * arena);
+            records.resize(elements && slots ? elements * slots : 1);
+        }
+        // element e's first n records and the first nbytes of its arena: what the run completed
+        void fetch(size_t e, int n, int nbytes, std::vector<T> &r, std::vector<uint8_t> &b) const {
+            records.download(r, e * slots, (size_t)n);
+            bytes.download(b, e * arena, (size_t)nbytes);
+        }
+    };
+    // One struct per layer, in the order of a step: n is the layer's slot count per stream
+    struct {                                          // FIC: the run's FIBs and CRC flags
+        devarr<uint8_t> fibs, crc;
+        devarr<dabgpu_fic_event> events;              // fic_on_gpu: the FIC layer's events, tables, run records
+        devarr<dabgpu_fic_table> tables;
+        devarr<dabgpu_fic_run> runs;
+        std::vector<dabgpu_fic_table> table;          // fic_on_gpu: [stream] the tables of this step
+        std::vector<fib_processor> parser;            // auto_layout: [stream]
+        int64_t frame = 0;                            // the frame of the FIB the host's fib_processor is parsing
+        fib_cb on_fib;
+        ensemble_name_cb on_ensemble_name;
+        service_name_cb on_service_name;
+    } fic_;
+    struct {                                          // MSC rows, packed
+        int n = 0, stride = 0, maxbits = 0;
+        devarr<uint8_t> rows;
+        msc_cb on_msc;
+    } msc_;
+    struct {                                          // DAB+ superframes
+        int n = 0, stride = 0;
+        devarr<uint8_t> bytes;
+        devarr<dabgpu_superframe> info;
+        sf_cb on_superframe;
+    } dabplus_;
+    struct {                                          // PAD: label records, X-PAD groups, run records
+        int n = 0;
+        devarr<dabgpu_pad_label> labels;
+        slot_store<dabgpu_datagroup> groups;
+        devarr<dabgpu_pad_run> runs;
+        dynamic_label_cb on_label;
+        pad_datagroup_cb on_datagroup;
+    } pad_;
+    struct {                                          // on_pad_object (first use): a MOT state per stream and PAD slot
+        devarr<uint8_t> states;
+        devarr<dabgpu_packet_run> group_runs;         // what dabgpu_mot_groups reads: the PAD layer's run records
+        slot_store<dabgpu_mot_object> objects;
+        devarr<dabgpu_mot_run> runs;
+        pad_object_cb on_object;
+    } pad_mot_;
+    struct {                                          // layer II PCM
+        int n = 0;
+        devarr<int16_t> pcm;
+        devarr<dabgpu_mp2_info> info;
+        pcm_cb on_pcm;
+    } mp2_;
+    struct {                                          // audio output (buffers on first use): samples and pair counts
+        int n = 0;
+        devarr<float> samples;
+        devarr<int32_t> pairs;
+        audio_cb on_audio;
+    } audio_;
+    struct {                                          // packet mode: data groups, run records, per-CIF records
+        int n = 0, cap = 0;                           // cap: the largest stored group
+        slot_store<dabgpu_datagroup> groups;
+        devarr<dabgpu_packet_run> runs;
+        devarr<dabgpu_packet_info> info;
+        datagroup_cb on_datagroup;
+        packet_quality_cb on_quality;
+    } packet_;
+    struct {                                          // MOT objects of the packet entries
+        int n = 0;
+        slot_store<dabgpu_mot_object> objects;
+        devarr<dabgpu_mot_run> runs;
+        mot_object_cb on_object;
+    } mot_;
+    struct {                                          // IP (first use): a result per group of the packet slots
+        slot_store<dabgpu_ip_result> results;
+        devarr<dabgpu_ip_run> runs;
+        datagram_cb on_datagram;
+        ip_quality_cb on_quality;
+    } ip_;
     config cfg_;
     dabgpu_pipe *pipe_ = nullptr;
-    devbuf iq_, fic_, crc_, msc_, sf_, sfi_, pcm_, mp2i_, pkb_, pkg_, pkr_, pki_;
-    int nmp_ = 0, npk_ = 0, pk_cap_ = 0;
-    devbuf aus_, aun_;                                // the audio output layer's samples and pair counts (first use)
-    int naudio_ = 0;
-    audio_cb audio_cb_;
-    size_t pk_slots_ = 0, pk_arena_ = 0;
-    devbuf mob_, moo_, mor_;                          // the MOT layer's arenas, object records, run records
-    int nmot_ = 0;
-    size_t mot_arena_ = 0;
-    mot_object_cb mot_cb_;
-    devbuf ipb_, ipo_, ipr_;                          // the IP layer's arenas, result records, run records (first use)
-    size_t ip_arena_ = 0;
-    datagram_cb ip_cb_;
-    ip_quality_cb ipq_cb_;
-    devbuf pdl_, pdg_, pdb_, pdr_;                    // the PAD layer's label and group records, arenas, run records
-    devbuf pms_, pmr_, pmo_, pmb_, pmm_;              // on_pad_object: MOT states, packet-run and object records, bodies, runs
-    int npad_ = 0, pad_slots_ = 0;
-    size_t pad_arena_ = 0, pad_mot_arena_ = 0;
-    dynamic_label_cb label_cb_;
-    pad_datagroup_cb pad_dg_cb_;
-    pad_object_cb pad_obj_cb_;
-    pcm_cb pcm_cb_;
-    datagroup_cb dg_cb_;
-    packet_quality_cb pq_cb_;
+    devbuf iq_;                                       // the streams' samples as loaded (cf32, s16 or u8 pairs)
     int64_t stride_ = 0;
     std::vector<int64_t> navail_;
-    int msc_stride_ = 0, sf_stride_ = 0, ndp_ = 0, maxbits_ = 0, nsub_ = 0;
     std::vector<std::vector<dabgpu_subch>> tab_;      // [stream] the applied tables
-    std::vector<fib_processor> fibs_;                 // auto_layout: [stream]
     std::vector<std::vector<dabgpu_subch>> parsed_;   // auto_layout: [stream] parsed at the end of the last step
-    devbuf fce_, fct_, fcr_;                          // fic_on_gpu: the FIC layer's events, tables, run records
-    std::vector<dabgpu_fic_table> fic_tab_;           // fic_on_gpu: [stream] the tables of this step
-    ensemble_name_cb ens_name_cb_;
-    service_name_cb svc_name_cb_;
-    int64_t fib_frame_ = 0;                           // the frame of the FIB the host's fib_processor is parsing
-    std::vector<int64_t> frames_done_;     // frames delivered per stream
-    fib_cb fib_cb_;
-    msc_cb msc_cb_;
-    sf_cb sf_cb_;
+    std::vector<int64_t> frames_done_;                // frames delivered per stream
+    std::vector<dabgpu_frame_info> frame_info_;       // [stream][frame] of this step
+    void start_auto_layout();
+    // the loaders' shared start (one array per stream, stride_, iq_ sized) and end
+    void begin_load(const char *who, size_t given, const std::vector<int64_t> &n, size_t bytes_per_pair);
+    void finish_load(const std::vector<int64_t> &n, int format);
+    char *stream_iq(int s, size_t bytes_per_pair) const { return static_cast<char *>(iq_.get()) + bytes_per_pair * stride_ * s; }
+    bool gpu_fic() const { return cfg_.auto_layout && cfg_.fic_on_gpu; }
+    int wanted() const;                               // the DABGPU_SUBCH_* bits auto_layout asks the FIC for
+    // step(), in this order
+    bool run_pipeline();
+    void deliver_fic_names();
+    void deliver_fibs();
+    void deliver_msc();
+    void run_dabplus();
+    void run_pad();
+    void run_pad_mot(const std::vector<dabgpu_pad_run> &run, std::vector<dabgpu_mot_run> &mrun);
+    void deliver_pad(const std::vector<dabgpu_pad_run> &run, const std::vector<dabgpu_mot_run> &mrun);
+    void run_mp2();
+    void run_audio();
+    void run_packet();
+    void run_mot();
+    void run_ip();
+    void advance_frames();
+    void apply_tables();
 };
 
 }  // namespace dabgpu

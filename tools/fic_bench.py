@@ -5,8 +5,8 @@ synthesiser's FIC with FIGs (figs=1) of an ensemble with four subchannels, every
 phase of it.  Prints one JSON line:
   - the operator alone: wall ms from dabgpu_fib_parse to dabgpu_sync with the inputs resident and
     the device otherwise idle, first call (new databases) and steady, with what the calls parsed;
-  - the host path over the same FIBs on one core: ensembleDecoder::step()'s own loop -- each FIB
-    expanded to one bit per byte, then fib_processor::process_FIB -- through tests/cpp's
+  - the host path over the same FIBs on one core: ensembleDecoder::step()'s own loop
+    (deliver_fibs, host/ensemble_decoder.cpp) -- each FIB expanded to one bit per byte, then fib_processor::process_FIB -- through tests/cpp's
     libficwrap.so (fw_fib is exactly that) for one slot's FIBs, times the slots, best of three,
     without the PCIe copy of the FIC the host path also needs.
 Under rocprofv3 --kernel-trace --stats the kernel's own time comes from its table.
