@@ -384,6 +384,32 @@ int         dabgpu_event_elapsed(dabgpu_ctx *ctx, int slot_a, int slot_b, float 
 #define DABGPU_IQ_S16  2
 int dabgpu_iq_convert(dabgpu_ctx *ctx, int format, const void *src_d, int64_t n_pairs, float *iq_d);
 
+/* ---- input rate conversion ------------------------------------------- */
+/* Streams sampled at in_rate Hz to the 2.048 MHz cf32 every OFDM entry point reads: the linear
+ * interpolation of airspyHandler::data_available (airspy-handler.cpp:138-148, 333-359), bit for
+ * bit.  With M = in_rate / 1000, block b of a stream reads its samples M b .. M b + M and writes
+ * its outputs 2048 b .. 2048 b + 2047:
+ *   out[2048 b + j] = x[M b + base[j] + 1] * frac[j] + x[M b + base[j]] * (1.0f - frac[j])
+ * (base / frac: the handler's mapTable_int / mapTable_float; every product, the difference and the
+ * sum rounded to fp32 on its own).  Stream s holds n_in_h[s] samples in `format` at sample
+ * src_stride * s of src_d and gets B = (n_in_h[s] < 1 ? 0 : (n_in_h[s] - 1) / M) blocks: its
+ * output goes to sample iq_stride * s of iq_d (strides in I/Q pairs, as in dabgpu_pipe_run),
+ * n_out_h[s] = 2048 B, n_used_h[s] = M B, and nothing past its n_out_h[s] samples is written.
+ * Sample n_used_h[s] is the first sample of the stream's next call: there is no device-side state.
+ * format: DABGPU_IQ_S12 (the handler's own), DABGPU_IQ_F32 (the samples as they are: cf32
+ * recordings at another rate), DABGPU_IQ_S16 / DABGPU_IQ_U8 with dabgpu_iq_convert's scalings;
+ * the arithmetic after the conversion to float is the same for all four.
+ * DABGPU_E_ARG: in_rate no multiple of 1000 or outside 2048000 .. 10000000, an unknown format,
+ * n_streams < 1, a negative count, iq_stride < 2048 B or src_stride < n_in_h[s] for some stream,
+ * src_d or iq_d not aligned to one I/Q pair of its type.  Asynchronous on the context stream
+ * (n_out_h / n_used_h are set on return and n_in_h is read before it; dabgpu_sync to wait for
+ * the samples). */
+#define DABGPU_IQ_S12 3   /* int16 I/Q pairs holding the Airspy's 12-bit samples: x / 2048
+                             (airspy-handler.cpp:340-341); rate conversion only */
+int dabgpu_rate_convert(dabgpu_ctx *ctx, int in_rate, int format,
+                        const void *src_d, int64_t src_stride, int n_streams, const int64_t *n_in_h,
+                        float *iq_d, int64_t iq_stride, int64_t *n_out_h, int64_t *n_used_h);
+
 /* ---- OFDM front end (L3) ---------------------------------------------- */
 
 /* phaseReference::findIndex batched (phasereference.cpp:60-88): for each of n

@@ -57,6 +57,7 @@ struct DemodAux {
 constexpr int RING8_BIAS = 127;
 constexpr int KERR_FRAME = 1;      // frame descriptor outside its stream / bad NCO phase
 constexpr int KERR_VITERBI = 2;    // Viterbi source outside its buffer
+constexpr int KERR_RATE = 4;       // rate conversion: a table entry outside its block or its staged piece
 
 struct AcqJob {
     int64_t iq_base;
@@ -405,6 +406,30 @@ struct AudioJob {
     int32_t *n_out;
     int64_t out_pairs, out_a, out_c;
 };
+
+// input rate conversion (k_rate.hip)
+struct RateTab {                    // airspyHandler's two tables for one rate (host/rate_converter.h)
+    float frac[2048];               // mapTable_float
+    int16_t base[2048];             // mapTable_int
+};
+constexpr int RATE_LDS_BYTES = 16384;   // input samples a workgroup stages at a time, as the stream holds them
+constexpr int RATE_GROUP = 64;          // streams per launch: their block counts travel as kernel arguments
+// Stream s (< n_streams <= RATE_GROUP) holds its samples in `format` at sample src_stride * s of src; block
+// b < blocks[s] of it (inputs M b .. M b + M) becomes samples out_stride * s + 2048 b .. + 2047 of out.  A
+// workgroup does its block in `passes` pieces of 2048 / passes outputs (1, 2, 4 or 8: the caller's choice,
+// so that a piece's input span fits RATE_LDS_BYTES).
+struct RateJob {
+    const void *src;
+    int64_t src_stride;
+    float *out;
+    int64_t out_stride;
+    const RateTab *tab;             // device
+    int32_t *err;                   // device error word
+    int32_t M, passes, n_streams;
+    int32_t first[8], last[8];      // per piece: the first and last sample of the block it reads (from the table)
+    int32_t blocks[RATE_GROUP];
+};
+hipError_t launch_rate_convert(hipStream_t st, int format, const RateJob &job);
 
 // iq: samples in format fmt (DABGPU_IQ_*); frame descriptors count samples
 hipError_t launch_prs_sync(hipStream_t st, const void *iq, int fmt, const dabgpu_frame *fr, int n, const OfdmTables &T,

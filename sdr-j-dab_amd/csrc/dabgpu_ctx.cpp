@@ -10,6 +10,7 @@
 #include <algorithm>
 #include "dabgpu_internal.h"
 #include "../host/audio_fir.h"
+#include "../host/rate_converter.h"
 #include "stage_layout.h"
 #include "dab_tables.h"
 
@@ -320,6 +321,22 @@ int dab::audio_tables(dabgpu_ctx *c, const float **out) {
     return 0;
 }
 
+// airspyHandler's mapTable_int / mapTable_float of a rate (host/rate_converter.h: products and
+// differences that are exact, so this file's contraction cannot change them)
+int dab::rate_tables(dabgpu_ctx *c, int rate, const RateEntry **out) {
+    auto it = c->ratetab.find(rate);
+    if (it == c->ratetab.end()) {
+        std::vector<RateTab> h(1);
+        dabgpu::rate_tables(rate, h[0].base, h[0].frac);
+        RateEntry e;
+        e.base.assign(h[0].base, h[0].base + 2048);
+        HIPCHK(e.tab.put(h));
+        it = c->ratetab.emplace(rate, std::move(e)).first;
+    }
+    *out = &it->second;
+    return 0;
+}
+
 // ----------------------------------------------------------------- context
 int dab::scratch(dabgpu_ctx *c, int slot, size_t bytes, void **p) {
     DevBuf<uint8_t> &b = c->scratch[slot];
@@ -349,8 +366,8 @@ int dab::kernel_errors(dabgpu_ctx *c) {
     return bounds_error(e);
 }
 int dab::bounds_error(int32_t e) {
-    return fail(DABGPU_E_BOUNDS, "kernel refused out-of-bounds work:%s%s", (e & KERR_FRAME) ? " frame descriptor" : "",
-                (e & KERR_VITERBI) ? " viterbi source" : "");
+    return fail(DABGPU_E_BOUNDS, "kernel refused out-of-bounds work:%s%s%s", (e & KERR_FRAME) ? " frame descriptor" : "",
+                (e & KERR_VITERBI) ? " viterbi source" : "", (e & KERR_RATE) ? " rate conversion table" : "");
 }
 
 // symbols 1..75 of a frame are split over `chunks` workgroups of k_demod (each
@@ -537,6 +554,60 @@ int dabgpu_iq_convert(dabgpu_ctx *c, int format, const void *src, int64_t n_pair
     // the vector path reads 16 B per 16 values: the source must be 16-byte aligned
     if (((uintptr_t)src & 15) || ((uintptr_t)iq & 15)) return fail(DABGPU_E_ARG, "IQ buffers must be 16-byte aligned");
     HIPCHK(launch_iq_convert(c->stream, format, src, 2 * n_pairs, iq));
+    return 0;
+}
+int dabgpu_rate_convert(dabgpu_ctx *c, int in_rate, int format, const void *src, int64_t src_stride, int n_streams,
+                        const int64_t *n_in, float *iq, int64_t iq_stride, int64_t *n_out, int64_t *n_used) {
+    if (!c || !n_in || !n_out || !n_used || n_streams < 1) return fail(DABGPU_E_ARG, "bad args");
+    if (!dabgpu::rate_valid(in_rate)) return fail(DABGPU_E_ARG, "in_rate %d: whole kHz in 2048000 .. 10000000", in_rate);
+    if (!dabgpu::rate_format_valid(format)) return fail(DABGPU_E_ARG, "unknown IQ format %d", format);
+    const int M = in_rate / 1000, bps = dabgpu::rate_format_bytes(format);
+    if (((uintptr_t)src & (uintptr_t)(bps - 1)) || ((uintptr_t)iq & 7))
+        return fail(DABGPU_E_ARG, "src_d and iq_d must be aligned to one I/Q pair (%d and 8 bytes)", bps);
+    bool any = false;
+    for (int s = 0; s < n_streams; s++) {
+        const int64_t n = n_in[s], B = n < 1 ? 0 : (n - 1) / M;
+        if (n < 0) return fail(DABGPU_E_ARG, "stream %d: %lld samples", s, (long long)n);
+        if (src_stride < n) return fail(DABGPU_E_ARG, "stream %d: src_stride %lld < %lld samples", s, (long long)src_stride, (long long)n);
+        if (B > 0x7FFFFFFF || iq_stride < 2048 * B)
+            return fail(DABGPU_E_ARG, "stream %d: iq_stride %lld < %lld outputs", s, (long long)iq_stride, (long long)(2048 * B));
+        any = any || B > 0;
+    }
+    if (any && (!src || !iq)) return fail(DABGPU_E_ARG, "null samples");
+    for (int s = 0; s < n_streams; s++) {
+        const int64_t B = n_in[s] < 1 ? 0 : (n_in[s] - 1) / M;
+        n_out[s] = 2048 * B;
+        n_used[s] = M * B;
+    }
+    if (!any) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    const RateEntry *e = nullptr;
+    if (int rc = rate_tables(c, in_rate, &e)) return rc;
+    RateJob J;
+    memset(&J, 0, sizeof J);
+    J.src_stride = src_stride;
+    J.out_stride = iq_stride;
+    J.tab = e->tab;
+    J.err = c->err;
+    J.M = M;
+    // the fewest pieces (of 2048 / passes outputs each) whose input spans all fit the kernel's LDS image
+    for (J.passes = 1; J.passes <= 8; J.passes *= 2) {
+        bool fits = true;
+        for (int p = 0, S = 2048 / J.passes; p < J.passes; p++) {
+            J.first[p] = e->base[p * S];
+            J.last[p] = e->base[p * S + S - 1] + 1;
+            fits = fits && (J.last[p] - J.first[p] + 1) * bps <= RATE_LDS_BYTES;
+        }
+        if (fits) break;
+    }
+    if (J.passes > 8) return fail(DABGPU_E_STATE, "rate %d: a piece's samples do not fit %d bytes", in_rate, RATE_LDS_BYTES);
+    for (int s0 = 0; s0 < n_streams; s0 += RATE_GROUP) {
+        J.n_streams = std::min(RATE_GROUP, n_streams - s0);
+        J.src = (const char *)src + src_stride * s0 * bps;
+        J.out = iq + 2 * iq_stride * s0;
+        for (int s = 0; s < J.n_streams; s++) J.blocks[s] = (int32_t)(n_out[s0 + s] / 2048);
+        HIPCHK(launch_rate_convert(c->stream, format, J));
+    }
     return 0;
 }
 int dabgpu_memset_d(dabgpu_ctx *c, void *dst, int value, size_t bytes) {

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <algorithm>
+#include <map>
 #include <utility>
 #include <vector>
 #include "../../include/dabgpu.h"
@@ -104,6 +105,13 @@ struct Stream {
     operator hipStream_t() const { return s; }
 };
 
+// airspyHandler's tables for one input rate, on the device and (mapTable_int) on the host: the
+// samples a piece of consecutive outputs reads decide k_rate_convert's passes
+struct RateEntry {
+    DevBuf<RateTab> tab;
+    std::vector<int16_t> base;      // [2048]
+};
+
 }  // namespace dab
 
 // Members are destroyed in reverse order of declaration: the stream comes last, so it has
@@ -121,6 +129,7 @@ struct dabgpu_ctx {
     dab::DevBuf<uint8_t> fic_inv;  // the FIC profile's inverse depuncturing table (make_inv)
     dab::DevBuf<uint8_t> mp2tab;   // layer II tables (Mp2Tabs, mp2_host_tables)
     dab::DevBuf<float> audiotab;   // audioSink's filter kernels (audio_host_fir)
+    std::map<int, dab::RateEntry> ratetab;   // rate conversion tables by input rate, each made at the rate's first use
     dab::DevBuf<int32_t> err;      // device error word (KERR_* bits)
     dab::PinBuf<int32_t> h_err;    // its pinned host copy (read after every synchronising pass)
     dab::OfdmTables T{};
@@ -164,5 +173,6 @@ std::vector<uint8_t> mp2_host_tables();                  // an Mp2Tabs (k_mp2.hi
 int mp2_tables(dabgpu_ctx *c, const Mp2Tabs **out);      // the context's device copy, made at first use
 const std::vector<float> &audio_host_fir();              // DABGPU_TABLE_AUDIO_FIR, float[3][5]
 int audio_tables(dabgpu_ctx *c, const float **out);      // the context's device copy, made at first use
+int rate_tables(dabgpu_ctx *c, int rate, const RateEntry **out);   // the context's entry for a rate, made at first use
 
 }  // namespace dab

@@ -375,6 +375,7 @@ def lib() -> C.CDLL:
             "dabgpu_pipe_acquire_wait": ([vp], i32),
             "dabgpu_pipe_set_display_token": ([vp, i32], i32),
             "dabgpu_iq_convert": ([vp, i32, vp, i64, vp], i32),
+            "dabgpu_rate_convert": ([vp, i32, i32, vp, i64, i32, vp, vp, i64, vp, vp], i32),
             "dabgpu_event_record": ([vp, i32], i32),
             "dabgpu_kernel_errors": ([vp], i32),
             "dabgpu_event_elapsed": ([vp, i32, i32, C.POINTER(C.c_float)], i32),
@@ -461,6 +462,7 @@ def _p(a: np.ndarray) -> C.c_void_p:
 
 
 IQ_F32, IQ_U8, IQ_S16 = 0, 1, 2   # sample formats (dabgpu_iq_convert, dabgpu_pipe_set_iq_format)
+IQ_S12 = 3                        # int16 pairs holding the Airspy's 12-bit samples, x / 2048 (dabgpu_rate_convert only)
 TABLE_PRS, TABLE_MAPPER, TABLE_REFARG, TABLE_OSC, TABLE_NCO = 1, 2, 3, 4, 5
 
 
@@ -628,6 +630,19 @@ class Context:
         """dabgpu_iq_convert: recorded samples (IQ_U8 / IQ_S16) in src -> cf32 in dst"""
         _chk(lib().dabgpu_iq_convert(self.h, fmt, C.c_void_p(src.ptr.value + src_off), n_pairs,
                                      C.c_void_p(dst.ptr.value + dst_off)), "dabgpu_iq_convert")
+
+    def rate_convert(self, rate: int, fmt: int, src: "DevBuf", src_stride: int, n_in, dst: "DevBuf", dst_stride: int,
+                     src_off: int = 0, dst_off: int = 0):
+        """dabgpu_rate_convert: streams sampled at rate Hz (n_in[s] samples of format fmt at sample
+        src_stride * s of src) -> 2.048 MHz cf32 at sample dst_stride * s of dst, as airspyHandler
+        converts them.  Asynchronous (sync() to wait).  Returns (n_out, n_used), int64 per stream:
+        sample n_used[s] of a stream is the first sample of its next call."""
+        n_in = np.ascontiguousarray(n_in, np.int64)
+        n_out, n_used = np.zeros(len(n_in), np.int64), np.zeros(len(n_in), np.int64)
+        _chk(lib().dabgpu_rate_convert(self.h, int(rate), int(fmt), C.c_void_p(src.ptr.value + src_off), int(src_stride),
+                                       len(n_in), _p(n_in), C.c_void_p(dst.ptr.value + dst_off), int(dst_stride),
+                                       _p(n_out), _p(n_used)), "dabgpu_rate_convert")
+        return n_out, n_used
 
     def load_iq_file(self, path: str, max_pairs: Optional[int] = None, chunk_pairs: int = 1 << 25):
         """Read a .raw (u8) or .sdr (WAV PCM16) recording into HBM as interleaved cf32,

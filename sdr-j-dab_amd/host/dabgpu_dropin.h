@@ -622,6 +622,12 @@ public:
     // (.raw bytes), n[s] pairs each, copied to HBM as they are -- the pipeline converts them
     // in its sample loads with the readers' scaling (wavfiles.cpp:172, rawfiles.cpp:115-117)
     void load_recorded(int format, const std::vector<const void *> &samples, const std::vector<int64_t> &n);
+    // streams sampled at rate Hz (whole kHz, 2048000 .. 10000000), n[s] I/Q pairs each in format
+    // DABGPU_IQ_S12 (the Airspy's int16 pairs, x / 2048), _S16, _U8 or _F32: uploaded as they are, in
+    // pieces, and converted on the device to the 2.048 MHz cf32 the decoder then holds, as
+    // airspyHandler::data_available converts them (dabgpu_rate_convert; rate_converter.h is the same
+    // on the host).  Stream s then holds 2048 * ((n[s] - 1) / (rate / 1000)) samples, as after load.
+    void load_rate(int rate, int format, const std::vector<const void *> &samples, const std::vector<int64_t> &n);
     // one recording file per stream, all .sdr (RIFF/WAVE PCM16, 2 channels, 2048000 Hz, as
     // wavFiles accepts them: wavfiles.cpp:56-69) or all .raw (u8 I/Q): read in pieces straight
     // into HBM, unconverted.  Throws dabgpu::error for any other file.

@@ -9,6 +9,7 @@
 
 #include "dropin_chk.h"
 #include "ensemble_util.h"
+#include "rate_converter.h"
 
 namespace dabgpu {
 
@@ -174,6 +175,41 @@ void ensembleDecoder::load_recorded(int format, const std::vector<const void *> 
     for (int s = 0; s < cfg_.n_streams; s++)
         chk(dabgpu_memcpy_h2d(thread_context(), stream_iq(s, bps), samples[s], bps * n[s]), "dabgpu_memcpy_h2d");
     finish_load(n, format);
+}
+
+void ensembleDecoder::load_rate(int rate, int format, const std::vector<const void *> &samples, const std::vector<int64_t> &n) {
+    const char *who = "ensembleDecoder::load_rate: one sample array per stream";
+    if (!rate_valid(rate) || !rate_format_valid(format))
+        throw error(DABGPU_E_ARG, "ensembleDecoder::load_rate: a rate of whole kHz in 2048000 .. 10000000 and a DABGPU_IQ_* format");
+    if ((int)n.size() != cfg_.n_streams) throw error(DABGPU_E_ARG, who);
+    const int64_t M = rate / 1000, bps = rate_format_bytes(format);
+    std::vector<int64_t> n_out(n.size());
+    int64_t most = 0;                                        // blocks of the longest stream
+    for (size_t s = 0; s < n.size(); s++) {
+        if (n[s] < 0) throw error(DABGPU_E_ARG, who);
+        n_out[s] = 2048 * (n[s] < 1 ? 0 : (n[s] - 1) / M);
+        most = std::max(most, n_out[s] / 2048);
+    }
+    begin_load(who, samples.size(), n_out, sizeof(float) * 2);
+    // K blocks of every stream at a time through a staging buffer of at most 256 MB: a piece holds M K + 1
+    // samples, the last of them the first of the next piece (dabgpu_rate_convert's n_used)
+    const int64_t K = std::max<int64_t>(1, std::min(most, ((int64_t)1 << 28) / (bps * M * cfg_.n_streams)));
+    const int64_t piece = M * K + 1;
+    devbuf stage((size_t)(bps * piece * cfg_.n_streams));
+    std::vector<int64_t> count(n.size()), made(n.size()), used(n.size());
+    for (int64_t first = 0; first < most; first += K) {
+        for (int s = 0; s < cfg_.n_streams; s++) {
+            count[s] = std::max<int64_t>(0, std::min(piece, n[s] - M * first));
+            if (count[s])
+                chk(dabgpu_memcpy_h2d(thread_context(), static_cast<char *>(stage.get()) + bps * piece * s,
+                                      static_cast<const char *>(samples[s]) + bps * M * first, (size_t)(bps * count[s])), "dabgpu_memcpy_h2d");
+        }
+        chk(dabgpu_rate_convert(thread_context(), rate, format, stage.get(), piece, cfg_.n_streams, count.data(),
+                                reinterpret_cast<float *>(stream_iq(0, sizeof(float) * 2)) + 2 * 2048 * first, stride_, made.data(), used.data()),
+            "dabgpu_rate_convert");
+    }
+    chk(dabgpu_sync(thread_context()), "dabgpu_sync");       // (the staging buffer goes)
+    finish_load(n_out, DABGPU_IQ_F32);
 }
 
 void ensembleDecoder::load_files(const std::vector<std::string> &paths) {
