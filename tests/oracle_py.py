@@ -169,9 +169,14 @@ class MP4:
         oracle().orc_mp4_init(C.byref(self.st), bitrate)
 
     def add(self, bits):
-        """-> dict(status, out[110*RSDims], n_corrected, num_aus, au_start, au_crc)"""
+        """-> dict(status, out[110*RSDims], n_corrected, num_aus, au_start, au_crc).
+        orc_superframe reads an AU where the start table puts it, up to 4095 + 959 + 2 bytes
+        behind the superframe's end for a crafted table: the buffer is zero that far, which is
+        the GPU layer's rule (bytes past the superframe read as zero; the reference reads
+        uninitialised memory there)."""
         rs = self.br // 8
-        out = np.zeros(110 * rs, np.uint8)
+        buf = np.zeros(110 * rs + 4096 + 962, np.uint8)
+        out = buf[:110 * rs]
         nc = C.c_int16(0)
         na = C.c_int(0)
         aus = np.zeros(8, np.int16)
