@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/dabgpu.h"
+#include "msc_feed.h"
 
 namespace dab {
 
@@ -176,14 +177,9 @@ struct DpState {
     int32_t fill, blocks;           // blockFillIndex, blocksInBuffer (mp4processor.cpp:86-87)
 };
 struct DpJob {
-    const uint8_t *msc;             // MSC bits of the run: [S][ncif][nsub][msc_stride]
-    int32_t msc_stride, ncif, nsub, ndp, nstreams;
-    int32_t packed;                 // msc holds bytes (8 bits msb first), else one bit per byte
-    const int64_t *cif0s;           // [stream] CIF index of the run's first CIF slot
-    const int32_t *ncifs;           // [stream] CIFs the stream delivered in the run
-    const int32_t *dp_sub;          // [S][ndp] table entry of each DAB+ slot of the stream, -1: absent
-    const int16_t *dp_br;           // [S][ndp] its bitRate
-    const int64_t *dp_since;        // [S][ndp] its entry's since_cif (VitJob::ent_since)
+    MscFeed feed;
+    SlotMapView map;                // [S][ndp] the DAB+ slots
+    int32_t ndp;
     uint8_t *ring;                  // [S][ndp][120*DP_MAX_RS] 5-CIF byte rings
     DpState *state;                 // [S][ndp]
     uint8_t *code;                  // [S][ndp][ncif] scratch: 0 fire code failed, 2 rejected, 3 decoded
@@ -228,14 +224,9 @@ struct Mp2SyncState {               // mp2Processor's synchroniser, zero for a n
     int32_t half_rate;              // baudRate: 0 48000, 1 24000
 };
 struct Mp2SyncJob {
-    const uint8_t *msc;             // MSC bits of the run: [S][ncif][nsub][msc_stride]
-    int32_t msc_stride, ncif, nsub, nmp, nstreams;
-    int32_t packed;                 // msc holds bytes (8 bits msb first), else one bit per byte
-    const int64_t *cif0s;           // [stream] CIF index of the run's first CIF slot
-    const int32_t *ncifs;           // [stream] CIFs the stream delivered in the run
-    const int32_t *mp_sub;          // [S][nmp] table entry of each MP2 slot of the stream, -1: absent
-    const int16_t *mp_br;           // [S][nmp] its bitRate
-    const int64_t *mp_since;        // [S][nmp] its entry's since_cif
+    MscFeed feed;
+    SlotMapView map;                // [S][nmp] the MP2 slots
+    int32_t nmp;
     Mp2SyncState *state;            // [S][nmp]
     uint8_t *part;                  // [S][nmp][fstride] the frame being collected, packed
     uint8_t *frames;                // [S * nmp][ncif][fstride] the frame that completed in each CIF
@@ -254,16 +245,11 @@ struct PkState {                    // an mscDatagroup's assembler, {0, -1, 0, 0
     int32_t reserved;
 };
 struct PkJob {
-    const uint8_t *msc;             // MSC bits of the run: [S][ncif][nsub][msc_stride]
-    int32_t msc_stride, ncif, nsub, npk, nstreams;
-    int32_t packed;                 // msc holds bytes (8 bits msb first), else one bit per byte
+    MscFeed feed;
+    SlotMapView map;                // [S][npk] the packet slots
+    int32_t npk;
     int32_t ncell;                  // cells per CIF the buffers hold: max_bitrate / 8
     int32_t cap;                    // max_group_bytes
-    const int64_t *cif0s;           // [stream] CIF index of the run's first CIF slot
-    const int32_t *ncifs;           // [stream] CIFs the stream delivered in the run
-    const int32_t *pk_sub;          // [S][npk] table entry of each packet slot of the stream, -1: absent
-    const int16_t *pk_br;           // [S][npk] its bitRate
-    const int64_t *pk_since;        // [S][npk] its entry's since_cif
     PkState *state;                 // [S][npk]
     const uint8_t *carry_in;        // [S][npk][cap] the series in flight before the run
     uint8_t *carry_out;             // ... and after it (not the memory of carry_in)

@@ -127,18 +127,18 @@ int layer_ready(const dabgpu_pipe *p, int kind) {
     return 0;
 }
 
-// a cleared job over the last run's MSC rows (DpJob, Mp2SyncJob and PkJob name these fields alike)
-template <class Job>
-void msc_feed(const dabgpu_pipe *p, Job &J) {
-    memset(&J, 0, sizeof J);
-    J.msc = p->feed.last_msc;
-    J.msc_stride = p->feed.last_msc_stride;
-    J.packed = p->feed.last_msc_packed ? 1 : 0;
-    J.ncif = 4 * p->F;
-    J.nsub = p->NSUB;
-    J.nstreams = p->S;
-    J.cif0s = p->cif0_dev(p->cur);
-    J.ncifs = p->ncif_dev(p->cur);
+// the last run's MSC rows
+MscFeed msc_feed(const dabgpu_pipe *p) {
+    MscFeed f;
+    f.msc = p->feed.last_msc;
+    f.msc_stride = p->feed.last_msc_stride;
+    f.ncif = 4 * p->F;
+    f.nsub = p->NSUB;
+    f.nstreams = p->S;
+    f.packed = p->feed.last_msc_packed ? 1 : 0;
+    f.cif0s = p->cif0_dev(p->cur);
+    f.ncifs = p->ncif_dev(p->cur);
+    return f;
 }
 
 // A layer's pass on the last run's back-end stream (behind its channel decoding and the layers
@@ -461,12 +461,10 @@ int dabgpu_pipe_dabplus(dabgpu_pipe *p, uint8_t *sf_bytes, int32_t sf_stride, da
     if (!p || !sf_bytes || !info) return fail(DABGPU_E_ARG, "null arg");
     if (int rc = layer_ready(p, slots::DABPLUS)) return rc;
     if (sf_stride < 110 * p->dp.max_rs) return fail(DABGPU_E_ARG, "sf_stride %d < %d", sf_stride, 110 * p->dp.max_rs);
-    DpJob J;
-    msc_feed(p, J);
+    DpJob J = {};
+    J.feed = msc_feed(p);
+    J.map = p->dp.map.view();
     J.ndp = p->NDP;
-    J.dp_sub = p->dp.map.sub_d;
-    J.dp_br = p->dp.map.br_d;
-    J.dp_since = p->dp.map.since_d;
     J.ring = p->dp.ring_d;
     J.state = p->dp.state_d;
     J.code = p->dp.code_d;
@@ -605,12 +603,10 @@ int dabgpu_pipe_mp2(dabgpu_pipe *p, int16_t *pcm, dabgpu_mp2_info *info) {
     if (!p || !pcm || !info) return fail(DABGPU_E_ARG, "null arg");
     if (int rc = layer_ready(p, slots::MP2)) return rc;
     Mp2Layer &m = p->mp2;
-    Mp2SyncJob Y;
-    msc_feed(p, Y);
+    Mp2SyncJob Y = {};
+    Y.feed = msc_feed(p);
+    Y.map = m.map.view();
     Y.nmp = p->NMP;
-    Y.mp_sub = m.map.sub_d;
-    Y.mp_br = m.map.br_d;
-    Y.mp_since = m.map.since_d;
     Y.state = m.sync_d;
     Y.part = m.part_d;
     Y.frames = m.frames_d;
@@ -695,14 +691,12 @@ int dabgpu_pipe_packet(dabgpu_pipe *p, uint8_t *bytes, dabgpu_datagroup *groups,
     if (!p || !bytes || !groups || !run || !info) return fail(DABGPU_E_ARG, "null arg");
     if (int rc = layer_ready(p, slots::PACKET)) return rc;
     PacketLayer &k = p->pk;
-    PkJob J;
-    msc_feed(p, J);
+    PkJob J = {};
+    J.feed = msc_feed(p);
+    J.map = k.map.view();
     J.npk = p->NPK;
     J.ncell = k.ncell;
     J.cap = k.cap;
-    J.pk_sub = k.map.sub_d;
-    J.pk_br = k.map.br_d;
-    J.pk_since = k.map.since_d;
     J.state = k.state_d;
     J.carry_in = k.carry_d[k.cur];
     J.carry_out = k.carry_d[k.cur ^ 1];

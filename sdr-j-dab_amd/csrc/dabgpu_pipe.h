@@ -49,6 +49,7 @@ struct SlotMap {
         if (e == hipSuccess) e = br_d.alloc(n);
         return e != hipSuccess ? e : since_d.alloc(n);
     }
+    dab::SlotMapView view() const { return {sub_d, br_d, since_d}; }
 };
 // DAB+ superframe layer (mp4Processor per DAB+ subchannel and stream)
 struct DabPlus {

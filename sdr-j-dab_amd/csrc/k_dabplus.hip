@@ -180,17 +180,6 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// byte i of one CIF's decoded bits, 8 bits msb first (addtoFrame, mp4processor.cpp:115-121)
-__device__ __forceinline__ uint32_t pack_byte(const uint8_t *bits, int i) {
-    const uint2 w = *(const uint2 *)(bits + 8 * i);
-    uint32_t t = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) t = (t << 1) | ((w.x >> (8 * j)) & 1u);
-#pragma unroll
-    for (int j = 0; j < 4; j++) t = (t << 1) | ((w.y >> (8 * j)) & 1u);
-    return t;
-}
-
 // Byte p of the superframe candidate ending at CIF cl of this run: the 5 blocks
 // cl-4..cl in delivery order, i.e. the reference's ring read from its oldest block
 // (mp4processor.cpp:128-140).  Blocks before the run come from the carry (the
@@ -199,8 +188,7 @@ __device__ __forceinline__ uint32_t window_byte(const DpJob &J, const uint8_t *c
                                                 int nbytes, int cl, int p) {
     const int b = p / nbytes, w = p - b * nbytes, q = cl - 4 + b;
     if (q < 0) return carry[(q + 4) * nbytes + w];
-    const uint8_t *src = J.msc + (((int64_t)stream * J.ncif + q) * J.nsub + sub) * J.msc_stride;
-    return J.packed ? src[w] : pack_byte(src, w);
+    return row_byte(msc_row(J.feed, stream, q, sub), J.feed.packed, w);
 }
 
 // Bytes 4d .. 4d+3 of the same window as one little-endian word (packed MSC with 4-byte
@@ -209,10 +197,10 @@ __device__ __forceinline__ uint32_t window_word(const DpJob &J, const uint8_t *c
                                                 int nbytes, int cl, int d) {
     const int p = 4 * d, b = p / nbytes, w = p - b * nbytes, q = cl - 4 + b;
     if (q < 0) return *(const uint32_t *)(carry + (q + 4) * nbytes + w);
-    return *(const uint32_t *)(J.msc + (((int64_t)stream * J.ncif + q) * J.nsub + sub) * J.msc_stride + w);
+    return *(const uint32_t *)(msc_row(J.feed, stream, q, sub) + w);
 }
 __device__ __forceinline__ bool words_ok(const DpJob &J) {
-    return J.packed && (((uintptr_t)J.msc | (uintptr_t)J.msc_stride | (uintptr_t)J.ring) & 3) == 0;
+    return J.feed.packed && (((uintptr_t)J.feed.msc | (uintptr_t)J.feed.msc_stride | (uintptr_t)J.ring) & 3) == 0;
 }
 // the window's fsz bytes into LDS: every load of a lane in flight before its first store
 // (a load-store pair per byte would wait out one memory round trip per byte)
@@ -251,23 +239,6 @@ __device__ __forceinline__ void window_to_lds(const DpJob &J, const uint8_t *car
     }
 }
 
-// a * b in GF(2)[x] / (x^16 + x^12 + x^5 + 1)
-__device__ __forceinline__ uint32_t crc_mulmod(uint32_t a, uint32_t b) {
-    uint32_t r = 0;
-#pragma unroll
-    for (int k = 15; k >= 0; k--) {
-        r = ((r << 1) ^ ((r & 0x8000u) ? 0x1021u : 0u)) & 0xFFFFu;
-        if ((b >> k) & 1u) r ^= a;
-    }
-    return r;
-}
-
-__device__ __forceinline__ uint32_t wave_xor(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v ^= (uint32_t)__shfl_xor((int)v, o, 64);
-    return v;
-}
-
 // processSuperframe (mp4processor.cpp:146-292) of the candidate window ending at CIF cl of
 // (stream, DAB+ subchannel) sd, by one wave: RS(120,110) over the RSDims columns, the AU
 // table and AU CRCs.  The verdict (2 rejected, 3 decoded) goes to J.code, the record and,
@@ -279,9 +250,9 @@ __device__ __forceinline__ uint32_t wave_xor(uint32_t v) {
 __device__ void sf_decode(const DpJob &J, const GfTabs &g, int sd, int cl, uint8_t *sfb, uint32_t *syn_s,
                           uint8_t *rl, int32_t *red, int lane) {
     const int stream = sd / J.ndp, dp = sd - stream * J.ndp;
-    const int br = J.dp_br[sd], sub = J.dp_sub[sd];
+    const int br = J.map.br[sd], sub = J.map.sub[sd];
     const int RS = br / 8, nbytes = 3 * br, fsz = 120 * RS, end = 110 * RS;
-    uint8_t *code = J.code + (int64_t)sd * J.ncif + cl;
+    uint8_t *code = J.code + (int64_t)sd * J.feed.ncif + cl;
     const uint8_t *carry = J.ring + (int64_t)sd * (120 * DP_MAX_RS);
     window_to_lds(J, carry, stream, sub, nbytes, cl, fsz, sfb, lane);
     for (int p = lane; p < 10 * RS; p += 64) syn_s[p] = 0;
@@ -380,7 +351,7 @@ __device__ void sf_decode(const DpJob &J, const GfTabs &g, int sd, int cl, uint8
                 const uint32_t b = k < limit ? sfb[ai + k] : 0u;
                 acc = ((acc << 8) ^ g.crc[((acc >> 8) ^ b) & 0xFFu]) & 0xFFFFu;
             }
-            if (acc) acc = crc_mulmod(acc, g.pow8[len - k1]);
+            if (acc) acc = crc16::mulmod(acc, g.pow8[len - k1]);
             acc = wave_xor(acc);
             const uint32_t hi = len < limit ? sfb[ai + len] : 0u, lo = len + 1 < limit ? sfb[ai + len + 1] : 0u;
             if (((~((hi << 8) | lo) & 0xFFFFu) ^ acc) == 0) mask |= 1u << i;
@@ -390,11 +361,11 @@ __device__ void sf_decode(const DpJob &J, const GfTabs &g, int sd, int cl, uint8
     }
     if (ok) {
         info.status = 3;
-        uint8_t *o = J.sf_out + (((int64_t)stream * J.ncif + cl) * J.ndp + dp) * J.sf_stride;
+        uint8_t *o = J.sf_out + (((int64_t)stream * J.feed.ncif + cl) * J.ndp + dp) * J.sf_stride;
         for (int i = lane; i < end; i += 64) o[i] = sfb[i];
     }
     if (lane == 0) {
-        J.info[((int64_t)stream * J.ncif + cl) * J.ndp + dp] = info;
+        J.info[((int64_t)stream * J.feed.ncif + cl) * J.ndp + dp] = info;
         *code = (uint8_t)info.status;
     }
 }
@@ -406,9 +377,9 @@ __device__ void sf_decode(const DpJob &J, const GfTabs &g, int sd, int cl, uint8
 // the next run.  nc: LDS [4 * 3 * 384]
 __device__ void dp_walk(const DpJob &J, int sd, uint8_t *nc, int lane) {
     const int stream = sd / J.ndp, dp = sd - stream * J.ndp;
-    const int br = J.dp_br[sd], sub = J.dp_sub[sd], nbytes = 3 * br;
+    const int br = J.map.br[sd], sub = J.map.sub[sd], nbytes = 3 * br;
     if (sub < 0) {                                       // absent slot: status -1 records, no state
-        for (int cl = lane; cl < J.ncif; cl += 64) {
+        for (int cl = lane; cl < J.feed.ncif; cl += 64) {
             dabgpu_superframe info;
             info.status = -1;
             info.num_aus = 0;
@@ -416,22 +387,22 @@ __device__ void dp_walk(const DpJob &J, int sd, uint8_t *nc, int lane) {
             for (int i = 0; i < 7; i++) info.au_start[i] = 0;
             info.au_crc_ok = 0;
             info.reserved = J.sf_compact ? 0xFF : 0;
-            J.info[((int64_t)stream * J.ncif + cl) * J.ndp + dp] = info;
+            J.info[((int64_t)stream * J.feed.ncif + cl) * J.ndp + dp] = info;
         }
         return;
     }
     DpState st = J.state[sd];
-    const uint8_t *code = J.code + (int64_t)sd * J.ncif;
-    const int nd = J.ncifs[stream];                     // CIFs this stream delivered
-    const int64_t cif0 = J.cif0s[stream] - J.dp_since[sd];   // CIF index counted from the entry's since_cif
-    for (int c0 = 0; c0 < J.ncif; c0 += 64) {
+    const uint8_t *code = J.code + (int64_t)sd * J.feed.ncif;
+    const int nd = J.feed.ncifs[stream];                // CIFs this stream delivered
+    const int64_t rel0 = rel_cif(J.feed, J.map, sd, stream);
+    for (int c0 = 0; c0 < J.feed.ncif; c0 += 64) {
         const int cl = c0 + lane;
-        const int v = cl < J.ncif ? code[cl] : 0;
+        const int v = cl < J.feed.ncif ? code[cl] : 0;
         int fs = 0;
-        const int nc = min(64, J.ncif - c0);
+        const int nc = min(64, J.feed.ncif - c0);
         for (int i = 0; i < nc; i++) {                  // uniform
             int s;
-            if (c0 + i >= nd || cif0 + c0 + i < 16) {
+            if (!fed(sub, nd, rel0, c0 + i)) {
                 s = -1;                                  // not delivered (warm-up, or past the stream's CIFs)
             } else {
                 st.blocks++;
@@ -445,7 +416,7 @@ __device__ void dp_walk(const DpJob &J, int sd, uint8_t *nc, int lane) {
             }
             if (lane == i) fs = s;
         }
-        if (cl < J.ncif && fs < 2) {
+        if (cl < J.feed.ncif && fs < 2) {
             dabgpu_superframe info;
             info.status = (int8_t)fs;
             info.num_aus = 0;
@@ -453,7 +424,7 @@ __device__ void dp_walk(const DpJob &J, int sd, uint8_t *nc, int lane) {
             for (int i = 0; i < 7; i++) info.au_start[i] = 0;
             info.au_crc_ok = 0;
             info.reserved = 0;
-            J.info[((int64_t)stream * J.ncif + cl) * J.ndp + dp] = info;
+            J.info[((int64_t)stream * J.feed.ncif + cl) * J.ndp + dp] = info;
         }
     }
     // carry = the stream's last 4 delivered CIFs (oldest first); with fewer than 4 new
@@ -467,8 +438,7 @@ __device__ void dp_walk(const DpJob &J, int sd, uint8_t *nc, int lane) {
             v[k] = 0;
             if (p < 4 * nbytes) {
                 const int b = p / nbytes, w = p - b * nbytes, q = nd - 4 + b;
-                const uint8_t *src = J.msc + (((int64_t)stream * J.ncif + (q >= 0 ? q : 0)) * J.nsub + sub) * J.msc_stride;
-                v[k] = q >= 0 ? (J.packed ? src[w] : pack_byte(src, w)) : carry[(q + 4) * nbytes + w];
+                v[k] = q >= 0 ? row_byte(msc_row(J.feed, stream, q, sub), J.feed.packed, w) : carry[(q + 4) * nbytes + w];
             }
         }
 #pragma unroll
@@ -507,12 +477,13 @@ __global__ __launch_bounds__(64 * DP_WAVES) void k_dp_layer(DpJob J, int c0, int
     __shared__ int32_t nlist;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, sd = blockIdx.x;
     const int stream = sd / J.ndp, dp = sd - stream * J.ndp;
-    const int br = J.dp_br[sd], sub = J.dp_sub[sd], nbytes = 3 * br;
+    const int br = J.map.br[sd], sub = J.map.sub[sd], nbytes = 3 * br;
     if (sub < 0) {                                       // absent slot (the whole workgroup): status -1 records
         if (w == 0 && last) dp_walk(J, sd, sfb[1], lane);
         return;
     }
-    const int64_t since = J.dp_since[sd];
+    const int nfed = J.feed.ncifs[stream];
+    const int64_t rel0 = rel_cif(J.feed, J.map, sd, stream);
     const uint32_t *tabs32 = (const uint32_t *)J.tabs;
     for (int i = t; i < (int)sizeof(GfTabs) / 4; i += 64 * DP_WAVES) ((uint32_t *)&g)[i] = tabs32[i];
     if (t == 0) nlist = 0;
@@ -520,15 +491,16 @@ __global__ __launch_bounds__(64 * DP_WAVES) void k_dp_layer(DpJob J, int c0, int
     const uint8_t *carry = J.ring + (int64_t)sd * (120 * DP_MAX_RS);
     for (int cl = c0 + t; cl < c1; cl += 64 * DP_WAVES) {
         // a window holding an undelivered CIF (de-interleaver warm-up, or a CIF slot the
-        // stream did not fill in this run) is never evaluated
-        bool ok = !(cl >= J.ncifs[stream] || J.cif0s[stream] + cl - 4 - since < 16);
+        // stream did not fill in this run) is never evaluated: its CIFs are delivered when
+        // its newest and its oldest are
+        bool ok = fed(sub, nfed, rel0, cl) && fed(sub, nfed, rel0, cl - 4);
         if (ok) {
             uint32_t x[11];
 #pragma unroll
             for (int p = 0; p < 11; p++) x[p] = window_byte(J, carry, stream, sub, nbytes, cl, p);
             ok = fire_ok(x, g.fire);
         }
-        J.code[(int64_t)sd * J.ncif + cl] = ok ? 1 : 0;
+        J.code[(int64_t)sd * J.feed.ncif + cl] = ok ? 1 : 0;
         if (ok) list[atomicAdd(&nlist, 1)] = (int16_t)(cl - c0);
     }
     __syncthreads();
@@ -548,9 +520,9 @@ __global__ __launch_bounds__(64 * DP_WAVES) void k_dp_layer(DpJob J, int c0, int
     __syncthreads();                                     // the walk's records are written
     if (w == 0) {
         int k = 0;
-        for (int c0 = 0; c0 < J.ncif; c0 += 64) {
+        for (int c0 = 0; c0 < J.feed.ncif; c0 += 64) {
             const int cl = c0 + lane;
-            dabgpu_superframe *r = cl < J.ncif ? &J.info[((int64_t)stream * J.ncif + cl) * J.ndp + dp] : nullptr;
+            dabgpu_superframe *r = cl < J.feed.ncif ? &J.info[((int64_t)stream * J.feed.ncif + cl) * J.ndp + dp] : nullptr;
             const bool dec = r && r->status == 3;
             const uint64_t bal = __ballot(dec);
             const int kk = k + __popcll(bal & ((1ull << lane) - 1ull));
@@ -567,20 +539,21 @@ __global__ __launch_bounds__(64 * DP_WAVES) void k_dp_layer(DpJob J, int c0, int
     __syncthreads();
     const int nk = nlist, end = 110 * (br / 8);
     for (int q = w; q < nk; q += DP_WAVES) {             // a wave per superframe, a byte per lane
-        const uint8_t *src = J.sf_out + (((int64_t)stream * J.ncif + list[q]) * J.ndp + dp) * J.sf_stride;
+        const uint8_t *src = J.sf_out + (((int64_t)stream * J.feed.ncif + list[q]) * J.ndp + dp) * J.sf_stride;
         uint8_t *dst = J.sf_compact + ((int64_t)sd * J.kmax + q) * J.sf_stride;
         for (int i = lane; i < end; i += 64) dst[i] = src[i];
     }
 }
 
 hipError_t launch_dabplus(hipStream_t st, const DpJob &job) {
-    if (job.ndp <= 0 || job.nstreams <= 0) return hipSuccess;
-    if (job.ncif < 4) return hipErrorInvalidValue;       // the carry holds the last 4 CIFs
-    if (job.sf_compact && job.ncif > DP_LIST) return hipErrorInvalidValue;   // the list holds the run's superframes
-    for (int c0 = 0; c0 < job.ncif; c0 += DP_LIST) {
-        const int c1 = c0 + DP_LIST < job.ncif ? c0 + DP_LIST : job.ncif;
-        hipLaunchKernelGGL(k_dp_layer, dim3(job.nstreams * job.ndp), dim3(64 * DP_WAVES), 0, st, job, c0, c1,
-                           c1 == job.ncif ? 1 : 0);
+    if (job.ndp <= 0 || job.feed.nstreams <= 0) return hipSuccess;
+    const int ncif = job.feed.ncif;
+    if (ncif < 4) return hipErrorInvalidValue;            // the carry holds the last 4 CIFs
+    if (job.sf_compact && ncif > DP_LIST) return hipErrorInvalidValue;   // the list holds the run's superframes
+    for (int c0 = 0; c0 < ncif; c0 += DP_LIST) {
+        const int c1 = c0 + DP_LIST < ncif ? c0 + DP_LIST : ncif;
+        hipLaunchKernelGGL(k_dp_layer, dim3(job.feed.nstreams * job.ndp), dim3(64 * DP_WAVES), 0, st, job, c0, c1,
+                           c1 == ncif ? 1 : 0);
     }
     return hipGetLastError();
 }

@@ -128,15 +128,6 @@ __device__ __forceinline__ void mp2_quant(int q, int &lev, int &grouped, int &cw
     }
 }
 
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int n = __shfl_up(v, d);
-        if (lane >= d) v += n;
-    }
-    return v;
-}
-
 // side information of one frame, per lane l = 2 * subband + channel
 struct Mp2Side {
     int32_t sf[64][3];      // the scale factor of each part, resolved (mp2processor.cpp:311-316)
@@ -181,7 +172,7 @@ __device__ __forceinline__ void mp2_parse(const uint8_t *__restrict__ f, int len
     // allocation
     const int bd = live ? T->band[table][sb] : 0;
     int w = own ? bd >> 4 : 0;
-    int inc = wave_incl_scan(w, lane);
+    int inc = wave_scan_incl(w, lane);
     int a = own ? (int)mp2_bits(f, len, pos + inc - w, w) : 0;
     const int a0 = __shfl(a, lane & ~1);
     if (live && !own) a = a0;
@@ -190,12 +181,12 @@ __device__ __forceinline__ void mp2_parse(const uint8_t *__restrict__ f, int len
     // scale factor selection, then the scale factors it announces
     const bool reads = live && q && ch < nch;
     w = reads ? 2 : 0;
-    inc = wave_incl_scan(w, lane);
+    inc = wave_scan_incl(w, lane);
     int si = reads ? (int)mp2_bits(f, len, pos + inc - w, 2) : 0;
     pos += __shfl(inc, 63);
     const int nsf = reads ? (si == 0 ? 3 : si == 2 ? 1 : 2) : 0;
     w = 6 * nsf;
-    inc = wave_incl_scan(w, lane);
+    inc = wave_scan_incl(w, lane);
     int s0 = 0, s1 = 0, s2 = 0;
     if (reads) {
         const int p0 = pos + inc - w;
@@ -210,7 +201,7 @@ __device__ __forceinline__ void mp2_parse(const uint8_t *__restrict__ f, int len
     int lev = 0, grouped = 0, cw = 0;
     if (q) mp2_quant(q, lev, grouped, cw);
     w = (own && q) ? (grouped ? cw : 3 * cw) : 0;
-    inc = wave_incl_scan(w, lane);
+    inc = wave_scan_incl(w, lane);
     S.spos[lane] = (int16_t)(inc - w);
     S.q[lane] = (uint8_t)((own && q) ? q : 0);
     const int sv[3] = {s0, s1, s2};
@@ -391,10 +382,6 @@ __global__ __launch_bounds__(MP2_THREADS) void k_mp2_decode(Mp2Job J) {
 // ---- the frame synchroniser ----------------------------------------------------------
 constexpr int MP2_MAX_FRAME = 6 * 384;      // bytes: 2 * 24 * bitRate bits at 384 kbit/s
 
-__device__ __forceinline__ uint32_t msc_bit(const uint8_t *__restrict__ row, int packed, int i) {
-    return packed ? (row[i >> 3] >> (7 - (i & 7))) & 1u : row[i] & 1u;
-}
-
 // addbittoMP2 for m bits at once: bits [i, i + m) of the CIF's row to bits [bc, bc + m) of the
 // frame being collected, each lane one byte of the frame
 __device__ __forceinline__ void mp2_take(uint8_t *part, int bc, const uint8_t *__restrict__ row, int packed, int i, int m,
@@ -404,7 +391,7 @@ __device__ __forceinline__ void mp2_take(uint8_t *part, int bc, const uint8_t *_
 #pragma unroll
         for (int b = 0; b < 8; b++) {
             const int d = 8 * k + b;
-            if (d >= bc && d < bc + m) byte = (byte & ~(0x80u >> b)) | (msc_bit(row, packed, i + d - bc) << (7 - b));
+            if (d >= bc && d < bc + m) byte = (byte & ~(0x80u >> b)) | (row_bit(row, packed, i + d - bc) << (7 - b));
         }
         part[k] = (uint8_t)byte;
     }
@@ -420,30 +407,32 @@ __global__ __launch_bounds__(64) void k_mp2_sync(Mp2SyncJob J) {
     __shared__ uint8_t part[MP2_MAX_FRAME];
     const int chain = blockIdx.x, lane = threadIdx.x;
     const int s = chain / J.nmp, m = chain % J.nmp;
-    const int sub = J.mp_sub[chain];
-    const int nb = 24 * J.mp_br[chain];
+    const MscFeed &F = J.feed;
+    const int sub = J.map.sub[chain], nfed = F.ncifs[s];
+    const int64_t rel0 = rel_cif(F, J.map, chain, s);
+    const int nb = 24 * J.map.br[chain];
     Mp2SyncState st = J.state[chain];
     uint8_t *carried = J.part + (int64_t)chain * J.fstride;
     if (sub >= 0)
         for (int k = lane; k < J.fstride; k += 64) part[k] = carried[k];
     __syncthreads();
-    for (int c = 0; c < J.ncif; c++) {
-        const int64_t o = ((int64_t)s * J.ncif + c) * J.nmp + m;
-        const bool fed = sub >= 0 && c < J.ncifs[s] && J.cif0s[s] + c - J.mp_since[chain] >= 16;
+    for (int c = 0; c < F.ncif; c++) {
+        const int64_t o = ((int64_t)s * F.ncif + c) * J.nmp + m;
+        const bool on = fed(sub, nfed, rel0, c);
         int emitted = 0, rate = 0;
-        if (fed) {
-            const uint8_t *row = J.msc + (((int64_t)s * J.ncif + c) * J.nsub + sub) * J.msc_stride;
+        if (on) {
+            const uint8_t *row = msc_row(F, s, c, sub);
             const int lf = st.half_rate ? 2 * nb : nb;
             int i = 0;
             while (i < nb) {
                 if (st.ok == 2) {
                     const int mm = max(1, min(nb - i, lf - st.bc));
-                    mp2_take(part, st.bc, row, J.packed, i, mm, lane);
+                    mp2_take(part, st.bc, row, F.packed, i, mm, lane);
                     __syncthreads();
                     st.bc += mm;
                     i += mm;
                     if (st.bc >= lf) {
-                        uint8_t *f = J.frames + ((int64_t)chain * J.ncif + c) * J.fstride;
+                        uint8_t *f = J.frames + ((int64_t)chain * F.ncif + c) * J.fstride;
                         for (int k = lane; k < J.fstride; k += 64) f[k] = k < (lf >> 3) ? part[k] : (uint8_t)0;
                         __syncthreads();
                         emitted = 1;
@@ -452,7 +441,7 @@ __global__ __launch_bounds__(64) void k_mp2_sync(Mp2SyncJob J) {
                     }
                 } else if (st.ok == 0) {
                     const int n = min(48, nb - i);
-                    const uint32_t bit = lane < n ? msc_bit(row, J.packed, i + lane) : 0u;
+                    const uint32_t bit = lane < n ? row_bit(row, F.packed, i + lane) : 0u;
                     const uint64_t mask = __ballot(bit != 0);
                     const uint64_t ext = ((1ull << st.hc) - 1ull) | (mask << st.hc);     // the carried ones, then the bits
                     const uint64_t x2 = (ext & ext >> 1) & (ext & ext >> 1) >> 2;
@@ -474,7 +463,7 @@ __global__ __launch_bounds__(64) void k_mp2_sync(Mp2SyncJob J) {
                     }
                 } else {
                     const int mm = min(24 - st.bc, nb - i);
-                    mp2_take(part, st.bc, row, J.packed, i, mm, lane);
+                    mp2_take(part, st.bc, row, F.packed, i, mm, lane);
                     __syncthreads();
                     st.bc += mm;
                     i += mm;
@@ -488,10 +477,10 @@ __global__ __launch_bounds__(64) void k_mp2_sync(Mp2SyncJob J) {
             }
         }
         if (lane == 0) {
-            J.info[o].status = fed ? emitted : -1;
+            J.info[o].status = on ? emitted : -1;
             J.info[o].sample_rate = rate;
             J.info[o].frame_bytes = 0;
-            J.present[(int64_t)chain * J.ncif + c] = (uint8_t)emitted;
+            J.present[(int64_t)chain * F.ncif + c] = (uint8_t)emitted;
         }
     }
     __syncthreads();
@@ -501,9 +490,9 @@ __global__ __launch_bounds__(64) void k_mp2_sync(Mp2SyncJob J) {
 }
 
 hipError_t launch_mp2_sync(hipStream_t st, const Mp2SyncJob &job) {
-    if (job.nmp <= 0 || job.nstreams <= 0 || job.ncif <= 0) return hipSuccess;
+    if (job.nmp <= 0 || job.feed.nstreams <= 0 || job.feed.ncif <= 0) return hipSuccess;
     if (job.fstride <= 0 || job.fstride > MP2_MAX_FRAME) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_mp2_sync, dim3(job.nstreams * job.nmp), dim3(64), 0, st, job);
+    hipLaunchKernelGGL(k_mp2_sync, dim3(job.feed.nstreams * job.nmp), dim3(64), 0, st, job);
     return hipGetLastError();
 }
 

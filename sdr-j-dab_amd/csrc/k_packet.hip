@@ -16,7 +16,9 @@
 //   k_pkt_copy      one wave per (stream, slot, CIF) and one for the carried bytes: the bytes of
 //                   completed groups to the arena, those of the series in flight to the carry
 //   k_pkt_groups    a wave per completed group: its CRC (the same CRC by linearity over 64
-//                   lanes) and the header fields
+//                   lanes, msc_feed.h's wave_crc16) and the header fields
+// The delivery rule, the row address and the row reader are msc_feed.h's, the CRC arithmetic
+// crc16_poly.h's.
 // Only the packetState, the address latch, the 500-packet window and the bytes of the series
 // in flight cross CIFs.  msc_bits_d is only read: check_CRC_bits' in-place inversion of a
 // packet's CRC field is applied where a copy reads it (useful length past the data field).
@@ -27,73 +29,17 @@ namespace dab {
 
 constexpr int PK_MAX_ROW = 24 * PK_MAX_CELLS;     // bytes of a CIF at 384 kbit/s
 
-// ---- CRC-16-CCITT (x^16 + x^12 + x^5 + 1) as polynomial arithmetic -----------------------
-__host__ __device__ constexpr uint32_t pk_mulmod(uint32_t a, uint32_t b) {       // a * b mod P
-    uint32_t r = 0;
-    for (int i = 15; i >= 0; i--) {
-        r <<= 1;
-        if (r & 0x10000u) r ^= 0x11021u;
-        if ((b >> i) & 1u) r ^= a;
-    }
-    return r;
-}
-__host__ __device__ constexpr uint32_t pk_xpow8(int n) {                         // x^(8 n) mod P
-    uint32_t r = 1, b = 0x100;
-    for (; n; n >>= 1) {
-        if (n & 1) r = pk_mulmod(r, b);
-        b = pk_mulmod(b, b);
-    }
-    return r;
-}
-// the register after one more byte (the message times x^16, from whatever it held)
-__device__ __forceinline__ uint32_t pk_crc_byte(uint32_t crc, uint32_t b) {
-    crc = ((crc >> 8) | (crc << 8)) & 0xFFFFu;
-    crc ^= b;
-    crc ^= (crc & 0xFFu) >> 4;
-    crc ^= (crc << 12) & 0xFFFFu;
-    crc ^= (crc & 0xFFu) << 5;
-    return crc;
-}
-// check_CRC_bits inverts the last 16 bits and wants a zero register: the register over the
-// bytes as they are must equal 0xFFFF * x^16
-constexpr uint32_t PK_CRC_GOOD = pk_mulmod(0xFFFFu, 0x1021u);
-constexpr uint32_t PK_X24 = pk_xpow8(24);          // one cell further
 // the all-ones start register after a packet of lc + 1 cells
 __device__ __forceinline__ uint32_t pk_ones(int lc) {
-    constexpr uint32_t o1 = pk_mulmod(0xFFFFu, pk_xpow8(24)), o2 = pk_mulmod(0xFFFFu, pk_xpow8(48)),
-                       o3 = pk_mulmod(0xFFFFu, pk_xpow8(72)), o4 = pk_mulmod(0xFFFFu, pk_xpow8(96));
+    constexpr uint32_t o1 = crc16::crc_ones(24), o2 = crc16::crc_ones(48), o3 = crc16::crc_ones(72), o4 = crc16::crc_ones(96);
     return lc == 0 ? o1 : lc == 1 ? o2 : lc == 2 ? o3 : o4;
 }
 
-__device__ __forceinline__ int pk_scan_excl(int v, int lane) {                   // exclusive prefix sum over the wave
-    int x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d);
-        if (lane >= d) x += y;
-    }
-    return x - v;
-}
 __device__ __forceinline__ int pk_top(uint64_t m) { return 63 - __builtin_clzll(m); }   // m != 0
 
 // the CIF's row as nbytes bytes in LDS
 __device__ __forceinline__ void pk_load_row(uint8_t *dst, const uint8_t *__restrict__ row, int packed, int nbytes, int lane) {
-    for (int k = lane; k < nbytes; k += 64) {
-        if (packed) {
-            dst[k] = row[k];
-        } else {
-            uint32_t b = 0;
-#pragma unroll
-            for (int i = 0; i < 8; i++) b = (b << 1) | (row[8 * k + i] & 1u);
-            dst[k] = (uint8_t)b;
-        }
-    }
-}
-__device__ __forceinline__ bool pk_fed(const PkJob &J, int e, int s, int c) {
-    return J.pk_sub[e] >= 0 && c < J.ncifs[s] && J.cif0s[s] + c - J.pk_since[e] >= 16;
-}
-__device__ __forceinline__ const uint8_t *pk_row(const PkJob &J, int e, int s, int c) {
-    return J.msc + (((int64_t)s * J.ncif + c) * J.nsub + J.pk_sub[e]) * J.msc_stride;
+    for (int k = lane; k < nbytes; k += 64) dst[k] = (uint8_t)row_byte(row, packed, k);
 }
 
 // record of a cell: bit 0 a packet starts here, 1 its CRC is good, 2-3 first/last,
@@ -101,14 +47,15 @@ __device__ __forceinline__ const uint8_t *pk_row(const PkJob &J, int e, int s, i
 __global__ __launch_bounds__(64) void k_pkt_scan(PkJob J) {
     __shared__ uint8_t row[PK_MAX_ROW];
     const int lane = threadIdx.x;
-    const int c = blockIdx.x % J.ncif, e = blockIdx.x / J.ncif, s = e / J.npk;
-    uint32_t *rec = J.rec + ((int64_t)e * J.ncif + c) * J.ncell;
-    if (!pk_fed(J, e, s, c)) {
+    const MscFeed &F = J.feed;
+    const int c = blockIdx.x % F.ncif, e = blockIdx.x / F.ncif, s = e / J.npk;
+    uint32_t *rec = J.rec + ((int64_t)e * F.ncif + c) * J.ncell;
+    if (!fed(F, J.map, e, s, c)) {
         if (lane < J.ncell) rec[lane] = 0;
         return;
     }
-    const int ncell = min((int)J.pk_br[e] >> 3, J.ncell);
-    pk_load_row(row, pk_row(J, e, s, c), J.packed, 24 * ncell, lane);
+    const int ncell = min((int)J.map.br[e] >> 3, J.ncell);
+    pk_load_row(row, msc_row(F, s, c, J.map.sub[e]), F.packed, 24 * ncell, lane);
     __syncthreads();
     const bool in = lane < ncell;
     const uint8_t *cell = row + 24 * (in ? lane : 0);
@@ -124,16 +71,17 @@ __global__ __launch_bounds__(64) void k_pkt_scan(PkJob J) {
     }
     uint32_t part = 0;
     if (in)
-        for (int i = 0; i < 24; i++) part = pk_crc_byte(part, cell[i]);
+        for (int i = 0; i < 24; i++) part = crc16::crc_byte(part, cell[i]);
     // a start lane gathers its packet's cells (all lanes shuffle, the packet's own are used)
     uint32_t crc = part;
     const bool st = (starts >> lane) & 1;
+    constexpr uint32_t x24 = crc16::xpow8(24);           // one cell further
 #pragma unroll
     for (int k = 1; k < 4; k++) {
         const uint32_t p = __shfl_down(part, k);
-        if (st && k <= lc) crc = pk_mulmod(crc, PK_X24) ^ p;
+        if (st && k <= lc) crc = crc16::mulmod(crc, x24) ^ p;
     }
-    const bool ok = (crc ^ pk_ones(lc)) == PK_CRC_GOOD;
+    const bool ok = (crc ^ pk_ones(lc)) == crc16::CRC_GOOD;
     if (lane < J.ncell) {
         uint32_t r = 0;
         if (st)
@@ -146,9 +94,9 @@ __global__ __launch_bounds__(64) void k_pkt_scan(PkJob J) {
 __global__ __launch_bounds__(64) void k_pkt_assemble(PkJob J) {
     const int lane = threadIdx.x, e = blockIdx.x, s = e / J.npk, j = e % J.npk;
     PkState st = J.state[e];
-    const int nbytes_row = 3 * J.pk_br[e];
+    const int nbytes_row = 3 * J.map.br[e];
     const uint64_t below = (1ull << lane) - 1ull;
-    int32_t *segtab = J.segtab + (int64_t)e * (1 + J.ncif * J.ncell);
+    int32_t *segtab = J.segtab + (int64_t)e * (1 + J.feed.ncif * J.ncell);
     dabgpu_datagroup *groups = J.groups + (int64_t)e * J.gslots;
     st.prev_state = st.state;
     st.prev_pending = st.pending;
@@ -156,17 +104,16 @@ __global__ __launch_bounds__(64) void k_pkt_assemble(PkJob J) {
     int ngroups = 0, nstored = 0, serial_next = 1, open_serial = 0;
     // what decides `fed` does not change over the run, and the next CIF's records are loaded
     // while this one's are worked on: the loop is a chain of latencies, nothing else
-    const bool present = J.pk_sub[e] >= 0;
-    const int nfed = J.ncifs[s];
-    const int64_t rel0 = J.cif0s[s] - J.pk_since[e];
-    const uint32_t *rec_e = J.rec + (int64_t)e * J.ncif * J.ncell;
+    const int sub = J.map.sub[e], nfed = J.feed.ncifs[s];
+    const int64_t rel0 = rel_cif(J.feed, J.map, e, s);
+    const uint32_t *rec_e = J.rec + (int64_t)e * J.feed.ncif * J.ncell;
     uint32_t rnext = lane < J.ncell ? rec_e[lane] : 0u;
-    for (int c = 0; c < J.ncif; c++) {
-        const bool fed = present && c < nfed && rel0 + c >= 16;
-        const int64_t cell0 = ((int64_t)e * J.ncif + c) * J.ncell;
-        dabgpu_packet_info *info = J.info + ((int64_t)s * J.ncif + c) * J.npk + j;
+    for (int c = 0; c < J.feed.ncif; c++) {
+        const bool on = fed(sub, nfed, rel0, c);
+        const int64_t cell0 = ((int64_t)e * J.feed.ncif + c) * J.ncell;
+        dabgpu_packet_info *info = J.info + ((int64_t)s * J.feed.ncif + c) * J.npk + j;
         const uint32_t r = rnext;                        // (k_pkt_scan wrote 0 for a CIF that is not fed)
-        if (c + 1 < J.ncif) rnext = lane < J.ncell ? rec_e[(int64_t)(c + 1) * J.ncell + lane] : 0u;
+        if (c + 1 < J.feed.ncif) rnext = lane < J.ncell ? rec_e[(int64_t)(c + 1) * J.ncell + lane] : 0u;
         const bool valid = r & 1u, ok = (r >> 1) & 1u;
         const int fl = (r >> 2) & 3, useful = (r >> 6) & 0x7F, addr = (r >> 13) & 0x3FF;
         const uint64_t V = __ballot(valid), BAD = __ballot(valid && !ok);
@@ -196,7 +143,7 @@ __global__ __launch_bounds__(64) void k_pkt_assemble(PkJob J) {
         const bool complete = act && ((fl == 3 && sb == 0) || (fl == 1 && sb == 1));
         const bool abort = act && sb == 1 && fl >= 2;
         const int n = takes ? min(useful, nbytes_row - (24 * lane + 3)) : 0;       // the copy stops at the CIF's end
-        const int E = pk_scan_excl(n, lane);
+        const int E = wave_scan_excl(n, lane);
         const int total = __shfl(E + n, 63);
         const uint64_t STARTS = __ballot(start), psb = STARTS & below;
         // the series open before this packet, and the one it feeds
@@ -207,7 +154,7 @@ __global__ __launch_bounds__(64) void k_pkt_assemble(PkJob J) {
         const int goff = start ? 0 : psb ? E - E_slb : st.pending + E;
         const int gtotal = goff + n;                                             // int32: no 4095-byte wrap
         const int gstored = complete ? min(gtotal, J.cap) : 0;
-        const int aoff = nstored + pk_scan_excl(gstored, lane);
+        const int aoff = nstored + wave_scan_excl(gstored, lane);
         const uint64_t COMPLETE = __ballot(complete);
         if (complete) {
             dabgpu_datagroup g = {};
@@ -237,7 +184,7 @@ __global__ __launch_bounds__(64) void k_pkt_assemble(PkJob J) {
         ngroups += __popcll(COMPLETE);
         nstored = __shfl(aoff + gstored, 63);
         if (lane == 0) {
-            info->status = fed ? 0 : -1;
+            info->status = on ? 0 : -1;
             info->packets = (int16_t)npk;
             info->crc_errors = (int16_t)__popcll(BAD);
             info->groups = (int16_t)__popcll(COMPLETE);
@@ -259,10 +206,10 @@ __global__ __launch_bounds__(64) void k_pkt_assemble(PkJob J) {
 __global__ __launch_bounds__(64) void k_pkt_copy(PkJob J) {
     __shared__ uint8_t row[PK_MAX_ROW];
     const int lane = threadIdx.x;
-    const int c = blockIdx.x % (J.ncif + 1), e = blockIdx.x / (J.ncif + 1), s = e / J.npk;
-    const int32_t *segtab = J.segtab + (int64_t)e * (1 + J.ncif * J.ncell);
+    const int c = blockIdx.x % (J.feed.ncif + 1), e = blockIdx.x / (J.feed.ncif + 1), s = e / J.npk;
+    const int32_t *segtab = J.segtab + (int64_t)e * (1 + J.feed.ncif * J.ncell);
     uint8_t *arena = J.bytes + (int64_t)e * J.arena, *carry = J.carry_out + (int64_t)e * J.cap;
-    if (c == J.ncif) {                                   // the bytes carried into the run
+    if (c == J.feed.ncif) {                                   // the bytes carried into the run
         const PkState st = J.state[e];
         const int fate = segtab[0], nn = min(st.prev_pending, J.cap);
         if (st.prev_state != 1 || fate == -1) return;
@@ -271,15 +218,15 @@ __global__ __launch_bounds__(64) void k_pkt_copy(PkJob J) {
         for (int i = lane; i < nn; i += 64) dst[i] = src[i];
         return;
     }
-    const int64_t cell0 = ((int64_t)e * J.ncif + c) * J.ncell;
+    const int64_t cell0 = ((int64_t)e * J.feed.ncif + c) * J.ncell;
     const int2 t = lane < J.ncell ? J.take[cell0 + lane] : make_int2(0, 0);
     const int n = t.x & 0x7F, goff = t.y;
     const int fate = n ? segtab[t.x >> 7] : -1;
     const int ncopy = fate == -1 ? 0 : max(0, min(n, J.cap - goff));             // the cap keeps the first bytes
     uint64_t M = __ballot(ncopy > 0);
     if (!M) return;
-    const int ncell = min((int)J.pk_br[e] >> 3, J.ncell);
-    pk_load_row(row, pk_row(J, e, s, c), J.packed, 24 * ncell, lane);
+    const int ncell = min((int)J.map.br[e] >> 3, J.ncell);
+    pk_load_row(row, msc_row(J.feed, s, c, J.map.sub[e]), J.feed.packed, 24 * ncell, lane);
     __syncthreads();
     const int64_t dsto = fate >= 0 ? (arena - J.bytes) + fate + goff : -1 - ((carry - J.carry_out) + goff);
     const int plen = 24 * (int)(((J.rec[cell0 + min(lane, J.ncell - 1)] >> 4) & 3u) + 1);
@@ -309,15 +256,7 @@ __global__ __launch_bounds__(64) void k_pkt_groups(PkJob J) {
         const uint32_t b0 = B(0);
         const bool ext = b0 & 0x80, crcf = b0 & 0x40, seg = b0 & 0x20, ua = b0 & 0x10;
         bool good = true;
-        if (crcf) {
-            const int m = (ns + 63) / 64, a = min(ns, lane * m), z = min(ns, a + m);
-            uint32_t part = 0;
-            for (int i = a; i < z; i++) part = pk_crc_byte(part, p[i]);
-            part = pk_mulmod(part, pk_xpow8(ns - z));
-#pragma unroll
-            for (int d = 32; d; d >>= 1) part ^= __shfl_xor(part, d);
-            good = ns >= 2 && !trunc && (part ^ pk_mulmod(0xFFFFu, pk_xpow8(ns))) == PK_CRC_GOOD;
-        }
+        if (crcf) good = ns >= 2 && !trunc && wave_crc16(p, ns, lane) == crc16::CRC_GOOD;   // (wave-uniform)
         if (lane) continue;
         int next = 2 + (ext ? 2 : 0);
         uint32_t last = 0, segno = 0, tidf = 0, tid = 0, li = 0;
@@ -347,15 +286,15 @@ __global__ __launch_bounds__(64) void k_pkt_groups(PkJob J) {
 }
 
 hipError_t launch_packet(hipStream_t st, const PkJob &J) {
-    if (J.npk <= 0 || J.nstreams <= 0 || J.ncif <= 0) return hipSuccess;
-    if (J.ncell <= 0 || J.ncell > PK_MAX_CELLS || J.cap <= 0 || J.gslots < J.ncif * J.ncell ||
-        J.arena < (int64_t)J.cap + (int64_t)J.ncif * J.ncell * 127)
+    if (J.npk <= 0 || J.feed.nstreams <= 0 || J.feed.ncif <= 0) return hipSuccess;
+    if (J.ncell <= 0 || J.ncell > PK_MAX_CELLS || J.cap <= 0 || J.gslots < J.feed.ncif * J.ncell ||
+        J.arena < (int64_t)J.cap + (int64_t)J.feed.ncif * J.ncell * 127)
         return hipErrorInvalidValue;
-    const int64_t ne = (int64_t)J.nstreams * J.npk;
-    if (ne * (J.ncif + 1) > 0x7FFFFFFF) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_pkt_scan, dim3((unsigned)(ne * J.ncif)), dim3(64), 0, st, J);
+    const int64_t ne = (int64_t)J.feed.nstreams * J.npk;
+    if (ne * (J.feed.ncif + 1) > 0x7FFFFFFF) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_pkt_scan, dim3((unsigned)(ne * J.feed.ncif)), dim3(64), 0, st, J);
     hipLaunchKernelGGL(k_pkt_assemble, dim3((unsigned)ne), dim3(64), 0, st, J);
-    hipLaunchKernelGGL(k_pkt_copy, dim3((unsigned)(ne * (J.ncif + 1))), dim3(64), 0, st, J);
+    hipLaunchKernelGGL(k_pkt_copy, dim3((unsigned)(ne * (J.feed.ncif + 1))), dim3(64), 0, st, J);
     hipLaunchKernelGGL(k_pkt_groups, dim3((unsigned)ne, 32), dim3(64), 0, st, J);
     return hipGetLastError();
 }

@@ -8,7 +8,8 @@
 // parallelism is handlers, one wave each (k_pad_walk), and inside a handler the lanes do what
 // is wide: they stage the PAD (up to 255 bytes) in LDS, move a sub-field's bytes (up to 48)
 // into the label text or the group buffer, take a completed group's CRC-16 over 64 slices
-// joined by x^(8d) shifts (the CRC is linear), and copy the group and the label snapshot out.
+// joined by x^(8d) shifts (the CRC is linear: msc_feed.h's wave_crc16 over crc16_poly.h's
+// arithmetic), and copy the group and the label snapshot out.
 // The state, 8.4 KB, lives in LDS for the pass: a workgroup of one wave, far below the CU's
 // 160 KB, so every handler of a C5-shaped call (256) is resident at once.  What is stateless in
 // a PAD -- the data stream element test, count, the F-PAD fields, the CI list, each sub-field's
@@ -21,36 +22,6 @@
 #include "dab_kernels.h"
 
 namespace dab {
-
-// ---- CRC-16-CCITT (x^16 + x^12 + x^5 + 1) as polynomial arithmetic (as k_packet.hip) --------
-__host__ __device__ constexpr uint32_t pad_mulmod(uint32_t a, uint32_t b) {      // a * b mod P
-    uint32_t r = 0;
-    for (int i = 15; i >= 0; i--) {
-        r <<= 1;
-        if (r & 0x10000u) r ^= 0x11021u;
-        if ((b >> i) & 1u) r ^= a;
-    }
-    return r;
-}
-__host__ __device__ constexpr uint32_t pad_xpow8(int n) {                        // x^(8 n) mod P
-    uint32_t r = 1, b = 0x100;
-    for (; n; n >>= 1) {
-        if (n & 1) r = pad_mulmod(r, b);
-        b = pad_mulmod(b, b);
-    }
-    return r;
-}
-__device__ __forceinline__ uint32_t pad_crc_byte(uint32_t crc, uint32_t b) {     // the register after one more byte
-    crc = ((crc >> 8) | (crc << 8)) & 0xFFFFu;
-    crc ^= b;
-    crc ^= (crc & 0xFFu) >> 4;
-    crc ^= (crc << 12) & 0xFFFFu;
-    crc ^= (crc & 0xFFu) << 5;
-    return crc;
-}
-// pad_crc complements the last two bytes and compares with the register from all ones: the
-// register over the bytes as they are, from zero, plus the preset's share must equal 0xFFFF * x^16
-constexpr uint32_t PAD_CRC_GOOD = pad_mulmod(0xFFFFu, 0x1021u);
 
 __device__ __forceinline__ int pad_sublen(uint32_t ci) {                         // mapLength (:86-95)
     const int k = (int)(ci >> 5);
@@ -188,13 +159,8 @@ __global__ __launch_bounds__(64) void k_pad_walk(PadJob J) {
                 touched |= 4u;
                 good = false;
             } else {
-                const int m = (length + 63) / 64, a = min(length, lane * m), z = min(length, a + m);
-                uint32_t part = 0;
-                for (int i = a; i < z; i++) part = pad_crc_byte(part, S.buffer[i]);
-                part = pad_mulmod(part, pad_xpow8(length - z));
-#pragma unroll
-                for (int d = 32; d; d >>= 1) part ^= __shfl_xor(part, d);
-                good = (part ^ pad_mulmod(0xFFFFu, pad_xpow8(length))) == PAD_CRC_GOOD;
+                // pad_crc complements the last two bytes and compares with the register from all ones
+                good = wave_crc16(S.buffer, length, lane) == crc16::CRC_GOOD;
             }
             if (!good) crc_failed++;
         }

@@ -211,14 +211,14 @@ def _feeder(plan):
 
     def craft(L, msc, ev):
         for (s, k), (br, rows) in plan.items():
-            for q in range(4 * F):
+            for q in range(4 * L.F):
                 if not ev[s, q, k]:
                     continue
                 row = rows[pos[(s, k)]] if pos[(s, k)] < len(rows) else np.zeros(3 * br, np.uint8)
                 pos[(s, k)] += 1
                 piece = np.ascontiguousarray(row if L.packed else np.unpackbits(row))
                 msc[s, q, k, :len(piece)] = piece
-                L.pipe.msc_d.upload_at(piece, (((s * 4 * F + q) * L.pipe.max_subch) + k) * L.pipe.msc_stride)
+                L.pipe.msc_d.upload_at(piece, (((s * 4 * L.F + q) * L.pipe.max_subch) + k) * msc.shape[-1])   # (the row stride of the format)
         return msc
     return craft, pos
 
@@ -279,6 +279,51 @@ def test_pipeline_crafted_rows(ctx, tx_iq, kat):  # noqa: F811
         assert ((rec["nbytes"] > 4095) & ((rec["flags"] & pp.ACCEPTED) != 0)).any()       # rule 2: no int16 wrap
     finally:
         L.close()
+
+
+SMALL = [(0, 6, 8, 0o103, 0, 8), (6, 12, 16, 0o103, 0, 8)]
+
+
+def test_pipeline_smallest_rows_both_formats(ctx):
+    """the smallest rows the shared row reader and delivery rule see: one stream, runs of one frame,
+    a packet-mode entry at 8 kbit/s (one 24-byte cell per CIF) and one at 16 kbit/s, crafted rows
+    (the golden lengths8 fixture; groups with a CRC cut into 24- and 48-byte packets, one of them
+    with a bad group CRC), six runs: the four of the 16-CIF warm-up, where nothing is fed, and two
+    behind it.  Once one bit per byte and once packed: info, run and group records and the bytes
+    are equal between the formats and equal the restatement's (Layer.run)."""
+    from dabamd.synth import Ensemble, PACKET
+    e = Ensemble(7, subch=[(0, 6, 8, 0o103, 0, 0, PACKET), (6, 12, 16, 0o103, 0, 0, PACKET)], figs=True)
+    iq = [e.generate(414, truth=False)["iq"]]
+    rows8 = [f for f in pp.fixtures() if f["name"] == "lengths8"][0]["rows"]
+    rng = np.random.default_rng(16)
+    pk = []
+    for n, good in ((40, True), (30, False), (21, True)):
+        pk += pp.packetize(pp.group(pp._bytes(rng, n), crcf=1, seg=1, segno=n, good=good), 77, [0, 1])
+    rows16 = pp.rows(pk, 16)
+    assert len(rows16) <= 8 <= len(rows8)
+    res = []
+    for packed in (False, True):
+        craft, pos = _feeder({(0, 0): (8, list(rows8)), (0, 1): (16, list(rows16))})
+        L = Layer(ctx, iq, _subs(SMALL), packed=packed, frames=1, audio=False)
+        try:
+            for _ in range(6):
+                L.run(craft)
+            assert pos == {(0, 0): 8, (0, 1): 8} and L.fed == {(0, 0): 8, (0, 1): 8}
+            res.append((L.out, L.asm))
+        finally:
+            L.close()
+    (oa, asm), (ob, _) = res
+    for r in range(6):
+        assert np.array_equal(oa[r][3], ob[r][3]) and np.array_equal(oa[r][2], ob[r][2])
+        assert (oa[r][3][0, :, :2]["status"] == (-1 if r < 4 else 0)).all(), (r, oa[r][3][0, :, :2]["status"])
+        for j in range(2):
+            n, nb = oa[r][2][0, j]["n_groups"], oa[r][2][0, j]["n_bytes"]
+            assert np.array_equal(oa[r][1][0, j, :n], ob[r][1][0, j, :n])
+            assert np.array_equal(oa[r][0][0, j, :nb], ob[r][0][0, j, :nb])
+    rec = {j: np.concatenate([o[1][0, j, :o[2][0, j]["n_groups"]] for o in oa]) for j in range(2)}
+    print("smallest rows: groups per entry", {j: len(rec[j]) for j in rec})
+    assert len(rec[0]) == 2                                 # lengths8's packets 0 and 4: the 24-byte ones
+    assert ((rec[1]["flags"] & pp.ACCEPTED) != 0).tolist() == [True, False, True]     # by the group CRC
 
 
 def test_pipeline_cap(ctx, tx_iq):
